@@ -6,6 +6,7 @@
   python bench.py --mask blob                           (BASELINE configs[3]: foreground_edit masks, its own JSON line)
   python bench.py --logit-scale 6                       (peaked softmax rows: prices the attention kernel's rescale path inside the step)
   python bench.py --emulate-rank 8                      (ONE process runs one rank's share of an 8-GPU step; collectives = device copies)
+  python bench.py --dump-outputs DIR                    (the latents the last timed step returned -> DIR/latents.npy: two builds, same inputs)
 
 Workload (BASELINE config 2): Wan2.2-Fun-5B-FLEXAM DiT (dim 3072, 24 heads x 128, ffn 14336,
 30 layers, 5.03 B parameters, random-init bf16), 97x512x896 -> latent [1,48,25,32,56], L = 11648 tokens
@@ -43,6 +44,29 @@ from benchlib.inputs import (PEAK_BF16_TFLOPS, PEAK_FP8_TFLOPS, PEAK_HBM_GBS, bl
                              set_logit_scale, synthetic_inputs)
 from benchlib.launch import launch_ranks, multi_gpu_check, visible_gpus_without_hip  # noqa: E402,F401
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, directory):
+    """--dump-outputs: every host tensor of `outputs` as <directory>/<name>.npy in float32, DUMP_BYTES at most in all.  An array larger
+    than its share is written as a sample instead: <name>_sample.npy holds the values at seeded flat positions, <name>_sample_index.npy
+    those positions (float64, exact below 2**53) -- the same positions on every run with the same arguments.  Returns {file: shape}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // len(outputs) - 1024                    # (room for the .npy headers)
+    written = {}
+    for name, t in outputs.items():
+        a = t.numpy().astype(np.float32, copy=False)
+        arrays = {name: a}
+        if a.nbytes > share:
+            k = share // (4 + 8)                                  # a float32 value and a float64 position per sampled element
+            pos = np.sort(np.random.default_rng(0).choice(a.size, k, replace=False))
+            arrays = {f"{name}_sample": a.reshape(-1)[pos], f"{name}_sample_index": pos.astype(np.float64)}
+        for n, v in arrays.items():
+            np.save(os.path.join(directory, n + ".npy"), v)
+            written[n + ".npy"] = list(v.shape)
+    return {"dir": directory, "arrays": written}
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -75,7 +99,12 @@ def main():
                          "copies on a side stream -> `emulated_ranks` / `predicted_scaling_no_comm` (benchlib/emulate.py); default: 8 on the headline "
                          "workload (a few seconds, after the timed region), off on the variant lines; 0 = off")
     ap.add_argument("--emulate-which", type=int, default=None, help="which rank of the sequence-parallel group to emulate (default: a middle chunk)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (the latents) as DIR/<name>.npy in float32, "
+                         "at most 64 MB in all (a fixed seeded sample of a larger array); the inputs are seeded, so two builds compare output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args, os.path.abspath(__file__))      # does not return
@@ -163,6 +192,11 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     finite = bool(torch.isfinite(pipe._state["latents"]).all())
+
+    def last_step_outputs():
+        # what denoise_step hands its caller: the latents, updated in place by every later step, so copied to the host now
+        return {"latents": pipe._state["latents"].float().cpu()} if args.dump_outputs and rank == 0 else None
+    outputs = last_step_outputs()
     rows_u = int(pipe._state["U"])
     # host side of a step: how long Python + ctypes need to ENQUEUE one step's ~420 launches (the GPU is idle-free while this
     # stays below the step's GPU time; at N ranks the GPU time shrinks N-fold, the enqueue time does not)
@@ -223,6 +257,7 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             elapsed = float(tt.item())
             finite = bool(torch.isfinite(pipe._state["latents"]).all())
+            outputs = last_step_outputs()
             check = multi_gpu_check(pipe, model, inp, cond, (args.warmup + args.steps) % total_steps, total_steps, world, rank)
     eng_sage = bool(getattr(eng, "sage_taken", False))          # what the engine DID (SAGE_ATTENTION is ignored under sequence parallelism)
     base = None
@@ -416,6 +451,8 @@ def main():
                                       + (f"profiles/{pmc}" if pmc else "no PMC table committed"))
         if base is not None:
             result["cpu_baseline"] = base
+        if outputs is not None:
+            result["dump_outputs"] = dump_outputs(outputs, args.dump_outputs)
         print(json.dumps(result))
     if world > 1:
         dist.barrier()

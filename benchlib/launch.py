@@ -61,21 +61,24 @@ def multi_gpu_check(pipe, model, inp, cond, step_index, total_steps, world, rank
 def visible_gpus_without_hip():
     """GPUs this process may use, counted from the KFD topology in sysfs (nodes with SIMDs), cut by HIP_VISIBLE_DEVICES /
     ROCR_VISIBLE_DEVICES when they are plain index lists.  No HIP / HSA call: the launcher must not initialise the runtime before
-    it starts the ranks (torch.cuda.device_count() only avoids HIP while its amdsmi path works).  None when sysfs says nothing."""
+    it starts the ranks (torch.cuda.device_count() only avoids HIP while its amdsmi path works).  A node whose properties this
+    process may not read (a container given some of the host's GPUs: EPERM on the others) is not counted -- the runtime enumerates
+    its agents from the same files.  None when sysfs says nothing."""
     import glob
     n = 0
     if not os.path.isdir("/sys/class/kfd"):
         return 0                                     # no KFD driver: no AMD GPU on this host
-    nodes = glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties")
-    if not nodes:
-        return None
-    for f in nodes:
+    readable = 0
+    for f in glob.glob("/sys/class/kfd/kfd/topology/nodes/*/properties"):
         try:
             props = dict(l.split()[:2] for l in open(f).read().splitlines() if len(l.split()) >= 2)
         except OSError:
-            return None
+            continue
+        readable += 1
         if int(props.get("simd_count", "0")) > 0:
             n += 1
+    if not readable:
+        return None
     for var in ("HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
         v = os.environ.get(var)
         if v is not None:

@@ -11,6 +11,7 @@ Fixtures:
   g3_block           one WanAttentionBlock, dim 256, L 256, per-token e (two distinct rows)    FX.py:422-472
   g4_dit_tokent      tiny Wan2_2Transformer3DModel_FlexAM, per-token t, all FlexAM inputs      FX.py:817-1123
   g4b_dit_nonsquare  same as g4 on a non-square latent [2,48,3,8,24] (catches h/w swaps)
+  g4c_dit_other_shape  one-layer model, other weights, latent [1,48,2,12,20], t = 133
   g5_dit_scalart     same, 1-D t branch                                                         FX.py:941-944
   g6_teacache        6 forwards with TeaCache on (identity rescale, threshold 2.0): computed and skipped steps  FX.py:977-1051
   g8_vae_encode      small AutoencoderKLWan2_2_ encode [1,3,9,32,64] / [1,3,1,32,32] -> normalised mu          VAE.py:788-818
@@ -18,6 +19,7 @@ Fixtures:
   g11_riflex         WanTransformer3DModel_FlexAM.enable_riflex() rope table (cos / sin of the complex freqs)              FX.py:57-113,774-788
   g12_t5             WanT5EncoderModel.forward (tiny umT5 config, per-layer relative position bias, key mask)            wan_text_encoder.py:256-305
   g7_vae_decode      small AutoencoderKLWan2_2_ decode [1,48,3,4,6] -> [1,3,9,64,96] + taps    VAE.py:820-849
+  g7b_vae_decode_four_chunks  same decoder, other weights, [1,48,4,2,4] -> [1,3,13,32,64]
   g9_sampler         4-step CFG/Euler/blend trace at latent [1,48,3,16,16] driving the
                      reference DiT module through oracle.sampler.denoise_loop                  PIPE.py:840-949
 """
@@ -112,6 +114,13 @@ def main():
         flat = {k: v for k, v in case.items() if torch.is_tensor(v)}
         flat.update({f"ctx{i}": u for i, u in enumerate(case["context"])})
         _save(name, dict(out=out, in_sum=C.checksum(flat), w_sum=C.checksum(sd)))
+    # G4c: a one-layer model with other weights on another shape: batch 1, 2 frames, a 12 x 20 latent, t = 133
+    cfg1 = dict(O.DIT_TINY, num_layers=1)
+    sd1 = C.dit_weights(cfg1, 99)
+    case = C.dit_case(cfg1, 5, frames=2, h=12, w=20, batch=1, t_value=133.0)
+    flat = {k: v for k, v in case.items() if torch.is_tensor(v)}
+    flat.update({f"ctx{i}": u for i, u in enumerate(case["context"])})
+    _save("g4c_dit_other_shape", dict(out=_ref_dit(ref, cfg1, sd1)(**case), in_sum=C.checksum(flat), w_sum=C.checksum(sd1)))
 
     # ---- G6 TeaCache: 6 calls, identity rescale, threshold 2.0 -> calc / skip / skip / calc / skip / calc
     m.enable_teacache(C.TEACACHE_CASE["coefficients"], C.TEACACHE_CASE["num_steps"], rel_l1_thresh=C.TEACACHE_CASE["thresh"],
@@ -154,6 +163,12 @@ def main():
     for h in hooks:
         h.remove()
     _save("g7_vae_decode", dict(out=out, middle=torch.cat(taps["middle"], dim=2), up1_last=taps["up1"][-1], in_sum=C.checksum(dict(z=z)), w_sum=C.checksum(vsd)))
+    # G7b: other weights, four latent frames (four chunks of the causal decode), a 2 x 4 latent
+    vsd = C.vae_weights(C.VAE_SMALL, seed=77, prefix="")
+    V.load_state_dict(vsd, strict=False)
+    z = C.vae_case(seed=78, frames=4, h=2, w=4)
+    out = V.decode(z, [mean, 1.0 / std]).clamp(-1, 1)
+    _save("g7b_vae_decode_four_chunks", dict(out=out, in_sum=C.checksum(dict(z=z)), w_sum=C.checksum(vsd)))
 
     # ---- G8: VAE encode (posterior mode, normalised) on a 9-frame clip (chunks 1+4+4) and a single image
     VE = ref.vae.AutoencoderKLWan2_2_(dim=C.VAE_ENC_SMALL["dim"], dec_dim=16, z_dim=48,

@@ -9,6 +9,8 @@ encodings and their frames, depth frames, all uint8 [T, H, W, 3].  Only data is 
   g13_raster_edges       + NaN / inf coordinates, points on the frame's edges and in row 0, negative fractions (truncation towards zero)
   g13_raster_foreground  + a random mask video, generate_type = foreground_edit                     (pipelines.py:1842-1850)
   g13_raster_wide        point_wise = 6 (7 x 7 squares in the tracking and depth videos, 5 x 5 in the cosine ones), all points visible
+  g13_raster_other_seed  another clip size (4 frames of 40 x 72, 900 points), drawn as full_edit and as background_edit with a random
+                         mask video; keys prefixed by the generate_type, no encodings
 """
 import os
 
@@ -45,16 +47,26 @@ def case(name):
     return pts, vis, mask, gen, point_wise
 
 
-def reference_outputs(ref, pts, vis, mask, gen, point_wise):
+def other_seed_case():
+    """Seeded inputs of g13_raster_other_seed: points, visibility, the background_edit mask video, height, width."""
+    rng = np.random.default_rng(77)
+    t_n, n, h, w = 4, 900, 40, 72
+    pts = np.stack([rng.uniform(-8, w + 8, (t_n, n)), rng.uniform(-8, h + 8, (t_n, n)), rng.uniform(0.2, 9, (t_n, n))], -1).astype(np.float32)
+    vis = rng.random((t_n, n)) > 0.2
+    mask = (rng.random((t_n, h, w)) > 0.4).astype(np.float32)
+    return pts, vis, mask, h, w
+
+
+def reference_outputs(ref, pts, vis, mask, gen, point_wise, h=H, w=W):
     u8 = lambda v: (v[0].permute(1, 2, 3, 0).numpy() * 255).round().astype(np.uint8)          # [1, 3, T, H, W] float -> [T, H, W, 3] bytes
-    out = {"tracking": np.stack(ref.fun_visualize_tracking_with_depth(torch.from_numpy(pts), torch.from_numpy(vis), H, W, point_wise=point_wise,
+    out = {"tracking": np.stack(ref.fun_visualize_tracking_with_depth(torch.from_numpy(pts), torch.from_numpy(vis), h, w, point_wise=point_wise,
                                                                         mask_video=mask, generate_type=gen))}
-    enc = ref.apply_cosine_positional_encoding(torch.from_numpy(pts), H, W, 4)
-    cos = ref._visualize_cosine_encoded_tracking(enc, pts, vis, H, W, False, mask_video=mask, generate_type=gen)
+    enc = ref.apply_cosine_positional_encoding(torch.from_numpy(pts), h, w, 4)
+    cos = ref._visualize_cosine_encoded_tracking(enc, pts, vis, h, w, False, mask_video=mask, generate_type=gen)
     for i in range(4):
         out[f"encoding{i}"] = enc[i].numpy()
         out[f"cos{i}"] = u8(cos[i])
-    out["depth"] = u8(ref._visualize_depth_tracking(torch.from_numpy(pts), vis, H, W, point_wise, False, mask_video=mask, generate_type=gen))
+    out["depth"] = u8(ref._visualize_depth_tracking(torch.from_numpy(pts), vis, h, w, point_wise, False, mask_video=mask, generate_type=gen))
     return out
 
 
@@ -72,6 +84,14 @@ def main():
             tensors["mask"] = torch.from_numpy(mask)
         save_file(tensors, os.path.join(OUT, f"g13_raster_{name}.safetensors"))
         print(f"g13_raster_{name}: painted pixels tracking {int((out['tracking'] > 0).any(-1).sum())}, depth {int((out['depth'] > 0).any(-1).sum())}")
+    pts, vis, mask, h, w = other_seed_case()
+    tensors = {"points": torch.from_numpy(pts), "visible": torch.from_numpy(vis.astype(np.uint8)), "mask": torch.from_numpy(mask)}
+    for gen, m in (("full_edit", None), ("background_edit", mask)):
+        with contextlib.redirect_stdout(io.StringIO()):
+            out = reference_outputs(ref, pts, vis, m, gen, 4, h, w)
+        tensors.update({f"{gen}_{k}": torch.from_numpy(np.ascontiguousarray(v)) for k, v in out.items() if not k.startswith("encoding")})
+    save_file(tensors, os.path.join(OUT, "g13_raster_other_seed.safetensors"))
+    print("g13_raster_other_seed written")
 
 
 if __name__ == "__main__":

@@ -8,8 +8,8 @@ Follows /root/reference/pipelines.py:
   depth_frames         _visualize_depth_tracking           pipelines.py:1763-1820
   should_draw          _should_draw_point                  pipelines.py:1842-1850
   frames_to_tensor     _convert_frames_to_tensor           pipelines.py:1658-1660
-Pinned by tests/golden/g13_raster*.safetensors (outputs of the reference's own methods, oracle/make_golden_raster.py) and, where
-/root/reference is mounted, by a live comparison (tests/test_raster_cpu.py).  Only tests/, __graft_entry__.smoke() and bench.py's
+Pinned by tests/golden/g13_raster*.safetensors (outputs of the reference's own methods, oracle/make_golden_raster.py;
+tests/test_raster_cpu.py).  Only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg may import this module.
 
 What the reference draws: per frame, the visible points with finite pixel coordinates, truncated to integers, inside the frame, in

@@ -2,9 +2,8 @@
 
 Runs only in the build container, where ``/root/reference`` is mounted.  Nothing
 from the reference travels to the GPU box: this module is used by
-``oracle/make_golden.py`` (to write ``tests/golden/*.safetensors``) and by the
-``needs_reference`` CPU tests (live oracle-vs-reference comparison).  It is never
-imported by ``flexam_amd`` (the product), ``bench.py`` or ``-m gpu`` tests.
+``oracle/make_golden.py`` (to write ``tests/golden/*.safetensors``).  It is never
+imported by ``flexam_amd`` (the product), ``bench.py`` or the tests.
 
 Why stubs are needed:
   * ``diffusers`` is not installed and there is no network; the DiT / VAE classes

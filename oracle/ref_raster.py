@@ -1,11 +1,11 @@
 """TEST INFRASTRUCTURE ONLY -- runs the REFERENCE's conditioning rasteriser (pipelines.py:1200-1253, 1501-1641, 1658-1850,
-1852-1902) for fixture generation and the live oracle-vs-reference CPU tests.
+1852-1902) for fixture generation (oracle/make_golden_raster.py).
 
 `/root/reference/pipelines.py` cannot be imported: its module level imports diffusers, torchvision, moviepy and three
 un-vendored submodules (pipelines.py:14-27).  The rasteriser methods themselves need numpy, torch, PIL, tqdm and matplotlib
 only, all of which this image has.  So the method definitions are cut out of the reference file BY NAME with `ast` at run time
 and executed as methods of an empty class -- the reference's own code runs, nothing of it is stored in this repository.  Never
-imported by flexam_amd, bench.py or `-m gpu` tests; only where /root/reference is mounted."""
+imported by flexam_amd, bench.py or the tests; only where the reference checkout is mounted."""
 import ast
 import os
 

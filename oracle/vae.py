@@ -15,8 +15,8 @@ marker of upsample3d (VAE.py:120-152) means: chunk 0 skips the time conv and
 leaves its history at zero.
 
 Works on a state dict with the reference's key names (prefix "model." as loaded by
-VAE.py:1073-1077).  Pinned against the reference module by golden G7/G10 and by
-the live comparison test (tests/test_oracle_vs_reference.py).
+VAE.py:1073-1077).  Pinned against the reference module by golden G7/G7b/G10
+(tests/test_oracle_golden.py, tests/test_oracle_vs_reference.py).
 """
 from typing import Dict, Optional
 

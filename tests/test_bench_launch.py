@@ -196,6 +196,27 @@ def test_one_gpu_line_carries_an_emulated_rank_of_four():
 
 
 @pytest.mark.gpu
+def test_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR`: the latents the last TIMED step returned, float32, as DIR/latents.npy.  One warm-up step + three timed
+    steps and three warm-up steps + one timed step run the same step indices on the same seeded inputs, so they dump the same latents;
+    the line counts exactly the timed steps and carries ms_per_step."""
+    import numpy as np
+    got = {}
+    for warmup, steps in ((1, 3), (3, 1)):
+        d = tmp_path / f"w{warmup}s{steps}"
+        r = _run(["--gpus", "1", *SMALL, "--warmup", str(warmup), "--steps", str(steps), "--dump-outputs", str(d)], {})
+        assert r.returncode == 0, r.stderr[-3000:]
+        res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+        assert res["steps"] == steps and res["warmup"] == warmup and res["finite"]
+        assert res["ms_per_step"] > 0 and res["ms_per_step"] * res["value"] == pytest.approx(1e3)
+        assert res["dump_outputs"]["arrays"] == {"latents.npy": [48, 3, 16, 16]} and os.listdir(d) == ["latents.npy"]
+        a = np.load(d / "latents.npy")
+        assert a.dtype == np.float32 and np.isfinite(a).all() and a.nbytes <= 64 << 20
+        got[(warmup, steps)] = a
+    assert np.array_equal(got[(1, 3)], got[(3, 1)])
+
+
+@pytest.mark.gpu
 def test_logit_scale_line_says_what_it_measured():
     """`bench.py --logit-scale S`: norm_q / norm_k x sqrt(S) on the random-init model (peaked softmax rows); a variant line, never the headline."""
     r = _run(["--gpus", "1", *SMALL, "--logit-scale", "6"], {})

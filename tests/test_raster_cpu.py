@@ -1,7 +1,7 @@
 """CPU: the conditioning rasteriser's oracle (oracle/raster.py) against the fixtures the reference's own methods produced
 (tests/golden/g13_raster_*: pipelines.py:1501-1641, 1658-1850 run through PIL, oracle/make_golden_raster.py), the product's host-side
 colour tables (flexam_amd/conditioning_raster.py: numpy, no GPU needed) against the oracle, the restated Spectral table against
-matplotlib where it is installed, and -- where /root/reference is mounted -- the oracle against the live reference on another seed."""
+matplotlib where it is installed, and the oracle against the reference's output on another seed and clip size (g13_raster_other_seed)."""
 import numpy as np
 import pytest
 import torch
@@ -125,25 +125,15 @@ def test_equal_depths_lower_index_on_top():
     assert fr[10, 12, 0] == 0
 
 
-@pytest.mark.needs_reference
-def test_oracle_matches_live_reference_other_seed():
-    import contextlib
-    import io
-    from oracle import ref_raster
-    ref = ref_raster.load()
-    rng = np.random.default_rng(77)
-    t_n, n, h, w = 4, 900, 40, 72
-    pts = np.stack([rng.uniform(-8, w + 8, (t_n, n)), rng.uniform(-8, h + 8, (t_n, n)), rng.uniform(0.2, 9, (t_n, n))], -1).astype(np.float32)
-    vis = rng.random((t_n, n)) > 0.2
-    mask = (rng.random((t_n, h, w)) > 0.4).astype(np.float32)
+def test_oracle_matches_reference_fixture_other_seed(golden):
+    """Another clip size and seed, drawn as full_edit and as background_edit (tests/golden/g13_raster_other_seed)."""
+    g = golden("g13_raster_other_seed")
+    pts, vis, mask, h, w = G.other_seed_case()
+    assert np.array_equal(g["points"].numpy(), pts) and np.array_equal(g["visible"].numpy().astype(bool), vis)      # the seeded inputs regenerate
+    assert np.array_equal(g["mask"].numpy(), mask)
     u8 = lambda v: (v[0].permute(1, 2, 3, 0).numpy() * 255).round().astype(np.uint8)
     for gen, m in (("full_edit", None), ("background_edit", mask)):
-        with contextlib.redirect_stdout(io.StringIO()):
-            tr = np.stack(ref.fun_visualize_tracking_with_depth(torch.from_numpy(pts), torch.from_numpy(vis), h, w, point_wise=4, mask_video=m, generate_type=gen))
-            enc = ref.apply_cosine_positional_encoding(torch.from_numpy(pts), h, w, 4)
-            cos = ref._visualize_cosine_encoded_tracking(enc, pts, vis, h, w, False, mask_video=m, generate_type=gen)
-            dep = u8(ref._visualize_depth_tracking(torch.from_numpy(pts), vis, h, w, 4, False, mask_video=m, generate_type=gen))
         got_t, got_c, got_d = O.visualize_tracking(pts, vis, 4, h, w, 4, gen, m)
-        assert np.array_equal(u8(got_t), tr) and np.array_equal(u8(got_d), dep)
+        assert np.array_equal(u8(got_t), g[f"{gen}_tracking"].numpy()) and np.array_equal(u8(got_d), g[f"{gen}_depth"].numpy())
         for i in range(4):
-            assert np.array_equal(u8(got_c[i]), u8(cos[i]))
+            assert np.array_equal(u8(got_c[i]), g[f"{gen}_cos{i}"].numpy())
