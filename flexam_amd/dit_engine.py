@@ -20,6 +20,7 @@ All arithmetic runs in libflexam_hip.so (flexam_amd/hip.py); torch only allocate
 """
 import math
 import os
+from collections import namedtuple
 from contextlib import nullcontext
 from typing import List, Optional
 
@@ -71,6 +72,13 @@ class _Image:
         self.buf = torch.zeros((self.rows + 2 * guard) * cp, device=device, dtype=BF16)
         self.img = self.buf[guard * cp:(guard + self.rows) * cp].view(f, h + 2, w + 2, cp)
         self.mat = self.img.view(self.rows, cp)
+
+
+# What the block and head launches of one forward depend on apart from buffer contents and addresses, resolved once at the start of
+# DiTEngine.run (DiTEngine._mode): the stages read it, and a recorded launch plan is keyed on it
+_Mode = namedtuple("_Mode", "B Lp lc tok0 R rows_per_batch only_row "                                 # sizes (Lp: padded sequence)
+                   "per_layer share0 sage sage_gather sage_fused fp8 fp8_oproj ffn_apriori "        # switches
+                   "sp rank sp_mode sp_pieces sp_overlap_level sp_fused_qkv use_plan")              # layout
 
 
 class DiTEngine:
@@ -393,6 +401,50 @@ class DiTEngine:
             hip.small_linear(e[sl], *self.time[2], silu_in=True, out=e0[sl])
         return e, e0.view(R, 6, d)
 
+    def _mode(self, bx, R, rows_per_batch, only_row, rows_shared, teacache):
+        """The mode of one forward (see _Mode).  Every environment switch a forward reads is read here, once per forward: tests and
+        benchlib flip them between forwards."""
+        env, cd, sp, L = os.environ, self.cond, self.sp_size, self.cond["L"]
+        B = cd["B"] if only_row is None else 1
+        sp_mode, pieces, overlap = getattr(self, "sp_mode", None), getattr(self, "sp_pieces", 1), getattr(self, "sp_overlap_level", 0)
+        # A sequence that does not divide over the ranks is padded to the next multiple with zero tokens at its end, as the reference
+        # does (FX.py:919-925); they are rows like any other in every token-local op, never keys of self-attention (the key ranges
+        # end at L), and the head gather drops them
+        # VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION under the K|V gather (one gather, waited for): the ranks exchange their MXFP8 key / value
+        # RECORDS (one per 64 keys) instead of bf16 rows, so every chunk is a whole number of 64-key tiles: the padding unit is 64 x ranks
+        sage_asked = env.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION"
+        sage_gather = sage_asked and self.fused and sp > 1 and sp_mode == "allgather" and overlap == 0 and pieces == 1
+        unit = sp * 64 if sage_gather else sp
+        Lp = -(-L // unit) * unit
+        # the reference reads the switch at every attention call (attention_utils.py:195); quantised self-attention on one rank: MXFP8
+        # operands of the rank's tokens.  Sequence parallel with the all-to-all over heads: every rank ends up with ALL tokens of its
+        # heads in bf16, packs them and runs the MXFP8 kernel on them.  K|V all-gather in its default form (one gather, waited for):
+        # each rank quantises ITS keys / values and the MXFP8 records are what is gathered (sage_gather, above).  The overlapped gather
+        # forms (head-group pieces, partial softmaxes) keep the bf16 kernel -- said once per process
+        sage = sage_asked and self.fused and (sp == 1 or (sp_mode == "ulysses" and Lp == L) or sage_gather)
+        if sage_asked and not sage and not DiTEngine._sage_warned:
+            DiTEngine._sage_warned = True
+            import warnings
+            warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored " +
+                          "under sequence parallelism with the OVERLAPPED K|V all-gather (FLEXAM_SP_OVERLAP=1 / head-group pieces) or an all-to-all "
+                          "over a padded sequence: self-attention runs the bf16 kernel", RuntimeWarning, stacklevel=3)
+        # CFG pair on one latent (PIPE.py:846-848 feeds `torch.cat([latents] * 2)`): until the first cross-attention the two samples
+        # are the same tensor -- same tokens, same timestep rows, same density -- so block 0 runs LayerNorm, q|k|v, RoPE, self-
+        # attention and the output projection ONCE and the second sample's residual stream is a copy (half of 1/30 of the
+        # attention and projection work of a step; every later operation sees the text and runs per sample)
+        share0 = (self.fused and B == 2 and bx == 1 and sp == 1 and rows_shared and cd.get("dens_same", False) and teacache is None
+                  and env.get("FLEXAM_SHARE_BLOCK0", "1") != "0")
+        per_layer = (not self.fused) or self.nl * R * 6 * self.dim * 4 > self.table_limit
+        lc = Lp // sp
+        return _Mode(B=B, Lp=Lp, lc=lc, tok0=self.sp_rank * lc, R=R, rows_per_batch=rows_per_batch, only_row=only_row,
+                     per_layer=per_layer, share0=bool(share0), sage=bool(sage), sage_gather=bool(sage_gather),
+                     sage_fused=bool(sage) and self.nh == 24 and self.hd == 128,
+                     fp8=self.fp8, fp8_oproj=self.fp8 and env.get("FLEXAM_FP8_OPROJ", "0") == "1",
+                     ffn_apriori=env.get("FLEXAM_FP8_FFN_APRIORI", "1") != "0",
+                     sp=sp, rank=self.sp_rank, sp_mode=sp_mode, sp_pieces=pieces, sp_overlap_level=overlap,
+                     sp_fused_qkv=getattr(self, "sp_fused_qkv", True),
+                     use_plan=self.fused and teacache is None and not per_layer and env.get("FLEXAM_REPLAY", "1") != "0")
+
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
             only_row: Optional[int] = None, teacache=None, cond_flag: bool = True, rows_shared: bool = False) -> torch.Tensor:
         """x [Bx, 48, F, H, W] (Bx = B, or 1 when all rows share the latent); t_rows [R] distinct
@@ -400,123 +452,74 @@ class DiTEngine:
         row_index int32 [B * L] global table row per token, or None (then token (b, l) uses row b).
         Returns the head output tokens fp32 [B, Lc, 4*out_dim] of this rank's token chunk."""
         cd, dev, d = self.cond, self.device, self.dim
-        B, L, lvid, ref_len = cd["B"], cd["L"], cd["lvid"], cd["ref_len"]
+        m = self._mode(x.shape[0], t_rows.numel(), rows_per_batch, only_row, rows_shared, teacache)
+        B, L, ref_len, lc, R = m.B, cd["L"], cd["ref_len"], m.lc, m.R
         # only_row: run a single conditioning row (cfg_skip: the unconditional row is dropped, cfg_optimization.py:5-37);
         # t_rows / row_index then describe that one row
         rsel = slice(None) if only_row is None else slice(only_row, only_row + 1)
-        if only_row is not None:
-            B = 1
         dens0 = cd["dens0"][rsel] if cd["dens0"] is not None else None
         dens_emb = cd["dens_emb"][rsel] if cd["dens_emb"] is not None else None
-        cx, f, h, w = cd["latent_shape"]
-        sp, rank = self.sp_size, self.sp_rank
-        # A sequence that does not divide over the ranks is padded to the next multiple with zero tokens at its end, as the reference
-        # does (FX.py:919-925); they are rows like any other in every token-local op, never keys of self-attention (the key ranges
-        # below end at L), and the head gather drops them
-        # VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION under the K|V gather (one gather, waited for): the ranks exchange their MXFP8 key / value
-        # RECORDS (one per 64 keys) instead of bf16 rows, so every chunk is a whole number of 64-key tiles: the padding unit is 64 x ranks
-        sage_asked = os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION"
-        sage_gather = (sage_asked and self.fused and sp > 1 and getattr(self, "sp_mode", None) == "allgather" and not self.sp_overlap
-                       and self.sp_pieces == 1)
-        unit = sp * 64 if sage_gather else sp
-        Lp = -(-L // unit) * unit
-        lc = Lp // sp
-        tok0 = rank * lc
-        if Lp > L and cd["cos"].shape[0] < Lp:             # RoPE rows of the pad tokens: the identity, like every token beyond the grid
-            extra = Lp - cd["cos"].shape[0]
+        if m.Lp > L and cd["cos"].shape[0] < m.Lp:         # RoPE rows of the pad tokens: the identity, like every token beyond the grid
+            extra = m.Lp - cd["cos"].shape[0]
             cd["cos"] = torch.cat([cd["cos"], torch.ones(extra, cd["cos"].shape[1], device=dev)])
             cd["sin"] = torch.cat([cd["sin"], torch.zeros(extra, cd["sin"].shape[1], device=dev)])
         ws = self._workspace(B, lc)
-        xres, hbuf, qkv, ao, ffn, head = ws["x"], ws["h"], ws["qkv"], ws["ao"], ws["ffn"], ws["head"]
+        xres = ws["x"]
         xr = xres.view(B, lc, d)
 
         # ---- stem: patch embedding of the noisy latent (+ cached static channels), ref tokens
         bx = x.shape[0]
-        full = torch.empty(Lp, d, device=dev, dtype=F32) if sp > 1 else None
-        if Lp > L:
+        full = torch.empty(m.Lp, d, device=dev, dtype=F32) if m.sp > 1 else None
+        if m.Lp > L:
             full[L:].zero_()
         for b in range(bx):
             pa = cd["patch_a"][b if cd["nb"] > 1 else 0]
             hip.patchify(x[b].to(dev).contiguous(), pa, col0=0)
-            dst = full if sp > 1 else xr[b]
+            dst = full if m.sp > 1 else xr[b]
             hip.gemm(pa, self.pe_w, self.pe_b, out=dst[ref_len:L], out_dtype=F32)
             if ref_len:
                 dst[:ref_len].copy_(cd["ref_tok"][b if cd["nb"] > 1 else 0])
-            if sp > 1:
-                xr[b].copy_(full[tok0:tok0 + lc])
-        # CFG pair on one latent (PIPE.py:846-848 feeds `torch.cat([latents] * 2)`): until the first cross-attention the two samples
-        # are the same tensor -- same tokens, same timestep rows, same density -- so block 0 runs LayerNorm, q|k|v, RoPE, self-
-        # attention and the output projection ONCE and the second sample's residual stream is a copy (half of 1/30 of the
-        # attention and projection work of a step; every later operation sees the text and runs per sample)
-        share0 = (self.fused and B == 2 and bx == 1 and sp == 1 and rows_shared and cd.get("dens_same", False) and teacache is None
-                  and os.environ.get("FLEXAM_SHARE_BLOCK0", "1") != "0")
-        self.share0_taken = bool(share0)
-        if not share0:
+            if m.sp > 1:
+                xr[b].copy_(full[m.tok0:m.tok0 + lc])
+        self.share0_taken, self.sage_taken = m.share0, m.sage          # what this forward DID (bench.py labels its line from them)
+        if not m.share0:
             for b in range(bx, B):
                 xr[b].copy_(xr[0])
 
         # ---- timestep embedding on the distinct rows + AdaLN tables of all blocks and the head
-        R = t_rows.numel()
         if rows_shared and R > rows_per_batch:     # every sample carries the same timestep rows (the sampler's CFG pair): embed once
             e1, e01 = self.embed_time(t_rows[:rows_per_batch])
             reps = R // rows_per_batch
             e, e0 = e1.repeat(reps, 1), e01.repeat(reps, 1, 1)
         else:
             e, e0 = self.embed_time(t_rows)
-        per_layer = (not self.fused) or self.nl * R * 6 * d * 4 > self.table_limit
         dens0c = dens0.contiguous() if dens0 is not None else None
         # the tables live in the workspace (one set per row count): the blocks' launches name their addresses, and a recorded launch plan
         # (below) is only valid while they stay put
-        tabs = ws.setdefault(("tabs", R, per_layer), {})
+        tabs = ws.setdefault(("tabs", R, m.per_layer), {})
         if not tabs:
-            tabs["blk"] = torch.empty(1 if per_layer else self.nl, R, 6, d, device=dev, dtype=F32)
+            tabs["blk"] = torch.empty(1 if m.per_layer else self.nl, R, 6, d, device=dev, dtype=F32)
             tabs["head"] = torch.empty(1, R, 2, d, device=dev, dtype=F32)
-        if per_layer:
-            tab, tab1 = None, tabs["blk"]
-        else:
-            tab = tabs["blk"]
-            hip.mod_table(self.mod, e0, tab, rows_per_batch, 0b010010, self.mdens, dens0c, 0xFF1FF0 if dens0 is not None else -1)
-        htab = tabs["head"]
+        if not m.per_layer:
+            hip.mod_table(self.mod, e0, tabs["blk"], rows_per_batch, 0b010010, self.mdens, dens0c, 0xFF1FF0 if dens0 is not None else -1)
         e2 = e.unsqueeze(1).expand(R, 2, d).contiguous()
         hd_dens = dens_emb.reshape(B, 1, d).contiguous() if dens_emb is not None else None
-        hip.mod_table(self.hmod, e2, htab, rows_per_batch, 0b10, self.hmdens if hd_dens is not None else None, hd_dens,
+        hip.mod_table(self.hmod, e2, tabs["head"], rows_per_batch, 0b10, self.hmdens if hd_dens is not None else None, hd_dens,
                       0xF0 if hd_dens is not None else -1)
-        calc = True
-        if teacache is not None:
-            calc = self._teacache_decide(teacache, e0, row_index, B, L, cond_flag)
+        calc = self._teacache_decide(teacache, e0, row_index, B, L, cond_flag) if teacache is not None else True
         if row_index is not None:
             # the per-token row index of THIS rank's rows, copied (47 KB) into a buffer of the workspace: the blocks' launches then see ONE
             # address from step to step whoever built the index (the sampler keeps one tensor per clip, the reference-style forward()
             # builds a new one per call) -- what a recorded launch plan (below) needs
-            if sp > 1:
+            if m.sp > 1:
                 from .dist import shard_rows
-                row_index = shard_rows(row_index, B, L, rank, sp, chunk=lc)
+                row_index = shard_rows(row_index, B, L, m.rank, m.sp, chunk=lc)
             buf = ws.get("row_index_buf")
             if buf is None or buf.numel() != row_index.numel():
                 buf = ws["row_index_buf"] = torch.empty(row_index.numel(), device=dev, dtype=I32)
             buf.copy_(row_index.reshape(-1))
             row_index = buf
-        rpb = lc                                   # used only when row_index is None: row = m // lc = b
-
-        nh, hdim = self.nh, self.hd
-        # the reference reads the switch at every attention call (attention_utils.py:195); quantised self-attention on one rank only
-        # one rank: the fused producer (RMSNorm + RoPE write the MXFP8 operands).  Sequence parallel with the all-to-all over heads: every
-        # rank ends up with ALL tokens of its heads in bf16, packs them and runs the MXFP8 kernel on them.  K|V all-gather in its default
-        # form (one gather, waited for): each rank quantises ITS keys / values and the MXFP8 records are what is gathered (sage_gather,
-        # above).  The overlapped gather forms (head-group pieces, partial softmaxes) keep the bf16 kernel -- said once per process
-        sage = sage_asked and self.fused and (sp == 1 or (self.sp_mode == "ulysses" and Lp == L) or sage_gather)
-        self.sage_taken = bool(sage)                       # what this forward DID (bench.py labels its line from it, like share0_taken)
-        if sage_asked and not sage and not DiTEngine._sage_warned:
-            DiTEngine._sage_warned = True
-            import warnings
-            warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored " +
-                          "under sequence parallelism with the OVERLAPPED K|V all-gather (FLEXAM_SP_OVERLAP=1 / head-group pieces) or an all-to-all "
-                          "over a padded sequence: self-attention runs the bf16 kernel", RuntimeWarning, stacklevel=2)
-        fp8_oproj = self.fp8 and os.environ.get("FLEXAM_FP8_OPROJ", "0") == "1"
-        q4 = qkv.view(B, lc, 3 * d)[:, :, 0:d].unflatten(2, (nh, hdim))
-        k4 = qkv.view(B, lc, 3 * d)[:, :, d:2 * d].unflatten(2, (nh, hdim))
-        v4 = qkv.view(B, lc, 3 * d)[:, :, 2 * d:].unflatten(2, (nh, hdim))
-        ao4 = ao.view(B, lc, nh, hdim)
+        ws["row_index"] = row_index                        # this forward's (the stages read it here), or None
         if teacache is not None:
             key = "previous_residual_cond" if cond_flag else "previous_residual_uncond"
             if not calc:                                   # skipped step: x += residual of the last computed step (FX.py:1003-1006)
@@ -526,157 +529,194 @@ class DiTEngine:
                 hip.axpby(xres, 1.0, res.contiguous(), 1.0)
             else:
                 ori = xres.clone()
-        if calc and not self.fused:
-            self._run_block_modules(xres, B, lc, e0, row_index, rows_per_batch, dens0, t_rows, rsel)
 
-        def run_blocks():
-            for i, p in enumerate(self.blocks if (calc and self.fused) else ()):
-                if per_layer:                                  # one table, rebuilt per layer (bounded memory, see table_limit)
-                    hip.mod_table(self.mod[i:i + 1], e0, tab1, rows_per_batch, 0b010010, self.mdens[i:i + 1], dens0c,
-                                  0xFF1FF0 if dens0 is not None else -1)
-                    T = tab1[0]
-                else:
-                    T = tab[i]
-                fp8_here = self.fp8
-                nb = 1 if (share0 and i == 0) else B               # samples that run the self-attention half of this block (share0: above)
-                mb = nb * lc
-                ri = row_index[:mb] if row_index is not None else None
-                if fp8_here:                                   # LN + modulate written as e4m3 + row scales: the fp8 QKV GEMM's A operand
-                    a8, sa, _ = self._ln_fp8(xres[:mb], ws, hbuf[:mb], shift=T[:, 0], scale=T[:, 1], row_index=ri, rows_per_batch=rpb)
-                else:
-                    hip.ln_modulate(xres[:mb], out=hbuf[:mb], eps=self.eps, shift=T[:, 0], scale=T[:, 1], row_index=ri, rows_per_batch=rpb)
-                if sp > 1 and self.sp_mode == "ulysses":
-                    # all tokens of H/sp heads per rank: q|k|v all-to-all -> attention -> all-to-all back; the o-projection reads the
-                    # returned blocks in place (flexam_amd/dist.py)
-                    a_o, koff_o = self._ulysses_attention(qkv, hbuf, fp8_here and (a8, sa), i, p, B, lc, tok0, sage=sage)
-                    hip.gemm_gate_residual(a_o, p["wo"], p["bo"], xres, gate=T[:, 2], gate_row=row_index, rows_per_batch=rpb, a_koff=koff_o)
-                elif sp > 1:
-                    # K|V projection + K norm/RoPE first, written straight into the send buffer; their all-gather (RCCL over xGMI)
-                    # runs under the Q projection, the Q norm/RoPE and the attention to the LOCAL chunk
-                    # (FLEXAM_SP_FUSED_QKV=1, default: ONE q|k|v launch instead -- at a rank's few thousand rows two launches of 24 and 12 tile
-                    #  columns quantise worse on 256 CUs than one of 36 (emulated rank of 8, profiles/r5*: 119 + 80 us against ~135), and the
-                    #  gather starts ~15 us later, not ~80)
-                    fused_qkv = self.sp_fused_qkv
-                    if sage:                               # (sage_gather: the MXFP8 records travel; always one q|k|v launch)
-                        self._proj(hbuf, fp8_here and (a8, sa), i, p, "wqkv", "bqkv", slice(None), qkv)
-                        self._allgather_attention_mx(qkv, p, ao4, q4, k4, v4, B, lc, tok0)
-                    else:
-                        self._proj(hbuf, fp8_here and (a8, sa), i, p, "wqkv", "bqkv", slice(None) if fused_qkv else slice(d, None), qkv if fused_qkv else qkv[:, d:])
-                        self._allgather_attention(qkv, hbuf, fp8_here and (a8, sa), i, p, ao4, q4, B, lc, tok0, q_done=fused_qkv)
-                    hip.gemm_gate_residual(ao, p["wo"], p["bo"], xres, gate=T[:, 2], gate_row=row_index, rows_per_batch=rpb)
-                else:
-                    a8sa = fp8_here and (a8[:mb], sa[:mb])
-                    self._proj(hbuf[:mb], a8sa, i, p, "wqkv", "bqkv", slice(None), qkv[:mb])
-                    if sage and nh == 24 and hdim == 128 and os.environ.get("FLEXAM_SAGE_FUSED", "1") != "0":   # SAGE_ATTENTION: MXFP8 operands (csrc/attn_fp8.inc);
-                        bufs = self._attn8_buffers(nb, lc)     # RMSNorm + RoPE write Q and K as operands directly, V is packed on its own
-                        hip.rmsnorm_rope_mx(qkv[:mb, 0:d], p["nq"], qkv[:mb, d:2 * d], p["nk"], bufs, cd["cos"], cd["sin"], lc, tok0, eps=self.eps)
-                        hip.attn_fp8_pack(None, None, v4[:nb], bufs)
-                        hip.attn_fwd_fp8(bufs, lc, out=ao4[:nb])
-                    else:
-                        hip.rmsnorm_rope(qkv[:mb, 0:d], p["nq"], qkv[:mb, d:2 * d], p["nk"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"],
-                                         tokens_per_batch=lc, token_offset=tok0, head_dim=hdim)
-                        if sage:
-                            bufs = self._attn8_buffers(nb, lc)
-                            hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs)
-                            hip.attn_fwd_fp8(bufs, lc, out=ao4[:nb])
-                        else:
-                            hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)
-                    if fp8_here and fp8_oproj:
-                        a8o, sao = hip.quantize_rows_fp8(ao[:mb], ws["a8d"][:mb], ws["sa"][:mb])
-                        hip.gemm_fp8_gate_residual(a8o, sao, self._fp8_w[i]["wo"], self._fp8_w[i]["s_wo"], p["bo"], xres[:mb], gate=T[:, 2], gate_row=ri,
-                                                   rows_per_batch=rpb)
-                    else:
-                        hip.gemm_gate_residual(ao[:mb], p["wo"], p["bo"], xres[:mb], gate=T[:, 2], gate_row=ri, rows_per_batch=rpb)
-                    if nb < B:
-                        hip.host_op(lambda: xr[1].copy_(xr[0]))         # (a torch copy, not a library call: a host step of a recorded plan)
-                # cross-attention on the text context (K/V precomputed per clip)
-                qc = qkv[:, 0:d]
-                if self.fp8:                                   # the Q projection of cross-attention on the fp8 pipe as well (its K|V are per clip)
-                    a8, sa, _ = self._ln_fp8(xres, ws, hbuf, ln_w=p["n3w"], ln_b=p["n3b"])
-                    hip.gemm_fp8(a8, sa, self._fp8_w[i]["cwq"], self._fp8_w[i]["s_cwq"], p["cbq"], out=qc)
-                else:
-                    hip.ln_modulate(xres, out=hbuf, eps=self.eps, ln_w=p["n3w"], ln_b=p["n3b"])
-                    hip.gemm(hbuf, p["cwq"], p["cbq"], out=qc)
-                hip.rmsnorm_rope(qc, p["cnq"], eps=self.eps)
-                kv = cd["cross_kv"][i][rsel]
-                if cd.get("cross_lk"):                          # the identical padded text rows as ONE weighted key
-                    lk = cd["cross_lk"]
-                    hip.attn_fwd_lastkey(q4, kv[:, :lk, 0:d].unflatten(2, (nh, hdim)), kv[:, :lk, d:].unflatten(2, (nh, hdim)), cd["cross_mult"],
-                                         out=ao4, prescaled=True)
-                else:
-                    hip.attn_fwd(q4, kv[:, :, 0:d].unflatten(2, (nh, hdim)), kv[:, :, d:].unflatten(2, (nh, hdim)), out=ao4, prescaled=True)
-                if self.fp8 and fp8_oproj:
-                    a8o, sao = hip.quantize_rows_fp8(ao, ws["a8d"], ws["sa"])
-                    hip.gemm_fp8_gate_residual(a8o, sao, self._fp8_w[i]["cwo"], self._fp8_w[i]["s_cwo"], p["cbo"], xres)
-                else:
-                    hip.gemm_gate_residual(ao, p["cwo"], p["cbo"], xres)
-                # FFN
-                if self.fp8:
-                    w8 = self._fp8_w[i]
-                    # FFN1 writes FFN2's e4m3 operand itself: its output row scales are known before it runs (a bound from the row's L2
-                    # norm, written by the LN launch), so there is no absmax / quantise pass over the [M, 14336] intermediate
-                    # (FLEXAM_FP8_FFN_APRIORI=0: the earlier form -- bf16 intermediate + an absmax row quantiser pass -- for checkpoints whose w1
-                    #  has a few very large rows: the bound is set by the LARGEST row norm, so every ordinary row's outputs then sit lower in
-                    #  e4m3's range.  One scale per output row has to cover all 14336 columns, so a per-tile bound cannot be used by FFN2.)
-                    apriori = os.environ.get("FLEXAM_FP8_FFN_APRIORI", "1") != "0"
-                    a8, sa, bound = self._ln_fp8(xres, ws, hbuf, nxt=(w8["w1_norm"], w8["b1_max"]) if apriori else None, shift=T[:, 3], scale=T[:, 4],
-                                                 row_index=row_index, rows_per_batch=rpb)
-                    if bound:
-                        hip.gemm_fp8_gelu_q(a8, sa, w8["w1"], w8["s_w1"], p["b1"], ws["so"], ws["a8"])
-                        a8, sa = ws["a8"], ws["so"]
-                    else:                                      # widths the fused LN launch does not cover: bf16 intermediate + row quantiser
-                        hip.gemm_fp8(a8, sa, w8["w1"], w8["s_w1"], p["b1"], out=ffn, epilogue=hip.EPI_GELU_TANH)
-                        a8, sa = hip.quantize_rows_fp8(ffn, ws["a8"], ws["sa"])
-                    hip.gemm_fp8_gate_residual(a8, sa, w8["w2"], w8["s_w2"], p["b2"], xres, gate=T[:, 5], gate_row=row_index, rows_per_batch=rpb)
-                else:
-                    hip.ln_modulate(xres, out=hbuf, eps=self.eps, shift=T[:, 3], scale=T[:, 4], row_index=row_index, rows_per_batch=rpb)
-                    # (FFN1 -> FFN2 per row chunk, so that the [M, 14336] intermediate stays in the Infinity Cache: the clock rises with the
-                    #  saved HBM traffic, but tile quantisation and launch ramps cost more: +0.5 / +1.6 / +7.1 % of a step at 2 / 4 / 7 chunks,
-                    #  profiles/r4p_ffn_row_chunks.txt)
-                    hip.gemm(hbuf, p["w1"], p["b1"], out=ffn, epilogue=hip.EPI_GELU_TANH)
-                    hip.gemm_gate_residual(ffn, p["w2"], p["b2"], xres, gate=T[:, 5], gate_row=row_index, rows_per_batch=rpb)
-        def run_head():
-            H = htab[0]
-            hip.ln_modulate(xres, out=hbuf, eps=self.eps, shift=H[:, 0], scale=H[:, 1], row_index=row_index, rows_per_batch=rpb)
-            hip.gemm(hbuf, self.head_w, self.head_b, out=head)
-
-        # ---- launch plan: the blocks and the head issue the same ~420 launches on the same buffers every step (only buffer CONTENTS
-        # change), so the first step records them (hip.record: executed and appended to command lists) and every later step re-issues
-        # the lists from C (flexam_replay, csrc/replay.hip: ~1 us per launch instead of 20-30 us of Python + ctypes).  Collectives,
-        # waits and torch copies between them are host steps of the plan (hip.host_op).  The key names everything the recorded launches
-        # depend on besides buffer contents; plans live in the per-clip state (new conditioning = new plans) and hold references to every
-        # tensor whose address they carry.  Not with TeaCache (data-dependent skipping), per-layer tables or blocks called as modules.
-        use_plan = (calc and self.fused and teacache is None and not per_layer and os.environ.get("FLEXAM_REPLAY", "1") != "0")
         self.replay_taken = False
-        if use_plan:
-            pkey = (self._ws_gen, B, lc, only_row, bool(share0), bool(sage), self.fp8, fp8_oproj, R, rows_per_batch,
-                    row_index.data_ptr() if row_index is not None else 0, tabs["blk"].data_ptr(), cd["cos"].data_ptr(),
-                    torch.cuda.current_stream().cuda_stream, hip.num_cus(), os.environ.get("FLEXAM_SAGE_FUSED", "1"), os.environ.get("FLEXAM_FP8_FFN_APRIORI", "1"),
-                    sp, rank, getattr(self, "sp_mode", None), getattr(self, "sp_pieces", 1), getattr(self, "sp_overlap_level", 0),
-                    getattr(self, "sp_fused_qkv", True), id(self.sp_group))
-            plans = cd.setdefault("_plans", {})
-            plan = plans.get(pkey)
-            if plan is None:
-                for k in [k for k in plans if k[0] != self._ws_gen]:      # plans of dropped activation buffers would keep those buffers alive
-                    del plans[k]
-                with hip.record() as plan:
-                    run_blocks()
-                    run_head()
-                while len(plans) >= 6:                     # (cond / uncond rows of cfg_skip, the shared-block-0 form, ...: a handful per clip)
-                    plans.pop(next(iter(plans)))
-                plans[pkey] = plan
-            else:
-                plan.run()
-                self.replay_taken = True
-            self.plan_launches = plan.launches
-        else:
-            run_blocks()
+        if m.use_plan:
+            self._record_or_replay(m, ws, e0, dens0c)
+            return ws["head"].view(B, lc, -1)
+        if calc and self.fused:
+            self._blocks(m, ws, e0, dens0c)
+        elif calc:
+            self._run_block_modules(xres, B, lc, e0, row_index, rows_per_batch, dens0, t_rows, rsel)
         if teacache is not None and calc:                  # residual = x_after_blocks - x_before (FX.py:1048-1051), kept on the GPU
             hip.axpby(ori, 1.0, xres, -1.0)
             setattr(teacache, key, ori)
-        if not use_plan:
-            run_head()
-        return head.view(B, lc, -1)
+        self._head(m, ws)
+        return ws["head"].view(B, lc, -1)
+
+    def _record_or_replay(self, m, ws, e0, dens0):
+        """The blocks and the head through a launch plan: they issue the same ~420 launches on the same buffers every step (only buffer
+        CONTENTS change), so the first step records them (hip.record: executed and appended to command lists) and every later step
+        re-issues the lists from C (flexam_replay, csrc/replay.hip: ~1 us per launch instead of 20-30 us of Python + ctypes).  Collectives,
+        waits and torch copies between them are host steps of the plan (hip.host_op).  The key is the mode and the addresses and context
+        the launches name; plans live in the per-clip state (new conditioning = new plans) and hold references to every tensor whose
+        address they carry.  Not with TeaCache (data-dependent skipping), per-layer tables or blocks called as modules (_Mode.use_plan)."""
+        cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
+        key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
+               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group))
+        plans = cd.setdefault("_plans", {})
+        plan = plans.get(key)
+        if plan is None:
+            for k in [k for k in plans if k[1] != self._ws_gen]:      # plans of dropped activation buffers would keep those buffers alive
+                del plans[k]
+            with hip.record() as plan:
+                self._blocks(m, ws, e0, dens0)
+                self._head(m, ws)
+            while len(plans) >= 6:                         # (cond / uncond rows of cfg_skip, the shared-block-0 form, ...: a handful per clip)
+                plans.pop(next(iter(plans)))
+            plans[key] = plan
+        else:
+            plan.run()
+            self.replay_taken = True
+        self.plan_launches = plan.launches
+
+    # ------------------------------------------------------------------ stages of a forward (fused blocks)
+    def _blocks(self, m, ws, e0, dens0):
+        tab = ws["tabs", m.R, m.per_layer]["blk"]
+        for i, p in enumerate(self.blocks):
+            if m.per_layer:                                # one table, rebuilt per layer (bounded memory, see table_limit)
+                hip.mod_table(self.mod[i:i + 1], e0, tab, m.rows_per_batch, 0b010010, self.mdens[i:i + 1], dens0,
+                              0xFF1FF0 if dens0 is not None else -1)
+            T = tab[0 if m.per_layer else i]
+            self._self_attention(i, p, T, m, ws)
+            self._cross_attention(i, p, m, ws)
+            self._ffn(i, p, T, m, ws)
+
+    def _heads(self, m, ws):
+        """q, k, v [B, lc, heads, 128] of ws["qkv"] and the attention output ws["ao"] as the same views."""
+        q4, k4, v4 = ws["qkv"].view(m.B, m.lc, 3, self.nh, self.hd).unbind(2)
+        return q4, k4, v4, ws["ao"].view(m.B, m.lc, self.nh, self.hd)
+
+    def _ln_a(self, m, ws, rows, nxt=None, **kw):
+        """LN + modulate of the first `rows` rows of the residual stream as the A operand of the next GEMM: bf16 rows of ws["h"]
+        (returns (None, False)), or with fp8 on ((e4m3 rows, row scales), whether FFN1's output scales were written) (_ln_fp8)."""
+        x, h = ws["x"][:rows], ws["h"][:rows]
+        if m.fp8:
+            a8, sa, bound = self._ln_fp8(x, ws, h, nxt, **kw)
+            return (a8, sa), bound
+        hip.ln_modulate(x, out=h, eps=self.eps, **kw)
+        return None, False
+
+    def _out_proj(self, i, p, wname, bname, a, ws, rows, fp8, **kw):
+        """ws["x"][:rows] += (a @ W^T + b) [* gate]: bf16 MFMA, or (FLEXAM_FP8_OPROJ) fp8 MFMA on `a` row-quantised by one more pass."""
+        x = ws["x"][:rows]
+        if fp8:
+            a8, sa = hip.quantize_rows_fp8(a, ws["a8d"][:rows], ws["sa"][:rows])
+            w8 = self._fp8_w[i]
+            hip.gemm_fp8_gate_residual(a8, sa, w8[wname], w8["s_" + wname], p[bname], x, **kw)
+        else:
+            hip.gemm_gate_residual(a, p[wname], p[bname], x, **kw)
+
+    def _norm_rope_qk(self, p, m, ws, nb, bufs=None):
+        """RMSNorm + RoPE of q and k of the first nb samples at this chunk's token offset.  With bufs (SAGE_ATTENTION) q, k and v become
+        the MXFP8 operands of the quantised attention (csrc/attn_fp8.inc): at the 5B model's 24 heads (sage_fused) the RMSNorm + RoPE
+        launch writes Q and K as operands directly and V is packed on its own; otherwise q and k are normed in bf16 and all three packed."""
+        d, rows, cd = self.dim, nb * m.lc, self.cond
+        q, k = ws["qkv"][:rows, 0:d], ws["qkv"][:rows, d:2 * d]
+        q4, k4, v4, _ = self._heads(m, ws)
+        if bufs is not None and m.sage_fused:
+            hip.rmsnorm_rope_mx(q, p["nq"], k, p["nk"], bufs, cd["cos"], cd["sin"], m.lc, m.tok0, eps=self.eps)
+            hip.attn_fp8_pack(None, None, v4[:nb], bufs)
+            return
+        hip.rmsnorm_rope(q, p["nq"], k, p["nk"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=m.lc,
+                         token_offset=m.tok0, head_dim=self.hd)
+        if bufs is not None:
+            hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs)
+
+    def _self_attention(self, i, p, T, m, ws):
+        """LN + modulate -> q|k|v -> self-attention in this forward's layout (one rank, all-to-all over heads or K|V all-gather) ->
+        output projection + gated residual."""
+        d = self.dim
+        nb = 1 if (m.share0 and i == 0) else m.B          # samples that run the self-attention half of this block (share0: _mode)
+        mb = nb * m.lc
+        ri = ws["row_index"][:mb] if ws["row_index"] is not None else None
+        a8sa, _ = self._ln_a(m, ws, mb, shift=T[:, 0], scale=T[:, 1], row_index=ri, rows_per_batch=m.lc)
+        gate = dict(gate=T[:, 2], gate_row=ri, rows_per_batch=m.lc)
+        if m.sp > 1 and m.sp_mode == "ulysses":
+            # all tokens of H/sp heads per rank: q|k|v all-to-all -> attention -> all-to-all back; the o-projection reads the
+            # returned blocks in place (flexam_amd/dist.py)
+            a_o, koff_o = self._ulysses_attention(a8sa, i, p, m, ws)
+            self._out_proj(i, p, "wo", "bo", a_o, ws, mb, False, a_koff=koff_o, **gate)
+            return
+        qkv, h = ws["qkv"], ws["h"]
+        if m.sp > 1:
+            # K|V projection + K norm/RoPE first, written straight into the send buffer; their all-gather (RCCL over xGMI)
+            # runs under the Q projection, the Q norm/RoPE and the attention to the LOCAL chunk
+            # (FLEXAM_SP_FUSED_QKV=1, default: ONE q|k|v launch instead -- at a rank's few thousand rows two launches of 24 and 12 tile
+            #  columns quantise worse on 256 CUs than one of 36 (emulated rank of 8, profiles/r5*: 119 + 80 us against ~135), and the
+            #  gather starts ~15 us later, not ~80; sage_gather: the MXFP8 records travel, always one q|k|v launch)
+            whole = m.sp_fused_qkv or m.sage
+            self._proj(h, a8sa, i, p, "wqkv", "bqkv", slice(None) if whole else slice(d, None), qkv if whole else qkv[:, d:])
+            if m.sage:
+                self._allgather_attention_mx(p, m, ws)
+            else:
+                self._allgather_attention(a8sa, i, p, m, ws)
+            self._out_proj(i, p, "wo", "bo", ws["ao"], ws, mb, False, **gate)
+            return
+        self._proj(h[:mb], a8sa, i, p, "wqkv", "bqkv", slice(None), qkv[:mb])
+        q4, k4, v4, ao4 = self._heads(m, ws)
+        if m.sage:
+            bufs = self._attn8_buffers(nb, m.lc)
+            self._norm_rope_qk(p, m, ws, nb, bufs)
+            hip.attn_fwd_fp8(bufs, m.lc, out=ao4[:nb])
+        else:
+            self._norm_rope_qk(p, m, ws, nb)
+            hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)
+        self._out_proj(i, p, "wo", "bo", ws["ao"][:mb], ws, mb, m.fp8_oproj, **gate)
+        if nb < m.B:
+            xr = ws["x"].view(m.B, m.lc, d)
+            hip.host_op(lambda: xr[1].copy_(xr[0]))         # (a torch copy, not a library call: a host step of a recorded plan)
+
+    def _cross_attention(self, i, p, m, ws):
+        """Cross-attention on the text context (K/V precomputed per clip): LN -> Q (on the fp8 pipe as well with fp8 on) -> attention
+        -> output projection + residual."""
+        d, cd, o = self.dim, self.cond, m.only_row
+        qc = ws["qkv"][:, 0:d]
+        a8sa, _ = self._ln_a(m, ws, m.B * m.lc, ln_w=p["n3w"], ln_b=p["n3b"])
+        self._proj(ws["h"], a8sa, i, p, "cwq", "cbq", slice(None), qc)
+        hip.rmsnorm_rope(qc, p["cnq"], eps=self.eps)
+        kv = cd["cross_kv"][i][slice(None) if o is None else slice(o, o + 1)]
+        heads = lambda t: t.unflatten(2, (self.nh, self.hd))
+        q4, _, _, ao4 = self._heads(m, ws)
+        if cd.get("cross_lk"):                             # the identical padded text rows as ONE weighted key
+            lk = cd["cross_lk"]
+            hip.attn_fwd_lastkey(q4, heads(kv[:, :lk, 0:d]), heads(kv[:, :lk, d:]), cd["cross_mult"], out=ao4, prescaled=True)
+        else:
+            hip.attn_fwd(q4, heads(kv[:, :, 0:d]), heads(kv[:, :, d:]), out=ao4, prescaled=True)
+        self._out_proj(i, p, "cwo", "cbo", ws["ao"], ws, m.B * m.lc, m.fp8_oproj)
+
+    def _ffn(self, i, p, T, m, ws):
+        """LN + modulate -> FFN1 + GELU -> FFN2 + gated residual."""
+        ri = ws["row_index"]
+        gate = dict(gate=T[:, 5], gate_row=ri, rows_per_batch=m.lc)
+        if not m.fp8:
+            self._ln_a(m, ws, m.B * m.lc, shift=T[:, 3], scale=T[:, 4], row_index=ri, rows_per_batch=m.lc)
+            # (FFN1 -> FFN2 per row chunk, so that the [M, 14336] intermediate stays in the Infinity Cache: the clock rises with the
+            #  saved HBM traffic, but tile quantisation and launch ramps cost more: +0.5 / +1.6 / +7.1 % of a step at 2 / 4 / 7 chunks,
+            #  profiles/r4p_ffn_row_chunks.txt)
+            hip.gemm(ws["h"], p["w1"], p["b1"], out=ws["ffn"], epilogue=hip.EPI_GELU_TANH)
+            hip.gemm_gate_residual(ws["ffn"], p["w2"], p["b2"], ws["x"], **gate)
+            return
+        w8 = self._fp8_w[i]
+        # FFN1 writes FFN2's e4m3 operand itself: its output row scales are known before it runs (a bound from the row's L2 norm, written
+        # by the LN launch), so there is no absmax / quantise pass over the [M, 14336] intermediate
+        # (FLEXAM_FP8_FFN_APRIORI=0: the earlier form -- bf16 intermediate + an absmax row quantiser pass -- for checkpoints whose w1
+        #  has a few very large rows: the bound is set by the LARGEST row norm, so every ordinary row's outputs then sit lower in
+        #  e4m3's range.  One scale per output row has to cover all 14336 columns, so a per-tile bound cannot be used by FFN2.)
+        (a8, sa), bound = self._ln_a(m, ws, m.B * m.lc, nxt=(w8["w1_norm"], w8["b1_max"]) if m.ffn_apriori else None, shift=T[:, 3],
+                                     scale=T[:, 4], row_index=ri, rows_per_batch=m.lc)
+        if bound:
+            hip.gemm_fp8_gelu_q(a8, sa, w8["w1"], w8["s_w1"], p["b1"], ws["so"], ws["a8"])
+            a8, sa = ws["a8"], ws["so"]
+        else:                                              # widths the fused LN launch does not cover: bf16 intermediate + row quantiser
+            hip.gemm_fp8(a8, sa, w8["w1"], w8["s_w1"], p["b1"], out=ws["ffn"], epilogue=hip.EPI_GELU_TANH)
+            a8, sa = hip.quantize_rows_fp8(ws["ffn"], ws["a8"], ws["sa"])
+        hip.gemm_fp8_gate_residual(a8, sa, w8["w2"], w8["s_w2"], p["b2"], ws["x"], **gate)
+
+    def _head(self, m, ws):
+        H = ws["tabs", m.R, m.per_layer]["head"][0]
+        hip.ln_modulate(ws["x"], out=ws["h"], eps=self.eps, shift=H[:, 0], scale=H[:, 1], row_index=ws["row_index"], rows_per_batch=m.lc)
+        hip.gemm(ws["h"], self.head_w, self.head_b, out=ws["head"])
 
     # ------------------------------------------------------------------ block-level seam
     def _run_block_modules(self, xres, B, lc, e0, row_index, rows_per_batch, dens0, t_rows, rsel):
@@ -734,7 +774,7 @@ class DiTEngine:
         return calc
 
     # ------------------------------------------------------------------ sequence parallel
-    def _ulysses_attention(self, qkv, hbuf, a8sa, layer, p, B, lc, tok0, sage=False):
+    def _ulysses_attention(self, a8sa, layer, p, m, ws):
         """h [B*lc, C] (LayerNorm output of this rank's tokens) -> q|k|v projection -> exchange -> attention -> exchange back ->
         (A base view, per-K-block A offsets) of the attention output for the o-projection.  Head group j = heads j*H/sp .. goes
         to rank j.
@@ -749,11 +789,11 @@ class DiTEngine:
         call runs while sample b + 1's blocks arrive and sample b - 1's output returns -- only the last return is not under compute;
         it pays when a link is slower than the ~0.1 ms the two smaller attention calls cost (about 35 GB/s at 8 GPUs)."""
         from .dist import all_to_all_blocks
-        sp, nh, hd, d, dev = self.sp_size, self.nh, self.hd, self.dim, self.device
+        sp, nh, hd, d, dev = m.sp, self.nh, self.hd, self.dim, self.device
+        B, lc, tok0, qkv, hbuf = m.B, m.lc, m.tok0, ws["qkv"], ws["h"]
         hg = nh // sp
         G = hg * hd
         W = 3 * G
-        ws = self._ws[(B, lc)]
         if "a2a_send" not in ws:
             ws["a2a_send"] = torch.empty(B, sp, lc, W, device=dev, dtype=BF16)
             ws["a2a_recv"] = torch.empty(B, sp, lc, W, device=dev, dtype=BF16)
@@ -768,9 +808,9 @@ class DiTEngine:
 
         def attend(b0, nb):
             """Attention of samples b0 .. b0 + nb - 1 on this rank's heads over all tokens; SAGE_ATTENTION: the received bf16 q|k|v are
-            packed into MXFP8 operands first (flexam_attn_fp8_pack) and the quantised kernel runs (run() only asks for it when nk = sp * lc)."""
+            packed into MXFP8 operands first (flexam_attn_fp8_pack) and the quantised kernel runs (_mode only asks for it when nk = sp * lc)."""
             q_, k_, v_ = full[b0:b0 + nb, :, 0], full[b0:b0 + nb, :nk, 1], full[b0:b0 + nb, :nk, 2]
-            if sage:
+            if m.sage:
                 bufs = self._attn8_buffers(nb, sp * lc, hg)
                 hip.attn_fp8_pack(q_, k_, v_, bufs)
                 hip.attn_fwd_fp8(bufs, sp * lc, out=out[b0:b0 + nb])
@@ -804,7 +844,7 @@ class DiTEngine:
             for b in bs:
                 if st[which][b] is not None:
                     st[which][b].wait()
-        if B == 1 or not self.sp_overlap:
+        if B == 1 or m.sp_overlap_level == 0:
             project_and_pack(slice(None), 0, B)
             hip.host_op(lambda: [go_there(b, False) for b in range(B)])
             attend(0, B)
@@ -813,7 +853,7 @@ class DiTEngine:
         for b in range(B):
             project_and_pack(slice(b * lc, (b + 1) * lc), b, 1)
             hip.host_op(lambda b=b: go_there(b, True))
-        if self.sp_overlap_level < 2:
+        if m.sp_overlap_level < 2:
             hip.host_op(lambda: wait("there", range(B)))
             attend(0, B)
             hip.host_op(lambda: ([go_back(b, True) for b in range(B)], wait("back", range(B))))
@@ -845,7 +885,7 @@ class DiTEngine:
             return hip.gemm_fp8(a8sa[0], a8sa[1], w8[wname][rows], w8["s_" + wname][rows], p[bname][rows], out=out)
         return hip.gemm(hbuf, p[wname][rows], p[bname][rows], out=out)
 
-    def _allgather_attention(self, qkv, hbuf, a8sa, layer, p, ao4, q4, B, lc, tok0, q_done=False):
+    def _allgather_attention(self, a8sa, layer, p, m, ws):
         """K|V of this rank's tokens are in qkv[:, C:] (projected, not yet normed).  The RMSNorm+RoPE launch writes K (normed,
         rotated) and V into the send buffer, cut into `sp_pieces` groups of heads: [G, B, lc, 2*C/G].  One all-gather per group
         and CFG row assembles [G, B, L, 2*C/G] in token order (the rank-major concatenation IS the token order: no re-layout
@@ -858,12 +898,13 @@ class DiTEngine:
         land together; cutting along the heads gives pieces that are complete work for part of the kernel, so all links stay
         busy in every phase (reference call sites of the missing exchange: wan_transformer3d_FlexAM.py:801-815, 970-975)."""
         from .dist import all_gather_into_tensor, group_backend
-        sp, nh, hd, d, dev = self.sp_size, self.nh, self.hd, self.dim, self.device
-        ws = self._ws[(B, lc)]
+        sp, nh, hd, d, dev = m.sp, self.nh, self.hd, self.dim, self.device
+        B, lc, tok0, qkv = m.B, m.lc, m.tok0, ws["qkv"]
+        q4, _, _, ao4 = self._heads(m, ws)
         L = sp * lc                                    # rows of the gathered buffer (the padded sequence)
         Lr = self.cond["L"]                            # keys: the real tokens; rows Lr .. L - 1 are zero pads (FX.py:919-925) and end every key range
         n_loc = max(0, min(lc, Lr - tok0))             # real tokens of the local chunk
-        G = self.sp_pieces
+        G = m.sp_pieces
         cb, hg = d // G, nh // G
         if "kv_send" not in ws:
             ws["kv_send"] = torch.empty(G, B, lc, 2 * cb, device=dev, dtype=BF16)
@@ -893,15 +934,15 @@ class DiTEngine:
                 if w is not None:
                     w.wait()
         hip.host_op(issue)
-        if not q_done:
-            self._proj(hbuf, a8sa, layer, p, "wqkv", "bqkv", slice(0, d), qkv[:, 0:d])
+        if not m.sp_fused_qkv:
+            self._proj(ws["h"], a8sa, layer, p, "wqkv", "bqkv", slice(0, d), qkv[:, 0:d])
         hip.rmsnorm_rope(qkv[:, 0:d], p["nq"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=lc, token_offset=tok0,
                          head_dim=hd)
         heads = lambda t: t.unflatten(2, (hg, hd))
         for g in range(G):
             qg, og = q4[:, :, g * hg:(g + 1) * hg], ao4[:, :, g * hg:(g + 1) * hg]
             kc, vc = cat[g, :, :, 0:cb], cat[g, :, :, cb:]
-            if g > 0 or not self.sp_overlap:
+            if g > 0 or m.sp_overlap_level == 0:
                 hip.host_op(lambda g=g: wait(g))
                 hip.attn_fwd(qg, heads(kc[:, :Lr]), heads(vc[:, :Lr]), out=og, prescaled=True)
                 continue
@@ -916,30 +957,21 @@ class DiTEngine:
                 n += hip.attn_fwd_partial(qg, heads(kc[:, tok0 + lc:Lr]), heads(vc[:, tok0 + lc:Lr]), ws["kv_part"], n, s_after, prescaled=True)
             hip.attn_merge(og, ws["kv_part"], n, prescaled=True)
 
-    def _allgather_attention_mx(self, qkv, p, ao4, q4, k4, v4, B, lc, tok0):
+    def _allgather_attention_mx(self, p, m, ws):
         """SAGE_ATTENTION under the K|V all-gather (r6; the reference's `sageattn` switch, attention_utils.py:195-203, with the exchange of
         the missing FlexAM/dist, wan_transformer3d_FlexAM.py:801-815): this rank's q, k (RMSNorm + RoPE at the chunk's global offset) and
-        v become MXFP8 operands -- written by the RMSNorm + RoPE launch itself at the 5B width (flexam_rmsnorm_rope_mx; the V half by the
-        pack kernel), else normed in bf16 and packed --, ONE all-gather moves the key / value RECORDS ([B, H, lc / 64] x 18 KiB per rank:
+        v become MXFP8 operands (_norm_rope_qk), ONE all-gather moves the key / value RECORDS ([B, H, lc / 64] x 18 KiB per rank:
         288 bytes per key and head instead of 512 in bf16; the rank-major result is the chunk layout flexam_attn_fwd_fp8_chunked reads),
-        and one attention call of the local queries over all L real keys follows.  lc is a multiple of 64 (run() pads to 64 x ranks)."""
+        and one attention call of the local queries over all L real keys follows.  lc is a multiple of 64 (_mode pads to 64 x ranks)."""
         from .dist import all_gather_into_tensor
-        sp, nh, hd, d = self.sp_size, self.nh, self.hd, self.dim
-        cd = self.cond
-        ws = self._ws[(B, lc)]
+        sp, B, lc = m.sp, m.B, m.lc
         bufs = self._attn8_buffers(B, lc)
         if "kv8_all" not in ws:
             ws["kv8_all"] = torch.empty(sp, *bufs[2].shape, device=self.device, dtype=torch.uint8)
         kv8_all = ws["kv8_all"]
-        if nh == 24 and hd == 128 and os.environ.get("FLEXAM_SAGE_FUSED", "1") != "0":
-            hip.rmsnorm_rope_mx(qkv[:, 0:d], p["nq"], qkv[:, d:2 * d], p["nk"], bufs, cd["cos"], cd["sin"], lc, tok0, eps=self.eps)
-            hip.attn_fp8_pack(None, None, v4, bufs)
-        else:
-            hip.rmsnorm_rope(qkv[:, 0:d], p["nq"], qkv[:, d:2 * d], p["nk"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"],
-                             tokens_per_batch=lc, token_offset=tok0, head_dim=hd)
-            hip.attn_fp8_pack(q4, k4, v4, bufs)
+        self._norm_rope_qk(p, m, ws, B, bufs)
         hip.host_op(lambda: all_gather_into_tensor(kv8_all.view(sp * B, *bufs[2].shape[1:]), bufs[2], group=self.sp_group))
-        hip.attn_fwd_fp8_chunked(bufs[0], bufs[1], kv8_all, lc, cd["L"], out=ao4)
+        hip.attn_fwd_fp8_chunked(bufs[0], bufs[1], kv8_all, lc, self.cond["L"], out=self._heads(m, ws)[3])
 
     def gather_tokens(self, head_local: torch.Tensor) -> torch.Tensor:
         """All-gather of the head output [B, Lc, 192] -> [B, L, 192] (the reference's one collective,

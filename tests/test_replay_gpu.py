@@ -106,7 +106,9 @@ def test_replayed_sampler_steps_equal_launch_by_launch_steps(variant, monkeypatc
 
 def test_new_conditioning_and_a_new_shape_get_new_plans():
     """Plans live in the per-clip state: a second clip (other conditioning CONTENTS in the same buffers' places, then another latent
-    shape) must not run the first clip's launches.  forward() through the reference's call signature, replay on: equal to replay off."""
+    shape) must not run the first clip's launches, and neither must the same clip once a mode switch flipped between two forwards (the
+    last call: VIDEOX_ATTENTION_TYPE, read per forward).  forward() through the reference's call signature, replay on: equal to replay
+    off."""
     cfg = dict(O.DIT_TINY)
     m = _model(cfg)
     outs = {}
@@ -114,19 +116,26 @@ def test_new_conditioning_and_a_new_shape_get_new_plans():
         os.environ["FLEXAM_REPLAY"] = replay
         try:
             res = []
-            for seed, (f, h, w) in ((41, (3, 16, 16)), (43, (3, 16, 16)), (41, (3, 16, 16)), (47, (5, 16, 24))):
+            for seed, (f, h, w), attn in ((41, (3, 16, 16), None), (43, (3, 16, 16), None), (41, (3, 16, 16), None), (47, (5, 16, 24), None),
+                                          (47, (5, 16, 24), "SAGE_ATTENTION")):
                 case = C.dit_case(cfg, seed, frames=f, h=h, w=w)
                 d = {k: ([u.to(DEV) for u in v] if isinstance(v, list) else (v.to(DEV) if torch.is_tensor(v) else v)) for k, v in case.items()}
+                n_cond = m.engine().n_conditioning if attn else None
+                if attn:
+                    os.environ["VIDEOX_ATTENTION_TYPE"] = attn
                 res.append(m(**d).float().cpu())
+                assert n_cond is None or m.engine().n_conditioning == n_cond      # (the same clip: its plans are still there)
                 assert not m.engine().replay_taken           # new conditioning (or a new shape): recorded afresh, never the old clip's launches
                 res.append(m(**d).float().cpu())             # the same call again (a new per-token timestep tensor, as the reference's loop builds one per step)
                 assert bool(m.engine().replay_taken) == (replay == "1")
             outs[replay] = res
         finally:
             os.environ.pop("FLEXAM_REPLAY", None)
+            os.environ.pop("VIDEOX_ATTENTION_TYPE", None)
     for a, b in zip(outs["0"], outs["1"]):
         assert torch.equal(a, b)
     assert torch.equal(outs["1"][0], outs["1"][1]) and not torch.equal(outs["1"][0], outs["1"][2])
+    assert not torch.equal(outs["1"][6], outs["1"][8])             # the switch took effect: quantised self-attention
 
 
 def test_emulated_rank_replays_with_collectives_as_host_steps():
