@@ -164,8 +164,8 @@ ATTN_SOURCES = ("flexam_amd/csrc/attn.hip", "flexam_amd/csrc/attn_fp8.inc", "fle
 ATTN_TRAFFIC_FILE = "profiles/head_attn_traffic.json"
 
 
-# compile-time switches of DIAGNOSTIC builds (tools/build_attn_variants.py, -DFLEXAM_DIAGNOSTIC_BUILD): never defined in the product
-# library, so the text they guard is not part of what the counter record was measured on
+# compile-time switches of the DIAGNOSTIC builds that earlier versions of attn.hip carried: never defined in the product library, so
+# text they guard is not part of what the counter record was measured on (kept so that older sources hash as they did)
 ATTN_DIAGNOSTIC_MACROS = ("FLEXAM_ATTN_STAMPS", "A32_NOMAX_ABLATE", "A32_VALU", "FLEXAM_ATTN_BODY16", "A32_RESCALE_THR", "A32_HALF_FRAG_ABLATE", "FLEXAM_DIAGNOSTIC_BUILD")
 
 

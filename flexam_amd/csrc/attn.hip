@@ -159,30 +159,15 @@ __device__ __forceinline__ float pair_sum(float x) {
 // (A 4-wave x 64-row variant -- each K/V fragment feeding two MFMAs -- was tried in r1: hipcc cannot keep
 //  Q in the accumulator file and spills 150+ VGPRs; see DESIGN.md.)
 // ------------------------------------------------------------------------------------------------
-#if (defined(FLEXAM_ATTN_STAMPS) || defined(A32_NOMAX_ABLATE) || defined(A32_VALU) || defined(FLEXAM_ATTN_BODY16) || defined(A32_RESCALE_THR) || defined(A32_HALF_FRAG_ABLATE)) && !defined(FLEXAM_DIAGNOSTIC_BUILD)
-#error "FLEXAM_ATTN_STAMPS / A32_NOMAX_ABLATE / A32_VALU / FLEXAM_ATTN_BODY16 / A32_RESCALE_THR / A32_HALF_FRAG_ABLATE are switches of diagnostic builds (timing ablations give WRONG results): add -DFLEXAM_DIAGNOSTIC_BUILD (tools/build_attn_variants.py does)"
-#endif
 #ifndef A32_DEFER
 #define A32_DEFER 0      // scores of a half tile whose exp2 / sum / pack wait for part A of the next step (see stepA); 0 = none
 #endif
-#ifdef FLEXAM_ATTN_STAMPS      // diagnostic builds only (MI355X_MICROARCH.md, DVFS give-back item 6): the in-kernel clock of the main loop
-__device__ unsigned long long g_attn_stamps[2 * 8192];      // per workgroup: shader cycles and 100 MHz ticks across the tile loop; read by nobody on the device
-__device__ unsigned long long g_attn_barrier_wait[8 * 8192];   // per workgroup and wave: shader cycles spent in the tile loop's s_barrier
-#define ATTN_STAMP_DECL() unsigned long long st0_ = 0, sr0_ = 0, bw_ = 0
-#define ATTN_STAMP_BEGIN() st0_ = __builtin_amdgcn_s_memtime(), sr0_ = __builtin_amdgcn_s_memrealtime()
-#define ATTN_STAMP_BARRIER(stmt) { const unsigned long long b0_ = __builtin_amdgcn_s_memtime(); stmt; bw_ += __builtin_amdgcn_s_memtime() - b0_; }
-#define ATTN_STAMP_END()                                                             \
-  if ((threadIdx.x & 63) == 0 && blockIdx.x < 8192) g_attn_barrier_wait[8 * blockIdx.x + (threadIdx.x >> 6)] = bw_;  \
-  if (threadIdx.x == 0 && blockIdx.x < 8192) {                                       \
-    g_attn_stamps[2 * blockIdx.x] = __builtin_amdgcn_s_memtime() - st0_;             \
-    g_attn_stamps[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime() - sr0_;     \
-  }
-#else
+// (ATTN_STAMP_*, A32_DEFER and body16 in attn_run are inert; they are part of the text the counter record in
+// profiles/head_attn_traffic.json was hashed from and go with the next change to this kernel)
 #define ATTN_STAMP_DECL()
 #define ATTN_STAMP_BEGIN()
 #define ATTN_STAMP_BARRIER(stmt) stmt
 #define ATTN_STAMP_END()
-#endif
 constexpr int NT = 512;
 constexpr int NSLOT = 4;
 constexpr int V_RING = NSLOT * KV_TILE_BYTES;   // LDS: [4 K slots][4 V slots]
@@ -192,12 +177,8 @@ using IC = std::integral_constant<int, V>;
 // P that is not exactly 1, i.e. with a bf16 rounding error the exact-maximum form does not have -- attention error against fp64 on
 // peaked rows (logit std 6, L = 11648) 1.51e-3 rms at 2^0, 1.77e-3 at 2^8, 2.10e-3 at 2^24 -- while the rescale branch costs
 // +1.2 % of a denoise step at 2^4 and -0.5 / -0.9 / -1.3 ... -2.1 % at 2^12 / 2^16 / 2^24 on such rows (nothing on N(0, 1) logits).
-// 8 stays: parity before speed.  -DA32_RESCALE_THR=n builds the other points (diagnostic builds).
-#ifdef A32_RESCALE_THR
-constexpr float RESCALE_THR_LOG2 = (float)A32_RESCALE_THR;
-#else
+// 8 stays: parity before speed.
 constexpr float RESCALE_THR_LOG2 = 8.0f;
-#endif
 
 // KIND: 0 = self-attention, 1 = short-context (text) attention: distinct profiler symbols.
 // PRE: q was multiplied by softmax_scale * log2(e) by its producer, BEFORE its one rounding to bf16 (in the DiT: folded into the
@@ -359,13 +340,8 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     constexpr int ghalf = decltype(ghalf_c)::value, ds0 = decltype(ds0_c)::value;
     constexpr int slot = (ghalf >> 1) & (NSLOT - 1);
     constexpr int imm = slot * KV_TILE_BYTES + (ghalf & 1) * 8192;
-#ifdef A32_HALF_FRAG_ABLATE     // TIMING ABLATION (WRONG results): half the K / V fragment reads per MFMA, everything else as it is -- the ceiling of what
-#pragma unroll                  // a tiling with 64 query rows per wave (each fragment feeding two MFMAs) could win at THIS occupancy
-    for (int i = 0; i < 2; ++i) kf[i] = kf[2 + i] = *(const bf16x8*)(kaddr[ds0 + i] + imm);
-#else
 #pragma unroll
     for (int i = 0; i < 4; ++i) kf[i] = *(const bf16x8*)(kaddr[ds0 + i] + imm);
-#endif
   };
   // ... and their 4 MFMAs of the S^T chain
   auto qk_mma = [&](auto ds0_c, const bf16x8 (&kf)[4], f32x16& sacc) {
@@ -424,11 +400,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     for (int ss = 0; ss < 2; ++ss) {
       bf16x8 vf[4];
 #pragma unroll
-#ifdef A32_HALF_FRAG_ABLATE
-      for (int dt = 0; dt < 2; ++dt) {
-#else
       for (int dt = 0; dt < 4; ++dt) {                                                   // 8 transposed reads first ...
-#endif
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vaddr[0][dt] + imm + ss * 4096));
         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vaddr[1][dt] + imm + ss * 4096));
         const bf16x4 lo_b = __builtin_bit_cast(bf16x4, lo), hi_b = __builtin_bit_cast(bf16x4, hi);
@@ -438,9 +410,6 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
           vf[dt][4 + e] = hi_b[e];
         }
       }
-#ifdef A32_HALF_FRAG_ABLATE
-      vf[2] = vf[0]; vf[3] = vf[1];
-#endif
 #pragma unroll
       for (int dt = 0; dt < 4; ++dt)                                                     // ... then 4 MFMAs
         o_acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[dt], pf_prev[ss], o_acc[dt], 0, 0, 0);
@@ -531,11 +500,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     const float m1 = vmax8(s_cur[8], s_cur[9], s_cur[10], s_cur[11], s_cur[12], s_cur[13], s_cur[14], s_cur[15]);
     // the test needs no row maximum: any(lane maximum > THR) over the wave is any(row maximum > THR); the exchange between the
     // two lanes of a row happens in the rare branch only (-0.7 % of a step, profiles/r4e_*)
-#ifdef A32_NOMAX_ABLATE      // TIMING ABLATION (WRONG results when a rescale would have been needed): what the 9 maxima of a half tile cost
-    const float mloc = s_cur[0];      // one score instead of the lane maximum: the test and its branch stay, the 9 maxima go
-#else
     const float mloc = vmax(m0, m1);
-#endif
     if constexpr (PRE) {
       // ---- deferred rescale (always taken for half 0, which sets the reference to the first row maximum): O, l, the pending
       // P(g-1), the scores of this half and the already started chain of the next half all move to the new reference
@@ -609,11 +574,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     for (int i = 0; i < 12; ++i) {
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS read
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-#ifdef A32_VALU
-      __builtin_amdgcn_sched_group_barrier(0x002, A32_VALU, 0);
-#else
       __builtin_amdgcn_sched_group_barrier(0x002, PRE ? (DEF >= 4 ? 3 : 4) : 5, 0);   // VALU (exp2 / fma / add / cvt)
-#endif
     }
   };
 
@@ -719,9 +680,6 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   }   // q blocks of this workgroup
 }
 
-#ifdef FLEXAM_ATTN_BODY16
-#include "attn_body16.inc"
-#endif
 #include "attn_fp8.inc"
 
 // out[b][q][head][:] = sum_s w_s O_s / sum_s w_s l_s with w_s = exp2((m_s - max_s m_s) * scale_log2e) for the rows of the
@@ -793,12 +751,6 @@ int attn_run(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k
   auto kern = cross ? (p.prescaled ? attn_fwd_kernel<1, true> : attn_fwd_kernel<1, false>)
                     : (p.prescaled ? attn_fwd_kernel<0, true> : attn_fwd_kernel<0, false>);
   bool body16 = false;
-#ifdef FLEXAM_ATTN_BODY16                              // diagnostic builds only (attn_body16.inc): the 16x16x32 body, selected per call
-  const char* be = getenv("FLEXAM_ATTN_BODY");
-  body16 = be && atoi(be) == 16;
-  if (body16) kern = cross ? (p.prescaled ? attn_fwd16_kernel<1, true> : attn_fwd16_kernel<1, false>)
-                           : (p.prescaled ? attn_fwd16_kernel<0, true> : attn_fwd16_kernel<0, false>);
-#endif
   // the text cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup
   const char* se_ = getenv("FLEXAM_ATTN_SHORT");       // read per call (A/B in one process); 0 = one workgroup per q block
   const bool short_ctx = !q8 && cross && p.prescaled && tiles_all <= NSLOT && kv_splits == 1 && partial_slot0 < 0 && !body16 && !(se_ && atoi(se_) == 0);
@@ -940,16 +892,6 @@ extern "C" int flexam_attn_fwd_fp8_chunked(const void* q8, const void* qs, const
   return attn_run(nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, o, o_bs, o_rs, B, H, Lq, Lk, head_dim, FLEXAM_ATTN_PRESCALED, kv_splits,
                   split_from_unit, ws_o, ws_ml, stream, -1, 0.f, q8, qs, kv8, chunk_tiles);
 }
-
-#ifdef FLEXAM_ATTN_STAMPS
-// diagnostic builds only (not declared in flexam_hip.h): copies the per-workgroup stamps of the last attention launch to the host
-extern "C" int flexam_debug_attn_stamps(unsigned long long* out, int n_workgroups) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_stamps), (size_t)n_workgroups * 16) == hipSuccess ? 0 : -1;
-}
-extern "C" int flexam_debug_attn_barrier_wait(unsigned long long* out, int n_workgroups) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_attn_barrier_wait), (size_t)n_workgroups * 64) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int head_dim, float softmax_scale,
                                  int n_slots, const float* ws_o, const float* ws_ml, void* stream) {

@@ -23,7 +23,7 @@
 //    ends up with 4 consecutive N columns of one output row -> 8-byte bf16 / 16-byte f32 stores.
 //  * workgroup -> tile map is XCD-aware: the 8 XCDs (private 4 MiB L2 each) get contiguous
 //    chunks of the tile list, walked in groups of 4 tile-rows so concurrently resident tiles
-//    share A row-panels and W column-panels in L2 (FLEXAM_GEMM_GM overrides the group height).
+//    share A row-panels and W column-panels in L2.
 #include <math.h>
 #include <stdlib.h>
 
@@ -59,27 +59,11 @@ struct GemmParams {
   int units, split_full, split_s;
   float* ws;
   int x_nt;                // gate-residual epilogue: X leaves / arrives with non-temporal hints (launch() decides: only when X is larger than the Infinity Cache can keep)
-  int debug;               // only in -DFLEXAM_GEMM_ABLATE builds (timing ablations, WRONG results): 1 no vmcnt wait, 2 no barrier, 4 no LDS-DMA, 8 half the ds_reads, 16 half the LDS-DMA
 };
 
 template <int V>
 using IC = std::integral_constant<int, V>;
 
-#if (defined(FLEXAM_GEMM_ABLATE) || defined(FLEXAM_GEMM_HALF_FRAG) || defined(FLEXAM_GEMM_STAMPS)) && !defined(FLEXAM_DIAGNOSTIC_BUILD)
-#error "FLEXAM_GEMM_ABLATE / FLEXAM_GEMM_HALF_FRAG (WRONG results: timing ablations) and FLEXAM_GEMM_STAMPS (in-kernel clock stamps) are switches of diagnostic builds: add -DFLEXAM_DIAGNOSTIC_BUILD"
-#endif
-#ifdef FLEXAM_GEMM_ABLATE
-#define ABLATE(p, bit) ((p).debug & (bit))
-#else
-#define ABLATE(p, bit) 0
-#endif
-
-#ifdef FLEXAM_GEMM_STAMPS      // diagnostic builds only: the anatomy of a launch -- per workgroup the 100 MHz counter at kernel entry, when the first K block of its
-__device__ unsigned long long g_gemm_stamps[4 * 1024];      // first unit has landed, at the end of its last K loop and at exit; read by nobody on the device
-#define GEMM_STAMP(i) if (threadIdx.x == 0 && blockIdx.x < 1024) g_gemm_stamps[4 * blockIdx.x + (i)] = __builtin_amdgcn_s_memrealtime()
-#else
-#define GEMM_STAMP(i)
-#endif
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GATE_RESIDUAL = 2 };
 
 // MT = 16-row m-tiles per wave: the workgroup tile is (32*MT) x 256 outputs, 8 waves = 2(M) x 4(N), two per SIMD.
@@ -145,7 +129,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   asm volatile("" : "+s"(wave));
   const int wm = wave / WNW, wn = wave % WNW;
-  if constexpr (!TAIL) { GEMM_STAMP(0); }
 
   // ---- persistent workgroups over an XCD-aware, grouped tile order: workgroup w lives on XCD w & 7 (round-robin
   // dispatch); that XCD owns a contiguous chunk of the tile list and its gridDim/8 workgroups walk the chunk with
@@ -293,15 +276,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     const char* sbase = i < PA ? a_tile + ka * 2 : w_tile + kw * 2;
     const uint32_t voff = i < PA ? a_off[i] : w_off[i - PA];
     const uint32_t dst = (uint32_t)(uintptr_t)LDS_PTR(buf) + (i < PA ? i * 8192 : A_BYTES + (i - PA) * 8192) + wave * 1024;
-    if (ABLATE(p, 4) || (ABLATE(p, 16) && i >= PA)) return;      // 16: no W-tile staging (half the LDS-DMA)
     // M0 (the LDS base of the DMA) is written and NOT restored: nothing else in this kernel uses it (gfx9+ LDS instructions do not;
     // tools/isa_loopwaits.py lists any other M0 reader of the listing), and the save / restore pair was 2 of the 6 scalar
     // instructions of every piece
     asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(dst) : "memory");
   };
   auto wait_barrier = [&](auto n_c) {                  // at most N of this wave's vector-memory operations still in flight, then barrier
-    if (!ABLATE(p, 1)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_c)::value) : "memory");
-    if (!ABLATE(p, 2)) __syncthreads();
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_c)::value) : "memory");
+    __syncthreads();
   };
   // fragment j (< NF = MT + NTW) of the set of K half hf: j < NTW -> W n-tile j, else A m-tile j - NTW, all 32 deep
   auto frag = [&](const char* buf, int hf, int j) -> bf16x8 {
@@ -350,7 +332,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   else if (!pend && nkl > 1) wait_barrier(IC<NP>{});     // only K block 1 is younger than K block 0
   else wait_barrier(IC<0>{});                            // (one or two K blocks: drain everything)
   pend = false;
-  if constexpr (!TAIL) { if (it == 0) { GEMM_STAMP(1); } }
   // The staging offsets are read by asm statements inside the K loop.  Should one of them ever come back from a spill slot, the
   // compiler's own wait for that reload must land here and not in the loop, where a vmcnt(0) would drain the LDS-DMA pipeline
   // on every K block.
@@ -362,10 +343,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   frag_setup();
 #pragma unroll
   for (int g = 0; g < (NF + PER - 1) / PER; ++g) ld2(smem, 0, g, f0);
-#ifdef FLEXAM_GEMM_HALF_FRAG
-#pragma unroll
-  for (int j = 0; j < NF; ++j) f1[j] = f0[j];
-#endif
 
   auto block = [&](int kb, auto dma_c, auto rd_c, auto wait_c) {
     constexpr bool DMA = decltype(dma_c)::value, RD = decltype(rd_c)::value;
@@ -377,9 +354,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
       __builtin_amdgcn_sched_barrier(0);
       mfma_group(g, f0);
       __builtin_amdgcn_sched_barrier(0);                // MFMAs first: the wait for F0 must not cover reads issued after it
-#ifndef FLEXAM_GEMM_HALF_FRAG                           // (compile-time form of ablation 8, without its run-time tests in the loop: the ceiling of
-      if (!ABLATE(p, 8)) ld2(cur, 1, g, f1);            //  what fewer fragment reads per MFMA -- 128 x 128 wave tiles: a third fewer -- could win)  8: no phase-A fragment reads (half the ds_reads)
-#endif
+      ld2(cur, 1, g, f1);
     }
     __builtin_amdgcn_sched_barrier(0);
     wait_barrier(wait_c);
@@ -404,7 +379,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   for (; kb + 2 < nkl; ++kb) block(kb, T_{}, T_{}, IC<0>{});
   if (kb + 1 < nkl) { block(kb, F_{}, T_{}, IC<0>{}); ++kb; }
   block(kb, F_{}, F_{}, IC<0>{});
-  if constexpr (!TAIL) { GEMM_STAMP(2); }
 
   // ---- the next unit's first two K blocks go on their way before this tile's epilogue: both buffers are idle from here on
   // (every wave passed the last barrier with its fragments in registers) and the epilogue has its own slice of LDS
@@ -728,12 +702,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): edge tiles / fp32 outputs issue an unknown number of stores, drained here (pend stays false)
   }   // !TAIL
   }   // tile loop
-#ifdef FLEXAM_GEMM_STAMPS
-  if constexpr (!TAIL) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // the epilogue's stores have left
-    GEMM_STAMP(3);
-  }
-#endif
 }
 
 // Second half of the tail split-K: one workgroup per (tail tile, row tile t).  Thread `te` owns the same 16-byte elements the
@@ -843,10 +811,9 @@ int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff,
   p.split_full = split_s > 1 ? tiles - rem : tiles;
   p.units = p.split_full + (split_s > 1 ? rem * split_s : 0);
   p.ws = g_ws.slabs;
-  static const int persist = [] { const char* e = getenv("FLEXAM_GEMM_PERSIST"); return e ? atoi(e) : 1; }();
   auto grid_for_units = [&](int nwg) {
     int grid = (nwg + 7) / 8 * 8;                        // a multiple of 8 so that blockIdx & 7 is the XCD
-    if (persist && grid > num_cus()) grid = num_cus();   // one persistent workgroup per CU (156 of its 160 KiB of LDS)
+    if (grid > num_cus()) grid = num_cus();              // one persistent workgroup per CU (156 of its 160 KiB of LDS)
     return grid;
   };
   if (p.split_full > 0) hipLaunchKernelGGL(kern, dim3(grid_for_units(p.split_full)), dim3(512), smem, s, p, a_koff);
@@ -911,21 +878,13 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
     // tiles' X footprint matters more than panel sharing with a long K -- one tile-row across all columns (whole 12 KiB rows of X):
     // 3 % faster than 4 at K = 14336.  With a short K (o-proj) r3 measured a tall group of 16 ahead; with the r5 epilogue (two
     // batches of X in flight) 4 ... 12 are level and 16 is 0.6 % behind (profiles/r5zb_gemm_gm_sweep.txt): 4 like the plain stores.
-    const char* g = getenv("FLEXAM_GEMM_GM");
-    p.gm = g ? atoi(g) : (EPI == EPI_GATE_RESIDUAL && a_koff == nullptr && p.K >= 8192 ? 1 : 4);
-    if (p.gm < 1) p.gm = 4;
+    p.gm = EPI == EPI_GATE_RESIDUAL && a_koff == nullptr && p.K >= 8192 ? 1 : 4;
   }
   if constexpr (EPI == EPI_GATE_RESIDUAL) {
     // X (fp32 residual stream) with non-temporal hints only when it cannot stay in the 256 MB Infinity Cache anyway (the single-GPU CFG pair:
     // 286 MB, -0.8 % of a step with the hints, r4as); a sequence-parallel rank's 36-72 MB is touched six times per block and should stay cached.
-    // FLEXAM_GEMM_X_NT=0 / 1 forces (A/B).
-    const char* e = getenv("FLEXAM_GEMM_X_NT");
-    p.x_nt = e ? atoi(e) : ((int64_t)p.M * p.N * 4 > (int64_t)160 << 20);
+    p.x_nt = (int64_t)p.M * p.N * 4 > (int64_t)160 << 20;
   }
-#ifdef FLEXAM_GEMM_ABLATE
-  const char* dbg = getenv("FLEXAM_GEMM_DEBUG");
-  p.debug = dbg ? atoi(dbg) : 0;
-#endif
   // output widths that are multiples of 160 but not of 256 (VAE encoder: 160, 320 channels): the 256 x 160 shape wastes nothing,
   // a 256-wide tile 37.5 %; FLEXAM_GEMM_N160=0 keeps the 256-wide shape (A/B), =2 also takes N = 640 (83 % of 256-wide tiles)
   {
@@ -935,11 +894,10 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
     const bool mult160 = p.N % 160 == 0 && p.N % 256 != 0 && (p.N <= 480 || mode == 2);
     if (mode && (narrow || mult160)) {
       // 384-row tiles where the rows fill many rounds of the CUs (the encoder's 160-channel convolutions: millions of rows): a third
-      // more MFMAs per fragment read and per staged byte; FLEXAM_GEMM_N160_TALL=0 keeps 256 rows (A/B)
-      static const int tall = [] { const char* t = getenv("FLEXAM_GEMM_N160_TALL"); return t ? atoi(t) : 1; }();
+      // more MFMAs per fragment read and per staged byte
       const long tiles_tall = (long)((p.M + 383) / 384) * ((p.N + 159) / 160);
       // (the read-modify-write epilogue next to 120 accumulators spills: that instance runs 320-row tiles, 100 accumulators)
-      if (tall && tiles_tall >= 4L * num_cus()) return launch_shape<EPI, OutT, EPI == EPI_GATE_RESIDUAL ? 5 : 6, 4, 5>(p, g_ws, a_koff, s);
+      if (tiles_tall >= 4L * num_cus()) return launch_shape<EPI, OutT, EPI == EPI_GATE_RESIDUAL ? 5 : 6, 4, 5>(p, g_ws, a_koff, s);
       return launch_shape<EPI, OutT, 4, 4, 5>(p, g_ws, a_koff, s);
     }
   }
@@ -980,13 +938,6 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
 }
 
 }  // namespace
-
-#ifdef FLEXAM_GEMM_STAMPS
-// diagnostic builds only (not declared in flexam_hip.h): the per-workgroup stamps of the last whole-tile GEMM launch
-extern "C" int flexam_debug_gemm_stamps(unsigned long long* out, int n_workgroups) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gemm_stamps), (size_t)n_workgroups * 32) == hipSuccess ? 0 : -1;
-}
-#endif
 
 extern "C" int flexam_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
                                 int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue, int out_f32,

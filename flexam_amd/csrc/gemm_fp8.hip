@@ -536,10 +536,7 @@ int launch_shape8(Gemm8Params p, hipStream_t s) {
 
 template <int EPI>
 int launch8(Gemm8Params p, hipStream_t s) {
-  {
-    const char* g = getenv("FLEXAM_GEMM_GM");
-    p.gm = g && atoi(g) >= 1 ? atoi(g) : 4;
-  }
+  p.gm = 4;
   switch (pick_mt8(p.M, p.tiles_n)) {
     case 6: return launch_shape8<EPI, 6>(p, s);
     case 5: return launch_shape8<EPI, 5>(p, s);

@@ -47,10 +47,7 @@ inline dim3 row_grid(int T, int H, int per_row) {
 // 16-byte (fp32) / 8-byte (bf16) access and kept in registers between the sum of squares and the write (8-byte bf16x4 stores);
 // the scalar form below remains for odd channel counts.  (r1's scalar form read every row twice with 2- / 4-byte accesses and
 // ran at ~2.5 TB/s: profiles/r2b_vae_notes.txt.)
-#ifndef FLEXAM_PREP_PIX1                                // diagnostic builds (tools/ab_prep_pix.py) override the positions per wave in flight
-#define FLEXAM_PREP_PIX1 4
-#define FLEXAM_PREP_PIX2 1
-#endif
+constexpr int PREP_PIX1 = 4, PREP_PIX2 = 1;      // positions per wave in flight with one / two 256-channel slabs (more slabs: 1)
 template <typename TI, int NSLAB>
 __global__ __launch_bounds__(256) void vae_prep_vec_kernel(const TI* __restrict__ src, int64_t lds_, int C, int T, int H, int W,
                                                            const float* __restrict__ gamma, int mode, bf16* __restrict__ dst, int Cp,
@@ -58,7 +55,7 @@ __global__ __launch_bounds__(256) void vae_prep_vec_kernel(const TI* __restrict_
   // PIX positions per wave and iteration, their loads issued together: with <= 256 channels a position is one 0.5-1 KB access per
   // wave, too little in flight to cover the HBM latency (counters: 2.7 / 3.8 TB/s at 256 channels against 5.3 at 512)
   // r5 A/B at the VAE's shapes (profiles/r5i_vae_prep_positions_in_flight.txt): 8 / 4 positions are 20-40 % SLOWER than 4 / 2, 512 channels best at 1
-  constexpr int PIX = NSLAB == 1 ? FLEXAM_PREP_PIX1 : NSLAB == 2 ? FLEXAM_PREP_PIX2 : 1;
+  constexpr int PIX = NSLAB == 1 ? PREP_PIX1 : NSLAB == 2 ? PREP_PIX2 : 1;
   const int lane = threadIdx.x & 63;
   const int Hp = H + 2, Wp = W + 2;
   // One image row (t, h) per blockIdx.y, 4 waves x PIX positions of it per blockIdx.x: no per-position division.  (r1-r4 walked a flat
@@ -563,13 +560,13 @@ extern "C" int flexam_vae_prep_cl(const void* src, int src_is_bf16, int64_t ld_s
                    (!gamma || (uintptr_t)gamma % 16 == 0);
   // vector form: one image row per blockIdx.y, 4 waves x PIX positions per blockIdx.x (PIX as in the kernel)
 #define PREP_VEC(TI_, NS_)                                                                                                         \
-  hipLaunchKernelGGL((vae_prep_vec_kernel<TI_, NS_>), rows_dim(prep_grid_x(W, (NS_) == 1 ? FLEXAM_PREP_PIX1 : (NS_) == 2 ? FLEXAM_PREP_PIX2 : 1), T, H), \
+  hipLaunchKernelGGL((vae_prep_vec_kernel<TI_, NS_>), rows_dim(prep_grid_x(W, (NS_) == 1 ? PREP_PIX1 : (NS_) == 2 ? PREP_PIX2 : 1), T, H), \
                      block, 0, st, (const TI_*)src, ld_src, C, T, H, W, gamma, mode, (bf16*)dst, Cp, t0, dst_compact)
   // bf16 rows of <= 256 channels: the span form (16-byte vectors on a contiguous stretch of the row, every lane busy).  Measured r5s at
   // the VAE's shapes: 160 channels bf16 91.5 against 123.7 us, 256 channels 130 against 133; on fp32 rows it LOSES (135 against 117,
   // 218 against 141: twice the registers per thread for the same bytes), so those keep the wave-per-position form.
   const bool span = vec && src_is_bf16 && C <= 256 && C % 8 == 0 && ld_src % 8 == 0 && Cp % 8 == 0 && (uintptr_t)dst % 16 == 0 &&
-                    ((uintptr_t)gamma % 16 == 0) && !getenv("FLEXAM_VAE_PREP_WAVE");
+                    ((uintptr_t)gamma % 16 == 0);
   if (span) {
     hipLaunchKernelGGL(vae_prep_span_kernel<bf16>, rows_dim((W + PREP_SPAN - 1) / PREP_SPAN, T, H), block, 0, st, (const bf16*)src, ld_src, C, T, H, W,
                        gamma, mode, (bf16*)dst, Cp, t0, dst_compact);

@@ -114,7 +114,7 @@ class DiTEngine:
         # AdaLN tables of all layers are built in one launch per step ([layers, R, 6, C] fp32, R = distinct timesteps x batch);
         # beyond this many bytes (masks with fractional edges: hundreds of distinct timesteps) ONE [R, 6, C] table is rebuilt
         # per layer instead -- the reference's own footprint is [B, L, 6, C] per step (wan_transformer3d_FlexAM.py:944)
-        self.table_limit = int(os.environ.get("FLEXAM_ADALN_TABLE_BYTES", str(1 << 30)))
+        self.table_limit = 1 << 30
         self.fp8 = False                            # BASELINE configs[4]: QKV / FFN GEMMs on fp8 MFMA (enable_fp8)
         self._fp8_w = None
         self.fp8_modules = False                    # fp8 GEMMs inside blocks that are called as modules (not the fused path): enable_fp8

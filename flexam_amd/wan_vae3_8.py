@@ -181,9 +181,8 @@ class _Conv:
         # image keeps `ci` channels per pixel (rounded to 8: 16-byte pixels) instead of padding each pixel to 64, and the kw taps of one
         # image row -- kw * cp CONTIGUOUS elements starting at pixel w - 1 -- are one K run, padded to 64 as a whole (3 * 160 = 480 ->
         # 512 instead of 3 * 192 = 576; 3 * 16 = 48 -> 64 instead of 192).  The run's last K block reads a few channels of pixel w + 2:
-        # finite activations against zero weights.  FLEXAM_VAE_RUNPACK=0 restores per-pixel padding (A/B only).
-        self.run_pack = kw == 3 and ci % 64 != 0 and os.environ.get("FLEXAM_VAE_RUNPACK", "1") != "0"
-        self.k_rowmajor = os.environ.get("FLEXAM_VAE_KORDER", "row") != "tap"
+        # finite activations against zero weights.
+        self.run_pack = kw == 3 and ci % 64 != 0
         if self.run_pack:
             self.cp = _round_up(ci, 8)
             self.krun = _round_up(kw * self.cp, 64)
@@ -200,9 +199,8 @@ class _Conv:
             # the same 64-channel slice of rows shifted by ONE position -- the second and third hit the L2 lines the first just
             # brought in.  (With the tap-major order (dt, dh, dw, channel block) a shifted re-read comes cp/64 K blocks later, after
             # the XCD's 32 workgroups have pulled 32 x cp/64 x 32 KiB through its 4 MiB L2: the 3x3x3 convs at 256 x 448 then fetch
-            # every activation ~9 times over the fabric.)  FLEXAM_VAE_KORDER=tap restores the tap-major order (A/B only).
-            if self.k_rowmajor:
-                wp = wp.view(co, kt, kh, kw, self.cp // 64, 64).permute(0, 1, 2, 4, 3, 5)
+            # every activation ~9 times over the fabric.)
+            wp = wp.view(co, kt, kh, kw, self.cp // 64, 64).permute(0, 1, 2, 4, 3, 5)
             self.weight = wp.reshape(co, kt * kh * kw * self.cp).to(BF16).contiguous()
         self.bias = bias.detach().to(device, F32).contiguous()
         self.hist = kt - 1
@@ -232,10 +230,8 @@ class _Conv:
                 for dh in range(self.kh):
                     if self.run_pack:
                         offs += [tap(dt, dh, 0) + 64 * blk for blk in range(self.krun // 64)]
-                    elif self.k_rowmajor:
-                        offs += [tap(dt, dh, dw) + cb * 64 for cb in range(self.cp // 64) for dw in range(self.kw)]
                     else:
-                        offs += [tap(dt, dh, dw) + cb * 64 for dw in range(self.kw) for cb in range(self.cp // 64)]
+                        offs += [tap(dt, dh, dw) + cb * 64 for cb in range(self.cp // 64) for dw in range(self.kw)]
             self._koff = torch.tensor(offs, dtype=I64, device=self.device)
             self.shape = (h, w)
             self.img = self.all[:self.hist + self.t_cap]
@@ -295,7 +291,7 @@ class _ConvFold(_Conv):
         co, ci, kt, kh, kw = w.shape
         assert (kh, kw) == (3, 3)
         self.co, self.ci, self.kt, self.kh, self.kw = co, ci, kt, kh, kw
-        self.run_pack, self.k_rowmajor = False, True
+        self.run_pack = False
         self.cp = _round_up(ci, 64)
         wf = torch.zeros(kt * 9 * co, self.cp, device=device, dtype=F32)
         wf[:, :ci] = w.permute(2, 3, 4, 0, 1).reshape(kt * 9 * co, ci)              # row (dt*9 + dh*3 + dw) * co + o
@@ -328,9 +324,7 @@ class _ConvS2D:
         self.co, self.ci, self.cs = co, ci, _round_up(ci, 64)
         wp = torch.zeros(co, 3, 3, self.cs, device=device, dtype=F32)
         wp[..., :ci] = w.permute(0, 2, 3, 1)
-        self.k_rowmajor = os.environ.get("FLEXAM_VAE_KORDER", "row") != "tap"      # see _Conv: (dh, channel block, dw, 64)
-        if self.k_rowmajor:
-            wp = wp.view(co, 3, 3, self.cs // 64, 64).permute(0, 1, 3, 2, 4)
+        wp = wp.view(co, 3, 3, self.cs // 64, 64).permute(0, 1, 3, 2, 4)      # K order as in _Conv: (dh, channel block, dw, 64)
         self.weight = wp.reshape(co, 9 * self.cs).to(BF16).contiguous()
         self.bias = bias.detach().to(device, F32).contiguous()
         self.t_cap, self.device, self.shape = t_cap, device, None
@@ -345,10 +339,7 @@ class _ConvS2D:
             offs = []
             tap = lambda dh, dw: (((dh >> 1) * wp + (dw >> 1)) * 4 + (dh & 1) * 2 + (dw & 1)) * self.cs
             for dh in range(3):
-                if self.k_rowmajor:
-                    offs += [tap(dh, dw) + cb * 64 for cb in range(self.cs // 64) for dw in range(3)]
-                else:
-                    offs += [tap(dh, dw) + cb * 64 for dw in range(3) for cb in range(self.cs // 64)]
+                offs += [tap(dh, dw) + cb * 64 for cb in range(self.cs // 64) for dw in range(3)]
             self._koff = torch.tensor(offs, dtype=I64, device=self.device)
             self.shape = (h2, w2)
         return self.img

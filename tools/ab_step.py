@@ -1,6 +1,6 @@
 """Dev tool: IN-STEP same-process A/B.  Builds bench.py's pipeline once (97x512x896, 30 layers, CFG pair) and alternates groups of
 denoise steps between arms; an arm is VAR=value (an environment switch the library reads per call) or lib=NAME
-(tools/probes/libflexam_var_NAME.so, `tree` = the in-tree library; the kernels are stateless, so the library can be swapped between
+(tools/probes/libflexam_var_NAME.so, a build from another checkout copied there; `tree` = the in-tree library; the kernels are stateless, so the library can be swapped between
 steps).  usage: ab_step.py ARM ARM ... [--steps=3] [--rounds=5] [--fp8=1] [--logit=6]; prints the median ms per step of every arm."""
 import os, sys, time, statistics
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,5 +1,5 @@
 """Dev tool: same-process A/B of the full-size VAE encode ([1,3,97,512,896]) and decode ([1,48,25,32,56]) between the tree's library and
-tools/probes/libflexam_var_NAME.so (usage: ab_vae_variants.py NAME); medians over 3 runs per arm, and the largest output difference."""
+tools/probes/libflexam_var_NAME.so (a build from another checkout copied there; usage: ab_vae_variants.py NAME); medians over 3 runs per arm, and the largest output difference."""
 import os, sys, time, statistics
 sys.path.insert(0, "/root/repo")
 import torch

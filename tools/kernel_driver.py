@@ -5,7 +5,7 @@ import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from flexam_amd import hip as H
-if os.environ.get("FLEXAM_DRIVER_LIB"):          # a diagnostic build of the library (tools/build_attn_variants.py) instead of the tree's
+if os.environ.get("FLEXAM_DRIVER_LIB"):          # another build of the library instead of the tree's
     H.load_library(os.environ["FLEXAM_DRIVER_LIB"])
 
 dev = torch.device("cuda:0"); BF = torch.bfloat16
