@@ -24,6 +24,12 @@
 //  * workgroup -> tile map is XCD-aware: the 8 XCDs (private 4 MiB L2 each) get contiguous
 //    chunks of the tile list, walked in groups of 4 tile-rows so concurrently resident tiles
 //    share A row-panels and W column-panels in L2.
+//  * W8 instances (flexam_gemm_w8*): W holds OCP e4m3 bytes -- the reference's qfloat8 weight storage
+//    (FlexAM/utils/fp8_optimization.py) -- and stays e4m3 in HBM and LDS (64-byte tile rows, 16-byte chunk
+//    index XOR (row>>2)&3: the ds_read_b64 fragment reads are conflict-free per tools/lds_sim.py).  A fragment
+//    of 8 e4m3 values is widened to bf16 in registers (exact) once per K half and reused by the wave's MT
+//    m-tiles; launch plan, MFMA order and epilogues are the bf16 instances', so the result is bit-identical
+//    to flexam_gemm_bf16 on the upcast weights.
 #include <math.h>
 #include <stdlib.h>
 
@@ -39,7 +45,7 @@ constexpr int TILE_BYTES = 256 * BK * 2;   // 32 KiB per operand tile (A: up to 
 
 struct GemmParams {
   const bf16* A;
-  const bf16* W;
+  const void* W;           // bf16, or e4m3 bytes (W8 instances); ldw in elements of W
   void* C;
   const float* bias;
   int64_t lda, ldw, ldc;
@@ -66,6 +72,22 @@ using IC = std::integral_constant<int, V>;
 
 enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GATE_RESIDUAL = 2 };
 
+// 8 OCP e4m3 values (byte j = element j) -> the 8 bf16 of an MFMA operand fragment; exact (every e4m3 value, subnormals and -0
+// included, is a bf16 value; the NaN codes 0x7F / 0xFF come out as NaN)
+__device__ __forceinline__ bf16x8 widen_e4m3(u32x2 r) {
+  const bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r.x, 1.0f, false), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r.x, 1.0f, true);
+  const bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r.y, 1.0f, false), d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(r.y, 1.0f, true);
+  return (bf16x8){a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+// fragment registers of one 32-deep K half: W n-tiles then A m-tiles (bf16: one array of NF); the W8 instances keep the W
+// fragments as the 8 raw e4m3 bytes until the MFMA group that first needs them
+template <int NTW, int MT>
+struct W8Frags {
+  u32x2 w[NTW];
+  bf16x8 a[MT];
+};
+
 // MT = 16-row m-tiles per wave: the workgroup tile is (32*MT) x 256 outputs, 8 waves = 2(M) x 4(N), two per SIMD.
 // MT = 8 (256 x 256) is the throughput shape; 7..4 exist so that a launch whose tile count is a little over a
 // multiple of the 256 CUs (N = 3072 projections: 91 x 12 tiles = 4.27 rounds) can trade tile height for a
@@ -88,10 +110,11 @@ enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GATE_RESIDUAL = 2 };
 // waves x 5 n-tiles = a (64 MT) x 160 tile for output widths that are multiples of 160 but not of 256 (the VAE encoder's 160 / 320 /
 // 640 channels, which fill 62.5 % / 62.5 % / 83 % of 256-wide tiles).  The 160-wide shape stores through the generic epilogue (its
 // 80-column wave rows do not fit the 128-byte LDS turn-around).
-template <int EPI, typename OutT, int MT, bool TAIL = false, int WMW = 2, int NTW = 4>
+template <int EPI, typename OutT, int MT, bool TAIL = false, int WMW = 2, int NTW = 4, bool W8 = false>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const int64_t* __restrict__ a_koff) {
   static_assert((WMW == 2 && (NTW == 4 || NTW == 3)) || (WMW == 4 && NTW == 5 && MT <= 6),
                 "supported wave layouts: 2 x 4 waves x 4 or 3 n-tiles, 4 x 2 waves x 5 n-tiles");
+  static_assert(!W8 || WMW == 2, "e4m3 W: the 256- and 192-wide tiles of the DiT shapes only");
   // STD: the LDS-staged epilogues (a wave's row of 16 NTW bf16 outputs turned around through a 128-byte LDS row).  NTW = 4: the 256-wide
   // tile of the DiT shapes.  NTW = 3 (r6): a 192-wide tile, (32 MT) x 192 -- with MT = 6 a 192 x 192 tile, 16 x 16 = 256 of which cover
   // a rank-of-eight's 2912 x 3072 outputs in ONE full round of the CUs (94.8 % useful) where 160 x 256 tiles are 228 tiles at 89 % fill:
@@ -111,7 +134,8 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   constexpr int STG_WAVE = RT * 128;        // epilogue staging per wave: one row tile of bf16 outputs (RT rows x 64 columns)
   constexpr int BM_ = WMW * 16 * MT;        // rows of this tile shape
   constexpr int PA = (BM_ + 63) / 64;       // 64-row staging pieces per thread for A
-  constexpr int PW = (BN_ + 63) / 64;       // ... and for W
+  constexpr int PW = W8 ? (BN_ + 127) / 128 : (BN_ + 63) / 64;   // ... and for W (e4m3: 128 rows of 64 bytes per piece)
+  constexpr int WB = W8 ? 1 : 2;            // bytes per W element
   constexpr int NP = PA + PW;               // LDS-DMA pieces per thread per K block
   // LDS image of one K block: [A tile | W tile].  Tiles of up to 256 rows keep the 32 KiB + 32 KiB form; the 384 x 160 shape (r6: 4 x 2
   // waves of 96 x 80 outputs, 30 MFMAs per 11 fragment reads instead of 20 per 9 on the 256 x 160 tile -- the VAE encoder's 160-channel
@@ -172,10 +196,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
       const int row = i * 64 + (ts >> 3);
       const int chunk = (ts & 7) ^ ((row >> 1) & 7);
       if (i < PA) a_off[i] = (uint32_t)(((int64_t)min(row, p.M - 1 - m0) * p.lda + chunk * 8) * 2);   // edge tiles re-read their last row
-      if (i < PW) w_off[i] = (uint32_t)(((int64_t)min(row, p.N - 1 - n0) * p.ldw + chunk * 8) * 2);
+      if constexpr (W8) {
+        // 64-byte rows: thread -> (row = i*128 + tid/4, LDS slot = tid%4), source chunk = slot ^ ((row>>2)&3); the rows a 192-wide
+        // tile does not have re-read its last one (no HBM traffic, the LDS rows are never read)
+        const int wr = i * 128 + (ts >> 2);
+        if (i < PW) w_off[i] = (uint32_t)((int64_t)min(min(wr, BN_ - 1), p.N - 1 - n0) * p.ldw + (((ts & 3) ^ ((wr >> 2) & 3)) << 4));
+      } else {
+        if (i < PW) w_off[i] = (uint32_t)(((int64_t)min(row, p.N - 1 - n0) * p.ldw + chunk * 8) * 2);
+      }
     }
     a_tile = (const char*)(p.A + (int64_t)m0 * p.lda);
-    w_tile = (const char*)(p.W + (int64_t)n0 * p.ldw);
+    w_tile = W8 ? (const char*)p.W + (int64_t)n0 * p.ldw : (const char*)((const bf16*)p.W + (int64_t)n0 * p.ldw);
   };
 
   // ---- fragment read offsets (bytes inside a tile): row = base16 + (lane&15), chunk = (lane>>4) + 4*ks
@@ -183,12 +214,19 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   // Rebuilt at the top of every unit from a fresh lane id: alive in the K loop only, not across the epilogue (where they were
   // spilled and came back behind a vmcnt(0) that drained the epilogue's stores in front of the next K loop).
   int frag_off[2];
+  int wfrag_off[W8 ? 2 : 1];
   auto frag_setup = [&]() {
     const int lf = fresh_lane();
     const int sw = ((lf & (RT - 1)) >> 1) & 7;
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
       frag_off[ks] = (lf & (RT - 1)) * 128 + (((4 * ks + (lf >> 4)) ^ sw) << 4);
+    if constexpr (W8) {
+      // e4m3 W: the same K values (8 (lane>>4) + 32 ks ..+7) are 8 bytes: half (lane>>4)&1 of 16-byte chunk 2 ks + (lane>>5) of a 64-byte row
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks)
+        wfrag_off[ks] = (lf & (RT - 1)) * 64 + (((2 * ks + (lf >> 5)) ^ (((lf & (RT - 1)) >> 2) & 3)) << 4) + ((lf >> 4) & 1) * 8;
+    }
   };
   // ---- bias of the wave's 64 columns through LDS (standard tile shape).  A plain bias load at the top of the epilogue sits BEHIND
   // the next unit's 16 prefetched LDS-DMA pieces in the wave's in-order vmcnt queue: the first use of the bias waited for all of
@@ -273,7 +311,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   // Inline asm: the scalar-base form (uniform 64-bit base + one 32-bit VGPR offset) keeps the per-thread
   // offsets in PA + 4 VGPRs; completion is tracked by hand (s_waitcnt vmcnt(0) in front of each barrier).
   auto dma = [&](int i, int64_t ka, int64_t kw, char* buf) {
-    const char* sbase = i < PA ? a_tile + ka * 2 : w_tile + kw * 2;
+    const char* sbase = i < PA ? a_tile + ka * 2 : w_tile + kw * WB;
     const uint32_t voff = i < PA ? a_off[i] : w_off[i - PA];
     const uint32_t dst = (uint32_t)(uintptr_t)LDS_PTR(buf) + (i < PA ? i * 8192 : A_BYTES + (i - PA) * 8192) + wave * 1024;
     // M0 (the LDS base of the DMA) is written and NOT restored: nothing else in this kernel uses it (gfx9+ LDS instructions do not;
@@ -291,18 +329,40 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     return j < NTW ? *(const bf16x8*)(buf + A_BYTES + wn * (16 * NTW * 128) + j * 2048 + fo)
                    : *(const bf16x8*)(buf + wm * (16 * MT * 128) + (j - NTW) * 2048 + fo);
   };
+  // W8: the 8 e4m3 bytes of W n-tile j (< NTW), ds_read_b64
+  auto frag_w8 = [&](const char* buf, int hf, int j) -> u32x2 {
+    return *(const u32x2*)(buf + A_BYTES + wn * (16 * NTW * 64) + j * 1024 + wfrag_off[hf & (W8 ? 1 : 0)]);
+  };
+  using FSet = std::conditional_t<W8, W8Frags<NTW, MT>, bf16x8[NF]>;
   // fragments 2g, 2g+1 of a set
   // (PER fragments per MFMA group so that the MT groups of a phase cover all NF: 2 for every 256-wide shape, 3 for the 160-wide one)
   constexpr int PER = (NF + MT - 1) / MT > 2 ? (NF + MT - 1) / MT : 2;
-  auto ld2 = [&](const char* buf, int hf, int g, bf16x8 (&f)[NF]) {
+  auto ld2 = [&](const char* buf, int hf, int g, FSet& f) {
 #pragma unroll
-    for (int j = PER * g; j < PER * g + PER; ++j)
-      if (j < NF) f[j] = frag(buf, hf, j);
+    for (int j = PER * g; j < PER * g + PER; ++j) {
+      if constexpr (W8) {
+        if (j < NTW) f.w[j] = frag_w8(buf, hf, j);
+        else if (j < NF) f.a[j - NTW] = frag(buf, hf, j);
+      } else {
+        if (j < NF) f[j] = frag(buf, hf, j);
+      }
+    }
   };
   // MFMA group g (of MT per K half, 64 matrix-pipe cycles each) on fragment set f
-  auto mfma_group = [&](int g, const bf16x8 (&f)[NF]) {
+  // (W8: group 0 of a phase widens the set's NTW W fragments; groups 1 .. MT-1 reuse them)
+  [[maybe_unused]] bf16x8 wide[W8 ? NTW : 1];
+  auto mfma_group = [&](int g, const FSet& f) {
+    if constexpr (W8) {
+      if (g == 0) {
 #pragma unroll
-    for (int nt = 0; nt < NTW; ++nt) acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[nt], f[NTW + g], acc[g][nt], 0, 0, 0);
+        for (int nt = 0; nt < NTW; ++nt) wide[nt] = widen_e4m3(f.w[nt]);
+      }
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt) acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wide[nt], f.a[g], acc[g][nt], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int nt = 0; nt < NTW; ++nt) acc[g][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(f[nt], f[NTW + g], acc[g][nt], 0, 0, 0);
+    }
   };
 
   // ---- main loop: two LDS buffers, two fragment sets (F0: k 0..31, F1: k 32..63 of a K block).  Per K block:
@@ -311,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   //   phase B: LDS-DMA of tile kb+2 into `cur`; MFMAs on F1 while F0 of block kb+1 is read from `nxt`
   // so no wave crosses the barrier without MFMA work already in registers, and the DMA pieces and fragment
   // reads of a phase are spread one group (4 MFMAs) apart instead of stalling the wave up front.
-  bf16x8 f0[NF], f1[NF];
+  FSet f0, f1;
   if (!staged) {
     bias_dma(n0, it & 1);
     grow_dma(m0, it & 1);
@@ -788,9 +848,9 @@ void plan_split(const GemmWorkspace& g_ws, int tiles, int nk, int& S, int& rem, 
   if (cost) *cost = best;
 }
 
-template <int EPI, typename OutT, int MT, int WMW = 2, int NTW = 4>
+template <int EPI, typename OutT, int MT, int WMW = 2, int NTW = 4, bool W8 = false>
 int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff, hipStream_t s) {
-  auto kern = gemm_bf16_kernel<EPI, OutT, MT, false, WMW, NTW>;
+  auto kern = gemm_bf16_kernel<EPI, OutT, MT, false, WMW, NTW, W8>;
   static bool attr_set[FLEXAM_MAX_DEVICES] = {};          // per device: the attribute belongs to the device's copy of the code object
   // two K-block buffers (128 KiB) + one row tile of bf16 outputs per wave + two bias slots + two gate-row slots per wave; the tall
   // 160-wide shape: two buffers of [384 rows of A | 3 pieces of W] (144 KiB), no staging
@@ -819,7 +879,7 @@ int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff,
   if (p.split_full > 0) hipLaunchKernelGGL(kern, dim3(grid_for_units(p.split_full)), dim3(512), smem, s, p, a_koff);
   if (split_s > 1) {
     // the K slices of the tail tiles, then (stream-ordered) their sum in slice order + the epilogue
-    auto tail = gemm_bf16_kernel<EPI_NONE, float, MT, true, WMW, NTW>;
+    auto tail = gemm_bf16_kernel<EPI_NONE, float, MT, true, WMW, NTW, W8>;
     static bool tail_attr[FLEXAM_MAX_DEVICES] = {};
     if (!tail_attr[dev]) {
       if (hipFuncSetAttribute((const void*)tail, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
@@ -829,12 +889,12 @@ int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff,
     hipLaunchKernelGGL(tail, dim3(grid_for_units(rem * split_s)), dim3(512), smem, s, p, a_koff);
     hipLaunchKernelGGL((gemm_splitk_finish_kernel<EPI, OutT, MT, WMW, NTW>), dim3(rem * MT), dim3(512), 0, s, p);
   }
-  return flexam_check_launch("flexam_gemm_bf16");
+  return flexam_check_launch(W8 ? "flexam_gemm_w8" : "flexam_gemm_bf16");
 }
 
-template <int EPI, typename OutT, int MT>
+template <int EPI, typename OutT, int MT, bool W8 = false>
 int launch_mt(const GemmParams& p, const GemmWorkspace& g_ws, const int64_t* a_koff, hipStream_t s) {
-  return launch_shape<EPI, OutT, MT>(p, g_ws, a_koff, s);
+  return launch_shape<EPI, OutT, MT, 2, 4, W8>(p, g_ws, a_koff, s);
 }
 
 // Tile height: rounds of 256 concurrently resident workgroups x relative cost of one tile (MT m-tiles of MFMA work
@@ -867,7 +927,9 @@ GemmWorkspace make_ws(void* ws, int64_t bytes) {
   return g;
 }
 
-template <int EPI, typename OutT>
+// W8: the e4m3-W instances take exactly the plan the bf16 ones take for the same M, N, K (and FLEXAM_GEMM_* switches); the 160-wide
+// shapes (VAE channel counts) have no e4m3 instance and are refused
+template <int EPI, typename OutT, bool W8 = false>
 int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_koff, hipStream_t s) {
   GemmParams p = p_;
   const GemmWorkspace g_ws = make_ws(ws, ws_bytes);
@@ -897,8 +959,12 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
       // more MFMAs per fragment read and per staged byte
       const long tiles_tall = (long)((p.M + 383) / 384) * ((p.N + 159) / 160);
       // (the read-modify-write epilogue next to 120 accumulators spills: that instance runs 320-row tiles, 100 accumulators)
-      if (tiles_tall >= 4L * num_cus()) return launch_shape<EPI, OutT, EPI == EPI_GATE_RESIDUAL ? 5 : 6, 4, 5>(p, g_ws, a_koff, s);
-      return launch_shape<EPI, OutT, 4, 4, 5>(p, g_ws, a_koff, s);
+      if constexpr (W8) {
+        return flexam_fail(FLEXAM_E_SHAPE, "gemm_w8: N=%d takes the 160-wide tile of the bf16 GEMM, which has no e4m3 form", p.N);
+      } else {
+        if (tiles_tall >= 4L * num_cus()) return launch_shape<EPI, OutT, EPI == EPI_GATE_RESIDUAL ? 5 : 6, 4, 5>(p, g_ws, a_koff, s);
+        return launch_shape<EPI, OutT, 4, 4, 5>(p, g_ws, a_koff, s);
+      }
     }
   }
   // 192 x 192 tiles (MT = 6, 3 n-tiles per wave) where their rounds of the CUs beat the best 256-wide plan: output widths that are
@@ -926,14 +992,14 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
       plan_split(g_ws, tiles192, nk, S, rem, &tail);
       take = (tiles192 / G + tail) * (0.75 * 6 + 1.1) < 0.95 * best256;
     }
-    if (take) return launch_shape<EPI, OutT, 6, 2, 3>(p, g_ws, a_koff, s);
+    if (take) return launch_shape<EPI, OutT, 6, 2, 3, W8>(p, g_ws, a_koff, s);
   }
   switch (pick_mt(g_ws, p.M, p.tiles_n, p.K / BK)) {
-    case 7: return launch_mt<EPI, OutT, 7>(p, g_ws, a_koff, s);
-    case 6: return launch_mt<EPI, OutT, 6>(p, g_ws, a_koff, s);
-    case 5: return launch_mt<EPI, OutT, 5>(p, g_ws, a_koff, s);
-    case 4: return launch_mt<EPI, OutT, 4>(p, g_ws, a_koff, s);
-    default: return launch_mt<EPI, OutT, 8>(p, g_ws, a_koff, s);
+    case 7: return launch_mt<EPI, OutT, 7, W8>(p, g_ws, a_koff, s);
+    case 6: return launch_mt<EPI, OutT, 6, W8>(p, g_ws, a_koff, s);
+    case 5: return launch_mt<EPI, OutT, 5, W8>(p, g_ws, a_koff, s);
+    case 4: return launch_mt<EPI, OutT, 4, W8>(p, g_ws, a_koff, s);
+    default: return launch_mt<EPI, OutT, 8, W8>(p, g_ws, a_koff, s);
   }
 }
 
@@ -950,7 +1016,7 @@ extern "C" int flexam_gemm_bf16(const void* A, int64_t lda, const void* W, int64
   FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "gemm: pointers must be 16-byte aligned");
   FX_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU, FLEXAM_E_ARG, "gemm: unknown epilogue %d", epilogue);
   GemmParams p{};
-  p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = C; p.bias = bias;
+  p.A = (const bf16*)A; p.W = W; p.C = C; p.bias = bias;
   p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.M = (int)M; p.N = (int)N; p.K = (int)K;
   p.tiles_n = (int)((N + BN - 1) / BN);   // tiles_m depends on the tile height launch() picks
   hipStream_t s = (hipStream_t)stream;
@@ -971,11 +1037,52 @@ extern "C" int flexam_gemm_bf16_gate_residual(const void* A, int64_t lda, const 
   FX_REQUIRE(lda % 8 == 0 && ldw % 8 == 0, FLEXAM_E_SHAPE, "gemm_gate_residual: lda/ldw must be multiples of 8");
   FX_REQUIRE(!gate || gate_row || rows_per_batch > 0, FLEXAM_E_ARG, "gemm_gate_residual: gate needs gate_row or rows_per_batch");
   GemmParams p{};
-  p.A = (const bf16*)A; p.W = (const bf16*)W; p.C = nullptr; p.bias = bias;
+  p.A = (const bf16*)A; p.W = W; p.C = nullptr; p.bias = bias;
   p.lda = lda; p.ldw = ldw; p.ldc = 0; p.M = (int)M; p.N = (int)N; p.K = (int)K;
   p.tiles_n = (int)((N + BN - 1) / BN);   // tiles_m depends on the tile height launch() picks
   p.X = X; p.ldx = ldx; p.gate = gate; p.gate_ld = gate_ld; p.gate_row = gate_row;
   p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
   FX_REQUIRE((uintptr_t)ws % 16 == 0, FLEXAM_E_ARG, "gemm_gate_residual: workspace must be 16-byte aligned");
   return launch<EPI_GATE_RESIDUAL, bf16>(p, ws, ws_bytes, a_koff, (hipStream_t)stream);
+}
+
+// e4m3 W (OCP bytes, ldw in bytes): the same problems, plans and epilogues as the bf16 pair above, bit-identical to them on W
+// upcast to bf16.  Every shape of the DiT blocks; output widths that would take the bf16 GEMM's 160-wide tile are refused.
+extern "C" int flexam_gemm_w8(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
+                              int64_t M, int64_t N, int64_t K, int epilogue, int out_f32, const int64_t* a_koff, void* ws,
+                              int64_t ws_bytes, void* stream) {
+  FX_REQUIRE(A && W && C, FLEXAM_E_ARG, "gemm_w8: null pointer");
+  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "gemm_w8: empty problem M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+  FX_REQUIRE(K % BK == 0, FLEXAM_E_SHAPE, "gemm_w8: K=%ld must be a multiple of %d (pad on the host)", (long)K, BK);
+  FX_REQUIRE(N % 4 == 0 && ldc % 4 == 0, FLEXAM_E_SHAPE, "gemm_w8: N=%ld and ldc=%ld must be multiples of 4", (long)N, (long)ldc);
+  FX_REQUIRE(lda % 8 == 0 && ldw % 16 == 0, FLEXAM_E_SHAPE, "gemm_w8: lda (elements) and ldw (bytes) must make 16-byte rows");
+  FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "gemm_w8: pointers must be 16-byte aligned");
+  FX_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU, FLEXAM_E_ARG, "gemm_w8: unknown epilogue %d", epilogue);
+  FX_REQUIRE(!out_f32 || epilogue == EPI_NONE, FLEXAM_E_ARG, "gemm_w8: f32 output supports no activation epilogue");
+  GemmParams p{};
+  p.A = (const bf16*)A; p.W = W; p.C = C; p.bias = bias;
+  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.tiles_n = (int)((N + BN - 1) / BN);
+  hipStream_t s = (hipStream_t)stream;
+  if (out_f32) return launch<EPI_NONE, float, true>(p, ws, ws_bytes, a_koff, s);
+  return epilogue == EPI_GELU ? launch<EPI_GELU, bf16, true>(p, ws, ws_bytes, a_koff, s) : launch<EPI_NONE, bf16, true>(p, ws, ws_bytes, a_koff, s);
+}
+
+extern "C" int flexam_gemm_w8_gate_residual(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* X,
+                                            int64_t ldx, const float* gate, int64_t gate_ld, const int32_t* gate_row,
+                                            int64_t rows_per_batch, int64_t M, int64_t N, int64_t K, const int64_t* a_koff, void* ws,
+                                            int64_t ws_bytes, void* stream) {
+  FX_REQUIRE(A && W && X, FLEXAM_E_ARG, "gemm_w8_gate_residual: null pointer");
+  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "gemm_w8_gate_residual: empty problem");
+  FX_REQUIRE(K % BK == 0 && N % 4 == 0 && ldx % 4 == 0, FLEXAM_E_SHAPE, "gemm_w8_gate_residual: K%%64, N%%4, ldx%%4 required");
+  FX_REQUIRE(lda % 8 == 0 && ldw % 16 == 0, FLEXAM_E_SHAPE, "gemm_w8_gate_residual: lda (elements) and ldw (bytes) must make 16-byte rows");
+  FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)X | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "gemm_w8_gate_residual: pointers must be 16-byte aligned");
+  FX_REQUIRE(!gate || gate_row || rows_per_batch > 0, FLEXAM_E_ARG, "gemm_w8_gate_residual: gate needs gate_row or rows_per_batch");
+  GemmParams p{};
+  p.A = (const bf16*)A; p.W = W; p.C = nullptr; p.bias = bias;
+  p.lda = lda; p.ldw = ldw; p.ldc = 0; p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.tiles_n = (int)((N + BN - 1) / BN);
+  p.X = X; p.ldx = ldx; p.gate = gate; p.gate_ld = gate_ld; p.gate_row = gate_row;
+  p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
+  return launch<EPI_GATE_RESIDUAL, bf16, true>(p, ws, ws_bytes, a_koff, (hipStream_t)stream);
 }

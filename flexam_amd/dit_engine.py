@@ -30,6 +30,7 @@ from . import hip
 from .rope import rope_angle_table, rope_tables
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
+F8 = torch.float8_e4m3fn
 
 
 def _round_up(v: int, m: int) -> int:
@@ -125,7 +126,9 @@ class DiTEngine:
         m, dev, d = self.model, self.device, self.dim
         bf = lambda t: t.detach().to(dev, BF16).contiguous()
         f32 = lambda t: t.detach().to(dev, F32).contiguous()
-        small = lambda t: t.detach().to(dev).contiguous() if t.dtype in (BF16, F32) else f32(t)
+        # (qfloat8 storage, fp8_optimization.py: the e4m3 parameters outside the blocks -- embeddings, head, conv taps, biases and
+        # norm rows -- are upcast here once, exactly; the block GEMM weights stay e4m3 in their packs, _Block.packed)
+        small = lambda t: t.detach().to(dev).contiguous() if t.dtype in (BF16, F32) else (bf(t) if t.dtype == F8 else f32(t))
 
         def pad_k(w2d):
             n, k = w2d.shape
@@ -230,7 +233,8 @@ class DiTEngine:
             for p in self.blocks:
                 q = {}
                 for name in ("wqkv", "cwq", "w1", "w2", "wo", "cwo"):
-                    q[name], q["s_" + name] = hip.quantize_rows_fp8(p[name])
+                    w = p[name]                                        # (qfloat8 storage: one e4m3 matrix upcast at a time)
+                    q[name], q["s_" + name] = hip.quantize_rows_fp8(w.to(BF16) if w.dtype == F8 else w)
                 # bounds for the a-priori scale of FFN1's e4m3 output (flexam_ln_modulate_fp8, next_scale): the largest L2 norm of a
                 # DEQUANTISED w1 row (what the MFMA multiplies) and the largest |bias|; two floats per layer, read back once
                 deq = q["w1"].view(torch.float8_e4m3fn).float() * q["s_w1"][:, None]

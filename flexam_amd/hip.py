@@ -26,6 +26,8 @@ _SIGNATURES = {
     "flexam_set_cu_budget": ([_I], c_int),
     "flexam_gemm_bf16": ([_P, _L, _P, _L, _P, _P, _L, _L, _L, _L, _I, _I, _P, _P, _L, _P], c_int),
     "flexam_gemm_bf16_gate_residual": ([_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P, _L, _P], c_int),
+    "flexam_gemm_w8": ([_P, _L, _P, _L, _P, _P, _L, _L, _L, _L, _I, _I, _P, _P, _L, _P], c_int),
+    "flexam_gemm_w8_gate_residual": ([_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P, _L, _P], c_int),
     "flexam_quantize_rows_fp8": ([_P, _L, _P, _L, _P, _L, _I, _P], c_int),
     "flexam_gemm_fp8": ([_P, _L, _P, _P, _L, _P, _P, _P, _L, _L, _L, _L, _I, _P], c_int),
     "flexam_gemm_fp8_gate_residual": ([_P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P], c_int),
@@ -341,8 +343,11 @@ def _gemm_workspace(device, stream: int):
 
 
 def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, out_dtype=BF16, a_koff=None, m=None, k=None):
-    """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  a, w bf16 2-D views (row stride free).
+    """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  a, w bf16 2-D views (row stride free); a float8_e4m3fn `w` (qfloat8 weight
+    storage) is read as such by gemm_w8.
     With a_koff (int64 [K/64]) `a` is only a base view: rows are `m`, K = `k` (implicit conv)."""
+    if w.dtype == F8:
+        return gemm_w8(a, w, bias, out, epilogue, out_dtype, a_koff, m, k)
     am, ak, lda = _rows(a)
     wn, wk, ldw = _rows(w)
     M = am if m is None else m
@@ -363,7 +368,9 @@ def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, out_dtype=BF16, a_koff=No
 
 def gemm_gate_residual(a, w, bias, x, gate=None, gate_row=None, rows_per_batch=0, a_koff=None):
     """x[M,N] (fp32, in place) += bf16(a @ w^T + bias) * gate[row].  With a_koff `a` is a base view
-    (implicit conv) and M, K come from x and w."""
+    (implicit conv) and M, K come from x and w.  A float8_e4m3fn `w` goes to gemm_w8_gate_residual."""
+    if w.dtype == F8:
+        return gemm_w8_gate_residual(a, w, bias, x, gate, gate_row, rows_per_batch, a_koff)
     am, ak, lda = _rows(a)
     N, K, ldw = _rows(w)
     M, xn, ldx = _rows(x)
@@ -375,6 +382,63 @@ def gemm_gate_residual(a, w, bias, x, gate=None, gate_row=None, rows_per_batch=0
     _check(lib().flexam_gemm_bf16_gate_residual(_ptr(a, BF16), lda, _ptr(w, BF16), ldw, _ptr(bias, F32), _ptr(x, F32), ldx,
                                                 _ptr(gate, F32), gate_ld, _ptr(gate_row, I32), rows_per_batch, M, N, K,
                                                 _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_bf16_gate_residual")
+    return x
+
+
+# ----------------------------------------------------------------------------- e4m3 weights, bf16 activations (qfloat8 modes)
+F8 = torch.float8_e4m3fn
+
+
+def _ptr_w8(w):
+    if w.dtype not in (F8, torch.uint8):
+        raise RuntimeError(f"flexam_amd.hip: expected float8_e4m3fn (or uint8 e4m3 bytes) weights, got {w.dtype}")
+    return _ptr(w)
+
+
+def gemm_w8_takes(n: int) -> bool:
+    """Whether flexam_gemm_w8* has a plan for output width `n`: every width except those the bf16 GEMM runs on its 160-wide tile
+    (csrc/gemm.hip launch(): N <= 160, and multiples of 160 that are not of 256 up to 480 -- all of them with FLEXAM_GEMM_N160=2;
+    none with FLEXAM_GEMM_N160=0), which has no e4m3 form."""
+    mode = int(os.environ.get("FLEXAM_GEMM_N160", "1") or 0)
+    narrow = n <= 160
+    mult160 = n % 160 == 0 and n % 256 != 0 and (n <= 480 or mode == 2)
+    return not (mode and (narrow or mult160))
+
+
+def gemm_w8(a, w, bias=None, out=None, epilogue=EPI_NONE, out_dtype=BF16, a_koff=None, m=None, k=None):
+    """gemm() with w [N, K] OCP e4m3 (float8_e4m3fn or uint8 bytes; a row slice of a fused buffer is fine): bit-identical to
+    gemm(a, w.to(bfloat16), ...), without a bf16 copy of w (flexam_gemm_w8)."""
+    am, ak, lda = _rows(a)
+    wn, wk, ldw = _rows(w)
+    M = am if m is None else m
+    K = wk if k is None else k
+    if a_koff is None and ak != K:
+        raise RuntimeError(f"gemm_w8: K mismatch a {ak} vs w {K}")
+    if out is None:
+        out = torch.empty(M, wn, device=a.device, dtype=out_dtype)
+    om, on, ldc = _rows(out)
+    if (om, on) != (M, wn):
+        raise RuntimeError(f"gemm_w8: out shape {tuple(out.shape)} != ({M}, {wn})")
+    st = _stream()
+    ws = _gemm_workspace(a.device, st)
+    _check(lib().flexam_gemm_w8(_ptr(a, BF16), lda, _ptr_w8(w), ldw, _ptr(bias, F32), _ptr(out), ldc, M, wn, K, epilogue,
+                                1 if out.dtype == F32 else 0, _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_w8")
+    return out
+
+
+def gemm_w8_gate_residual(a, w, bias, x, gate=None, gate_row=None, rows_per_batch=0, a_koff=None):
+    """gemm_gate_residual() with w [N, K] OCP e4m3 (flexam_gemm_w8_gate_residual)."""
+    am, ak, lda = _rows(a)
+    N, K, ldw = _rows(w)
+    M, xn, ldx = _rows(x)
+    if (a_koff is None and (ak != K or am != M)) or xn != N:
+        raise RuntimeError("gemm_w8_gate_residual: shape mismatch")
+    gate_ld = gate.stride(0) if gate is not None else 0
+    st = _stream()
+    ws = _gemm_workspace(a.device, st)
+    _check(lib().flexam_gemm_w8_gate_residual(_ptr(a, BF16), lda, _ptr_w8(w), ldw, _ptr(bias, F32), _ptr(x, F32), ldx,
+                                              _ptr(gate, F32), gate_ld, _ptr(gate_row, I32), rows_per_batch, M, N, K,
+                                              _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_w8_gate_residual")
     return x
 
 

@@ -31,6 +31,7 @@ class ModelConfig(dict):
 
 
 BF16 = torch.bfloat16
+F8 = torch.float8_e4m3fn
 _QSCALE_LOG2E = 1.4426950408889634
 
 
@@ -43,13 +44,23 @@ def _on(t: torch.Tensor, dev, dtype) -> torch.Tensor:
     return d.to(dev, dtype).contiguous()
 
 
+def _wmat(t: torch.Tensor, dev) -> torch.Tensor:
+    """A GEMM weight as the kernels read it: float8_e4m3fn parameters (qfloat8 storage, flexam_amd/fp8_optimization.py) stay
+    e4m3 -- hip.gemm reads them as such (flexam_gemm_w8), no bf16 copy is made -- when the e4m3 GEMM has a plan for their width
+    (every DiT block shape; not the narrow widths of e.g. a head, hip.gemm_w8_takes); everything else is bf16 (`_on`)."""
+    from . import hip
+    return _on(t, dev, F8 if t.dtype == F8 and hip.gemm_w8_takes(t.shape[0]) else BF16)
+
+
 def _fuse_rows(params, dev) -> torch.Tensor:
     """Row-wise concatenation of several weight matrices into ONE bf16 buffer (q|k|v, cross k|v) so that a single GEMM
-    produces all of them.  When the parameters already are bf16 on `dev`, they are re-pointed at their row range of the
-    fused buffer: state-dict keys, shapes and values are unchanged, in-place edits write through, and no second copy of
-    the weights exists."""
-    fused = torch.cat([p.detach().to(dev, BF16) for p in params])
-    if all(p.dtype == BF16 and p.device == dev for p in params):
+    produces all of them -- an e4m3 buffer when every one of them is float8_e4m3fn (qfloat8 storage).  When the parameters
+    already are of the buffer's dtype on `dev`, they are re-pointed at their row range of the fused buffer: state-dict keys,
+    shapes and values are unchanged, in-place edits write through, and no second copy of the weights exists."""
+    from . import hip
+    dt = F8 if all(p.dtype == F8 for p in params) and hip.gemm_w8_takes(sum(p.shape[0] for p in params)) else BF16
+    fused = torch.cat([p.detach().to(dev, dt) for p in params])
+    if all(p.dtype == dt and p.device == dev for p in params):
         off = 0
         for p in params:
             p.data = fused[off:off + p.shape[0]]
@@ -80,7 +91,7 @@ class HipLinear(nn.Linear):
                 wp = torch.zeros(w.shape[0], (k + 63) // 64 * 64, device=dev, dtype=BF16)
                 wp[:, :k] = w.to(BF16)
             else:
-                wp = _on(w, dev, BF16)
+                wp = _wmat(w, dev)
             self._pk = (sig, wp, _on(self.bias, dev, F32) if self.bias is not None else None)
         return self._pk[1], self._pk[2]
 
@@ -105,7 +116,8 @@ def _fp8_weight(pk: dict, name: str):
     from . import hip
     key = "_f8_" + name
     if key not in pk:
-        pk[key] = hip.quantize_rows_fp8(pk[name])
+        w = pk[name]
+        pk[key] = hip.quantize_rows_fp8(w.to(BF16) if w.dtype == F8 else w)     # (qfloat8 storage: one matrix upcast at a time)
     return pk[key]
 
 
@@ -176,7 +188,7 @@ class _SelfAttn(_Attn):
             f32 = lambda t: _on(t, dev, F32)
             wqkv = _fuse_rows([self.q.weight, self.k.weight, self.v.weight], dev)
             self._pk = dict(wqkv=wqkv, bqkv=torch.cat([f32(self.q.bias), f32(self.k.bias), f32(self.v.bias)]),
-                            wo=_on(self.o.weight, dev, BF16), bo=f32(self.o.bias),
+                            wo=_wmat(self.o.weight, dev), bo=f32(self.o.bias),
                             nq=f32(self.norm_q.weight) * self._q_scale(), nk=f32(self.norm_k.weight))
             self._pk["sig"] = self._sig()                     # after the re-pointing of q/k/v
         return self._pk
@@ -270,8 +282,8 @@ class _CrossAttn(_Attn):
             dev = self.q.weight.device
             f32 = lambda t: _on(t, dev, F32)
             cwkv = _fuse_rows([self.k.weight, self.v.weight], dev)
-            self._pk = dict(cwq=_on(self.q.weight, dev, BF16), cbq=f32(self.q.bias), cwkv=cwkv,
-                            cbkv=torch.cat([f32(self.k.bias), f32(self.v.bias)]), cwo=_on(self.o.weight, dev, BF16),
+            self._pk = dict(cwq=_wmat(self.q.weight, dev), cbq=f32(self.q.bias), cwkv=cwkv,
+                            cbkv=torch.cat([f32(self.k.bias), f32(self.v.bias)]), cwo=_wmat(self.o.weight, dev),
                             cbo=f32(self.o.bias), cnq=f32(self.norm_q.weight) * self._q_scale(), cnk=f32(self.norm_k.weight))
             self._pk["sig"] = self._sig()
         return self._pk
@@ -359,8 +371,8 @@ class _Block(nn.Module):
             f32 = lambda t: _on(t, dev, F32)
             pk = dict(sa)
             pk.update(ca)
-            pk.update(n3w=f32(self.norm3.weight), n3b=f32(self.norm3.bias), w1=_on(self.ffn[0].weight, dev, BF16),
-                      b1=f32(self.ffn[0].bias), w2=_on(self.ffn[2].weight, dev, BF16), b2=f32(self.ffn[2].bias),
+            pk.update(n3w=f32(self.norm3.weight), n3b=f32(self.norm3.bias), w1=_wmat(self.ffn[0].weight, dev),
+                      b1=f32(self.ffn[0].bias), w2=_wmat(self.ffn[2].weight, dev), b2=f32(self.ffn[2].bias),
                       mod=f32(self.modulation)[0], mdens=f32(self.modulation_density)[0], sig=sig, sa=sa, ca=ca)
             self._pk = pk
         return self._pk
@@ -526,7 +538,9 @@ class WanTransformer3DModel_FlexAM(nn.Module):
 
     @property
     def dtype(self):
-        return self.patch_embedding.weight.dtype
+        # qfloat8 storage (fp8_optimization.convert_weight_dtype_wrapper): the dtype the model computes in, as the reference's
+        # per-module upcast makes it
+        return getattr(self, "_flexam_compute_dtype", None) or self.patch_embedding.weight.dtype
 
     @property
     def device(self):

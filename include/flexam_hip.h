@@ -79,6 +79,19 @@ int flexam_gemm_bf16_gate_residual(const void* A, int64_t lda, const void* W, in
                                    int64_t rows_per_batch, int64_t M, int64_t N, int64_t K, const int64_t* a_koff,
                                    void* ws, int64_t ws_bytes, void* stream);
 
+/* The two GEMMs above with W held as OCP e4m3 bytes (float8_e4m3fn; ldw in BYTES, % 16 == 0; 16-byte aligned pointers): the
+ * weight-only fp8 storage of the reference's qfloat8 GPU_memory_modes (FlexAM/utils/fp8_optimization.py:20-57,
+ * comfyui/wan2_2_fun_flexam/nodes.py:327-343), read as e4m3 from HBM and LDS and widened to bf16 in registers -- exact, so the
+ * result is bit-identical to flexam_gemm_bf16 / _gate_residual on W upcast to bf16 (same tile plan, same FLEXAM_GEMM_* switches,
+ * same MFMA order).  Output widths that take the bf16 GEMM's 160-wide tile (N <= 160; N = 320, 480) are refused. */
+int flexam_gemm_w8(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
+                   int64_t M, int64_t N, int64_t K, int epilogue, int out_f32, const int64_t* a_koff, void* ws,
+                   int64_t ws_bytes, void* stream);
+int flexam_gemm_w8_gate_residual(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* X,
+                                 int64_t ldx, const float* gate, int64_t gate_ld, const int32_t* gate_row,
+                                 int64_t rows_per_batch, int64_t M, int64_t N, int64_t K, const int64_t* a_koff,
+                                 void* ws, int64_t ws_bytes, void* stream);
+
 /* fp8 variant of the two GEMMs above for the DiT's QKV / FFN projections (BASELINE.json configs[4]; selected explicitly, never
  * the default).  A8 [M,K], W8 [N,K]: OCP e4m3 bytes, K contiguous, K % 128 == 0, lda / ldw % 16 == 0; a_scale [M], w_scale [N]
  * fp32 row scales (value = byte * scale); fp32 accumulation on the block-scaled MFMA with unit block scales:

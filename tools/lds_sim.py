@@ -62,6 +62,19 @@ if __name__ == "__main__":
             worst = max(worst, ds_read_b128(addrs))
     print("gemm 32x32x16 frag read, swizzled:", worst)
 
+    # e4m3 W tile of the W8 GEMM [rows][64 e4m3] (64-B rows), 16-B chunk c of row r stored at slot c ^ ((r >> 2) & 3); lane l reads
+    # the 8 bytes of K 32 ks + 8 (l >> 4) of row l & 15: half (l >> 4) & 1 of chunk 2 ks + (l >> 5)
+    def w8_off(r, c):
+        return r * 64 + ((c ^ ((r >> 2) & 3)) * 16)
+    worst = 0
+    for ks in range(2):
+        for base in range(0, 256, 16):
+            addrs = [w8_off(base + (l & 15), 2 * ks + (l >> 5)) + 8 * ((l >> 4) & 1) for l in range(64)]
+            worst = max(worst, ds_read_b64(addrs))
+    print("gemm W8 e4m3 frag read (ds_read_b64), swizzled:", worst, "cycles (ideal 2)")
+    lin = [(l & 15) * 64 + 8 * (l >> 4) for l in range(64)]
+    print("gemm W8 e4m3 frag read, linear  :", ds_read_b64(lin))
+
     # attention K/V tile [keys][128 bf16] (256-B rows), image (b) of the guide (T10)
     def kv_off(row, ch):
         return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)))
