@@ -347,6 +347,63 @@ def test_vae_decode_chunk_true_widths_sixteenth_area():
     stats(out, want, "VAE decode, true widths, 1/16 area", rel_max=2e-2, peak=2.0)
 
 
+_ENC_TRUE = dict(z_dim=48, dim=160, dim_mult=(1, 2, 4, 4), temporal_down=(False, True, True))
+
+
+def _encode_true_widths(sd, x, chunk):
+    """The encoder at c_dim 160 (decoder kept at width 16) on `x`; chunk = FLEXAM_VAE_ENC_CHUNK (None: the default)."""
+    import os
+    from flexam_amd.wan_vae3_8 import AutoencoderKLWan3_8
+    saved = os.environ.pop("FLEXAM_VAE_ENC_CHUNK", None)
+    if chunk is not None:
+        os.environ["FLEXAM_VAE_ENC_CHUNK"] = str(chunk)
+    try:
+        vae = AutoencoderKLWan3_8(latent_channels=48, c_dim=160, dec_dim=16, dim_mult=[1, 2, 4, 4], temperal_downsample=[False, True, True],
+                                  spatial_compression_ratio=16)
+        missing, unexpected = vae.load_state_dict(sd, strict=False)
+        assert not unexpected and all(k.startswith(("model.decoder.", "model.conv2.")) for k in missing)
+        vae = vae.to("cuda:0")
+        eng = vae.encoder_engine()
+        assert eng.dims == [160, 160, 320, 640, 640] and eng.chunk == (chunk or 48)
+        return vae.encode(x.cuda()).latent_dist.mode()
+    finally:
+        os.environ.pop("FLEXAM_VAE_ENC_CHUNK", None)
+        if saved is not None:
+            os.environ["FLEXAM_VAE_ENC_CHUNK"] = saved
+
+
+def _encode_true_widths_chunkings_bit_identical():
+    sd = C.vae_enc_weights(_ENC_TRUE, seed=71, prefix="model.")
+    x = C.vae_enc_case(seed=72, frames=9, h=64, w=96)
+    a, b = _encode_true_widths(sd, x, None), _encode_true_widths(sd, x, 4)
+    assert torch.equal(a, b), f"chunks 1 + 8 and 1 + 4 + 4 differ by {float((a - b).abs().max()):.3g}"
+
+
+def test_vae_encode_true_widths_and_chunk_length():
+    """Wan2.2 VAE encoder at its real widths (c_dim 160, dim_mult (1,2,4,4): 160/320/640 channels -- run-packed 160-channel convs, the
+    192-channel space-to-depth groups; VAE.py:505-618, :788-818) on a 9-frame 64 x 96 clip: 3 latent frames, a 1-frame first chunk whose
+    time convolutions only cache, then the stride-2 hand-over.  The default walk (1 + 8 frames) and the reference's (1 + 4 + 4,
+    FLEXAM_VAE_ENC_CHUNK=4) against the fp32 oracle at the small encoder's tolerance.  Between the two walks only the GEMMs' row counts
+    differ, and with them the tail split-K plans: with the default plans they agree to 3.3e-3 rel-RMS (bf16 activations turn the
+    reordered fp32 sums into bf16 rounding flips that the following convolutions carry on), so the walks are compared where that is the only difference
+    -- in a child process with FLEXAM_GEMM_SPLITK=0 (read once per process) they must be bit-identical."""
+    import os, subprocess, sys
+    sd = C.vae_enc_weights(_ENC_TRUE, seed=71, prefix="model.")
+    x = C.vae_enc_case(seed=72, frames=9, h=64, w=96)
+    outs = {chunk: _encode_true_widths(sd, x, chunk) for chunk in (None, 4)}
+    assert all(o.shape == (1, 48, 3, 4, 6) for o in outs.values())
+    with torch.no_grad():
+        want = OV.vae_encode(sd, x, _ENC_TRUE["temporal_down"], OV.LATENT_MEAN, OV.LATENT_STD)
+    stats(outs[None], want, "VAE encode, true widths, 9 x 64 x 96, chunks 1 + 8", rel_max=2e-2, psnr_min=40.0)
+    stats(outs[4], want, "VAE encode, true widths, 9 x 64 x 96, chunks 1 + 4 + 4", rel_max=2e-2, psnr_min=40.0)
+    env = dict(os.environ, FLEXAM_GEMM_SPLITK="0")
+    code = ("import sys; sys.path.insert(0, %r); import test_full_width_gpu as T; T._encode_true_widths_chunkings_bit_identical(); "
+            "print('identical')" % os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600,
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    assert r.returncode == 0 and "identical" in r.stdout, r.stderr[-2000:]
+
+
 # ----------------------------------------------------------------------------- width x depth x steps together (r3 verdict item 3)
 def _three_layer_5b(seed=5):
     def make():
