@@ -5,14 +5,16 @@ Exports the reference's names (FlexAM/models/__init__.py, FlexAM/pipeline/__init
     Wan2_2Transformer3DModel_FlexAM, WanTransformer3DModel_FlexAM, AutoencoderKLWan3_8,
     Wan2_2FunControlPipeline_FlexAM, attention
 and, for the step in front of the sampler, `visualize_tracking_DELTA` (pipelines.py:1852: tracks -> conditioning videos), and the
-qfloat8 helpers of FlexAM/utils/fp8_optimization.py (`convert_model_weight_to_float8`, `convert_weight_dtype_wrapper`, ...).
+qfloat8 helpers of FlexAM/utils/fp8_optimization.py (`convert_model_weight_to_float8`, `convert_weight_dtype_wrapper`, ...), and
+demo.py's edit masks (`generate_mask_fg_tracking_for_validation`, `generate_mask_bg_tracking_for_validation`).
 Arithmetic runs in libflexam_hip.so (hand-written gfx950 HIP kernels, C ABI in
 include/flexam_hip.h); this package is the host-side mirror of the reference interface.
 """
 __all__ = ["Wan2_2Transformer3DModel_FlexAM", "WanTransformer3DModel_FlexAM", "AutoencoderKLWan3_8",
            "Wan2_2FunControlPipeline_FlexAM", "FlowMatchEulerDiscreteScheduler", "FlowUniPCMultistepScheduler",
            "FlowDPMSolverMultistepScheduler", "WanT5EncoderModel", "attention", "visualize_tracking_DELTA",
-           "replace_parameters_by_name", "convert_model_weight_to_float8", "autocast_model_forward", "convert_weight_dtype_wrapper"]
+           "replace_parameters_by_name", "convert_model_weight_to_float8", "autocast_model_forward", "convert_weight_dtype_wrapper",
+           "generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation"]
 
 
 def __getattr__(name):
@@ -47,4 +49,7 @@ def __getattr__(name):
     if name == "visualize_tracking_DELTA":
         from .conditioning_raster import visualize_tracking_DELTA
         return visualize_tracking_DELTA
+    if name in ("generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation"):
+        from . import edit_masks as m
+        return getattr(m, name)
     raise AttributeError(name)

@@ -83,6 +83,9 @@ _SIGNATURES = {
     "flexam_fn_count": ([], c_int),
     "flexam_fn_name": ([_I], c_char_p),
     "flexam_replay": ([_P, _L, _P, _P], c_int),
+    "flexam_edit_mask_blur": ([_P, _I, _I, _I, _P, _I, _P, _P, _P], c_int),
+    "flexam_edit_mask_hull": ([_P, _I, _I, _I, _P, _P, _P, _I, _P], c_int),
+    "flexam_edit_mask_dilate": ([_P, _P, _I, _I, _I, _P, _I, _P, _P], c_int),
 }
 
 _lib = None
@@ -1128,3 +1131,62 @@ def raster_resolve(keys, colors, out_u8=None, out_f32=None, want_u8=False, want_
     _check(lib().flexam_raster_resolve(_ptr(keys, torch.int64), _ptr(colors, U8), stride, N, T, H, W, _ptr(out_u8, U8), _ptr(out_f32, F32), _stream()),
            "flexam_raster_resolve")
     return out_u8, out_f32
+
+
+# ----------------------------------------------------------------------------- foreground-edit masks (csrc/edit_mask.hip)
+EDIT_MASK_SLOTS = 48          # frames the hull stage works on at once: its scratch is 5 * H * ceil(W / 2) ints per frame
+
+
+def _frames_u8(t, what):
+    if t.dim() != 3 or t.dtype != U8 or not t.is_contiguous():
+        raise RuntimeError(f"{what}: contiguous uint8 frames [n, H, W] required, got {tuple(t.shape)} {t.dtype}")
+    return t.shape
+
+
+def edit_mask_blur(src, weights, out=None):
+    """src [n, H, W] uint8 in {0, 1}, weights [r + 1] float64 (gaussian_filter's normalised kernel from its centre outwards) ->
+    out [n, H, W] uint8 = blurred > 0.5, with scipy.ndimage.gaussian_filter's arithmetic."""
+    n, H, W = _frames_u8(src, "edit_mask_blur")
+    if weights.dim() != 1 or weights.dtype != torch.float64 or not weights.is_contiguous() or weights.device != src.device:
+        raise RuntimeError("edit_mask_blur: weights must be a contiguous float64 vector on the frames' device")
+    if out is None:
+        out = torch.empty_like(src)
+    elif tuple(out.shape) != (n, H, W) or out.dtype != U8 or not out.is_contiguous():
+        raise RuntimeError(f"edit_mask_blur: out must be contiguous uint8 {(n, H, W)}")
+    tmp = torch.empty(n, H, W, device=src.device, dtype=F32)
+    _check(lib().flexam_edit_mask_blur(_ptr(src, U8), n, H, W, _ptr(weights, torch.float64), weights.numel() - 1, _ptr(tmp, F32),
+                                       _ptr(out, U8), _stream()), "flexam_edit_mask_blur")
+    return out
+
+
+def edit_mask_hull(binary):
+    """binary [n, H, W] uint8 -> (runs [n, H, ceil(W / 2)] int32, nruns [n, H] int32): per run slot the (lo | hi << 16) interval its
+    8-connected component's filled convex hull covers in its row (lo > hi: none)."""
+    n, H, W = _frames_u8(binary, "edit_mask_hull")
+    S = (W + 1) // 2
+    runs = torch.empty(n, H, S, device=binary.device, dtype=torch.int32)
+    nruns = torch.empty(n, H, device=binary.device, dtype=torch.int32)
+    slots = min(n, EDIT_MASK_SLOTS)
+    ws = torch.empty(slots, 5, H, S, device=binary.device, dtype=torch.int32)
+    _check(lib().flexam_edit_mask_hull(_ptr(binary, U8), n, H, W, _ptr(runs, torch.int32), _ptr(nruns, torch.int32), _raw(ws), slots,
+                                       _stream()), "flexam_edit_mask_hull")
+    return runs, nruns
+
+
+def edit_mask_dilate(runs, nruns, width, half_widths, out=None):
+    """runs / nruns of edit_mask_hull, half_widths [r + 1] int32 (the element's row half widths, |dy| = 0 .. r) -> out [n, H, W] uint8
+    in {0, 1}: the intervals dilated by the element."""
+    if runs.dim() != 3 or runs.dtype != torch.int32 or not runs.is_contiguous() or runs.shape[2] != (width + 1) // 2:
+        raise RuntimeError(f"edit_mask_dilate: runs must be contiguous int32 [n, H, ceil(W / 2)] for W = {width}, got {tuple(runs.shape)}")
+    n, H, _ = runs.shape
+    if tuple(nruns.shape) != (n, H) or nruns.dtype != torch.int32 or not nruns.is_contiguous():
+        raise RuntimeError(f"edit_mask_dilate: nruns must be contiguous int32 {(n, H)}")
+    if half_widths.dim() != 1 or half_widths.dtype != torch.int32 or not half_widths.is_contiguous() or half_widths.device != runs.device:
+        raise RuntimeError("edit_mask_dilate: half_widths must be a contiguous int32 vector on the runs' device")
+    if out is None:
+        out = torch.empty(n, H, width, device=runs.device, dtype=U8)
+    elif tuple(out.shape) != (n, H, width) or out.dtype != U8 or not out.is_contiguous():
+        raise RuntimeError(f"edit_mask_dilate: out must be contiguous uint8 {(n, H, width)}")
+    _check(lib().flexam_edit_mask_dilate(_ptr(runs, torch.int32), _ptr(nruns, torch.int32), n, H, width, _ptr(half_widths, torch.int32),
+                                         half_widths.numel() - 1, _ptr(out, U8), _stream()), "flexam_edit_mask_dilate")
+    return out

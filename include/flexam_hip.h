@@ -405,6 +405,24 @@ int flexam_fn_count(void);
 const char* flexam_fn_name(int id);
 int flexam_replay(const flexam_cmd* cmds, int64_t n, int64_t* failed_at, void* stream);
 
+/* Foreground-edit mask refinement (flexam_amd/edit_masks.py; csrc/edit_mask.hip).  Replaces the per-frame host loop of
+ * demo.py:33-96, generate_mask_fg_tracking_for_validation: scipy gaussian_filter, cv2 findContours / convexHull / fillPoly, cv2.dilate.
+ * Frames are n x H x W bytes, H <= 4096, W <= 16384; S = (W + 1) / 2 is the most runs a row can hold.
+ * edit_mask_blur: dst = (gaussian(src) > 0.5) for src in {0, 1}: scipy.ndimage.gaussian_filter's arithmetic (fp64 sums in its order,
+ *   mode 'reflect', float32 after each axis, axis 0 first).  weights[radius + 1]: the normalised kernel from its centre outwards (fp64);
+ *   tmp: n x H x W float32 scratch.
+ * edit_mask_hull: for every 8-connected component of bin (non-zero = set) the pixels in the closed convex hull of its pixel centres or
+ *   on the hull's edges drawn as 8-connected lines; components with collinear centres give nothing.  Out: nruns[n][H] and, per run slot
+ *   runs[n][H][S], the interval (lo | hi << 16) of its component in its row (lo > hi: none).  ws: slots x 5 x H x S ints of scratch;
+ *   frames are processed `slots` at a time.
+ * edit_mask_dilate: out[n][H][W] = 1 where some interval of a row y' with |y - y'| <= radius, widened by half_widths[|y - y'|] on both
+ *   sides, covers the pixel (the element's rows); 0 elsewhere.  radius 0, half_widths {0}: the intervals themselves. */
+int flexam_edit_mask_blur(const unsigned char* src, int n, int H, int W, const double* weights, int radius, float* tmp, unsigned char* dst,
+                          void* stream);
+int flexam_edit_mask_hull(const unsigned char* bin, int n, int H, int W, unsigned* runs, int* nruns, int* ws, int slots, void* stream);
+int flexam_edit_mask_dilate(const unsigned* runs, const int* nruns, int n, int H, int W, const int* half_widths, int radius, unsigned char* out,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
