@@ -42,12 +42,16 @@ __global__ __launch_bounds__(256) void softmax_bias_kernel(const float* __restri
   __syncthreads();
   mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   __syncthreads();
+  // No key survives the mask: the reference fills every masked score with finfo.min (wan_text_encoder.py:98), which swamps
+  // q.k and the bias, so all N scores are equal and the row is uniform.  exp(-inf - -inf) would make it NaN instead.
+  const bool none = mx == -INFINITY;
+  auto p = [&](int i) -> float { return none ? 1.f : __expf(val(i) - mx); };
   float sum = 0.f;
-  for (int i = threadIdx.x; i < N; i += 256) sum += __expf(val(i) - mx);
+  for (int i = threadIdx.x; i < N; i += 256) sum += p(i);
   sum = block_sum<256>(sum, red);
   const float inv = 1.f / sum;
   bf16* orow = out + (int64_t)blockIdx.x * ldo;
-  for (int i = threadIdx.x; i < Npad; i += 256) orow[i] = f2bf(i < N ? __expf(val(i) - mx) * inv : 0.f);
+  for (int i = threadIdx.x; i < Npad; i += 256) orow[i] = f2bf(i < N ? p(i) * inv : 0.f);
 }
 
 __global__ __launch_bounds__(256) void mul_bf16_kernel(const bf16* __restrict__ a, const bf16* __restrict__ b, bf16* __restrict__ out,

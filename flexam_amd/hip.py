@@ -1066,7 +1066,8 @@ def t5_norm(x, w, out, eps=1e-6):
 
 
 def softmax_bias_rows(s, out, n_valid, scale=1.0, bias=None, key_mask=None):
-    """out [M, Npad] bf16 = softmax(scale * s[:, :n_valid] + bias) over keys with key_mask != 0."""
+    """out [M, Npad] bf16 = softmax(scale * s[:, :n_valid] + bias) over keys with key_mask != 0 (uniform over the n_valid keys when
+    every key is masked, as in the reference); columns n_valid .. Npad are 0."""
     M = s.shape[0]
     _check(lib().flexam_softmax_bias_rows(_ptr(s, F32), s.stride(0), M, n_valid, scale, _ptr(bias, F32), bias.stride(0) if bias is not None else 0,
                                           _ptr(key_mask, F32), _ptr(out, BF16), out.stride(0), out.shape[1], _stream()),
