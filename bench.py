@@ -3,9 +3,10 @@
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: starts its own N rank processes, see launch_ranks)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+  python bench.py --full                                (everything besides the headline: see below)
   python bench.py --mask blob                           (BASELINE configs[3]: foreground_edit masks, its own JSON line)
   python bench.py --logit-scale 6                       (peaked softmax rows: prices the attention kernel's rescale path inside the step)
-  python bench.py --emulate-rank 8                      (ONE process runs one rank's share of an 8-GPU step; collectives = device copies)
+  python bench.py --full --emulate-rank 8               (ONE process runs one rank's share of an 8-GPU step; collectives = device copies)
   python bench.py --dump-outputs DIR                    (the latents the last timed step returned -> DIR/latents.npy: two builds, same inputs)
 
 Workload (BASELINE config 2): Wan2.2-Fun-5B-FLEXAM DiT (dim 3072, 24 heads x 128, ffn 14336,
@@ -21,9 +22,13 @@ local chunk under the gather).  FLEXAM_SP_MODE=ulysses selects the all-to-all-ov
 token chunks with the CFG pair batched), FLEXAM_CFG_PARALLEL=0/1 overrides the CFG split; for N >= 4 with nothing pinned the layout
 probe times two steps of every candidate on the node and runs the fastest; `config.parallelism` names what ran.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the self-attention flash kernel, timed
-live with events on the launch stream) and `cpu_baseline` (the fp32 oracle on the host cores, one of the
-60 block-forwards of a step, extrapolated -- a baseline, not a target).
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, the warm-up and timed steps,
+--dump-outputs, and for N > 1 the layout probe and the self-check that decide which exchange was measured and whether the
+figure is valid.  --full adds everything else after the timed region: the host enqueue time of a step, the configs[1] steps
+next to a --mask line, `roofline` / `kernels` (live per-kernel timing; dominant kernel: the self-attention flash kernel, timed
+with events on the launch stream), `cpu_baseline` (the fp32 oracle on the host cores, one of the 60 block-forwards of a step,
+extrapolated -- a baseline, not a target), `emulated_ranks` (8 by default on the headline workload), the VAE, the conditioning
+rasteriser and the end-to-end clip.  The --no-* switches and --emulate-rank refine what --full runs.
 
 The pieces live in benchlib/ (inputs, kernels, cpu_baseline, vae_clip, launch, probe, emulate); this file is the argument parser, the
 timed region and the JSON line.
@@ -82,11 +87,14 @@ def main():
                     "a SEPARATE line (dtype says so), never the headline")
     ap.add_argument("--fp8-oproj", action="store_true", help="with --fp8: the two output projections of a block on the fp8 pipe as well (FLEXAM_FP8_OPROJ=1; "
                     "beyond configs[4]'s 'QKV/FFN', its own line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cpu-legs", action="store_true", help="skip the config-1 and VAE-chunk CPU baseline legs (keep the one-block leg)")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-vae", action="store_true")
-    ap.add_argument("--no-clip", action="store_true", help="skip the end-to-end clip (pixels -> encode -> 50 steps -> decode -> frames)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what the headline does not need: host enqueue time, the configs[1] steps next to a "
+                         "--mask line, per-kernel rooflines, the CPU baseline, emulated ranks, VAE, rasteriser and the end-to-end clip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-cpu-legs", action="store_true", help="with --full: skip the config-1 and VAE-chunk CPU baseline legs (keep the one-block leg)")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="with --full: skip the per-kernel rooflines")
+    ap.add_argument("--no-vae", action="store_true", help="with --full: skip the VAE, the rasteriser and the clip")
+    ap.add_argument("--no-clip", action="store_true", help="with --full: skip the end-to-end clip (pixels -> encode -> 50 steps -> decode -> frames)")
     ap.add_argument("--mask", choices=["motion", "blob", "blob-open", "soft"], default="motion",
                     help="motion: BASELINE configs[1] (motion_transfer, frame 0 known); blob: configs[3] foreground_edit as demo.py "
                          "builds it; blob-open / soft: foreground masks that are not pinned (many per-token timesteps)")
@@ -95,9 +103,9 @@ def main():
                     help="multiply every self_attn.norm_q / norm_k weight by sqrt(S): q.k / sqrt(128) then has std ~S instead of ~1 (peaked softmax rows, "
                          "the attention kernel's deferred-rescale branch taken); a SEPARATE line that says so, never the headline")
     ap.add_argument("--emulate-rank", type=int, default=None, metavar="N",
-                    help="after the single-GPU measurement: one rank's share of an N-GPU step per layout, collectives replaced by same-size device "
-                         "copies on a side stream -> `emulated_ranks` / `predicted_scaling_no_comm` (benchlib/emulate.py); default: 8 on the headline "
-                         "workload (a few seconds, after the timed region), off on the variant lines; 0 = off")
+                    help="with --full, after the single-GPU measurement: one rank's share of an N-GPU step per layout, collectives replaced by same-size "
+                         "device copies on a side stream -> `emulated_ranks` / `predicted_scaling_no_comm` (benchlib/emulate.py); default: 8 on the "
+                         "headline workload (a few seconds, after the timed region), off on the variant lines; 0 = off")
     ap.add_argument("--emulate-which", type=int, default=None, help="which rank of the sequence-parallel group to emulate (default: a middle chunk)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step returned (the latents) as DIR/<name>.npy in float32, "
@@ -105,6 +113,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.emulate_rank and not args.full:
+        ap.error("--emulate-rank runs after the timed region: it needs --full")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         launch_ranks(args, os.path.abspath(__file__))      # does not return
@@ -198,14 +208,16 @@ def main():
         return {"latents": pipe._state["latents"].float().cpu()} if args.dump_outputs and rank == 0 else None
     outputs = last_step_outputs()
     rows_u = int(pipe._state["U"])
-    # host side of a step: how long Python + ctypes need to ENQUEUE one step's ~420 launches (the GPU is idle-free while this
-    # stays below the step's GPU time; at N ranks the GPU time shrinks N-fold, the enqueue time does not)
-    sync()
-    th0 = time.perf_counter()
-    for i in range(2):
-        pipe.denoise_step((args.warmup + args.steps + i) % total_steps)
-    host_enqueue = (time.perf_counter() - th0) / 2
-    sync()
+    host_enqueue = None
+    if args.full:
+        # host side of a step: how long Python + ctypes need to ENQUEUE one step's ~420 launches (the GPU is idle-free while this
+        # stays below the step's GPU time; at N ranks the GPU time shrinks N-fold, the enqueue time does not)
+        sync()
+        th0 = time.perf_counter()
+        for i in range(2):
+            pipe.denoise_step((args.warmup + args.steps + i) % total_steps)
+        host_enqueue = (time.perf_counter() - th0) / 2
+        sync()
 
     def timed(p):
         for i in range(args.warmup):
@@ -217,7 +229,7 @@ def main():
         sync()
         return time.perf_counter() - t0
     motion_elapsed = None
-    if args.mask != "motion" and world == 1:
+    if args.full and args.mask != "motion" and world == 1:
         # configs[3] next to configs[1]: the SAME steps on the motion_transfer conditioning, in this process (the delta is what
         # the foreground masks cost: per-token timestep rows, AdaLN table size)
         inp_m, cond_m = conditioning("motion")
@@ -230,7 +242,7 @@ def main():
     from benchlib.kernels import kernel_rooflines, kernels_object, newest_profile, roofline_object, sampler_step_roofline, self_attention_in_step
     lc = L // eng.sp_size
     b_local = 1 if eng.cfg_size == 2 else B
-    kern = None if args.no_kernel_timing else kernel_rooflines(eng, b_local, L, lc)
+    kern = kernel_rooflines(eng, b_local, L, lc) if args.full and not args.no_kernel_timing else None
     attn_in_step = None
     if kern is not None and world == 1:
         attn_in_step = self_attention_in_step(pipe, (args.warmup + args.steps + 2) % total_steps, b_local)
@@ -261,7 +273,7 @@ def main():
             check = multi_gpu_check(pipe, model, inp, cond, (args.warmup + args.steps) % total_steps, total_steps, world, rank)
     eng_sage = bool(getattr(eng, "sage_taken", False))          # what the engine DID (SAGE_ATTENTION is ignored under sequence parallelism)
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from benchlib.cpu_baseline import cpu_baseline, cpu_baseline_legs
         base = cpu_baseline(L, cfg)
         if not args.no_cpu_legs:
@@ -284,7 +296,9 @@ def main():
     emulated = raster = None
     headline = not (args.fp8 or args.sage or args.logit_scale is not None or args.mask != "motion" or args.layers != 30
                     or (args.frames, args.height, args.width) != (97, 512, 896))
-    n_emulate = args.emulate_rank if args.emulate_rank is not None else (8 if headline else 0)
+    n_emulate = 0
+    if args.full:
+        n_emulate = args.emulate_rank if args.emulate_rank is not None else (8 if headline else 0)
     if n_emulate and rank == 0 and world == 1:
         from benchlib.emulate import emulate
         pipe = eng = None
@@ -297,7 +311,7 @@ def main():
             model._parallel, model._engine = None, None
         pipe = eng = None
     clip = None
-    if rank == 0 and world == 1 and not args.no_vae:
+    if args.full and rank == 0 and world == 1 and not args.no_vae:
         from benchlib.vae_clip import time_clip, time_vae
         pipe = eng = None
         torch.cuda.empty_cache()
@@ -366,13 +380,7 @@ def main():
                                    f"random-init bf16 weights, synthetic conditioning " + tag,
                        "parallelism": par if world > 1 else "single GPU", "layers": cfg["num_layers"]},
             "sec_per_clip_50_steps_denoise_only": total_steps / steps_per_sec,
-            "vae_decode_sec": vae_sec, "vae_encode_sec_per_stream": enc_stream_sec, "conditioning_encode_sec_8_streams": enc_sec,
             "prepare_sec": prepare_sec,
-            "conditioning_raster": raster,
-            "clip_end_to_end": clip,
-            "sec_per_clip": (enc_sec + prepare_sec + total_steps / steps_per_sec + vae_sec) if vae_sec is not None else None,
-            "sec_per_clip_from_tracks": ((enc_sec + prepare_sec + total_steps / steps_per_sec + vae_sec + raster["sec"])
-                                         if vae_sec is not None and raster and raster.get("sec") else None),
             "dit_block_executed_tflops": executed_block_flops * steps_per_sec / 1e12,
             "dit_block_executed_mfma_frac": executed_block_flops * steps_per_sec / 1e12 / (PEAK_BF16_TFLOPS * world),
             "dit_block_algorithmic_tflops": step_block_flops * steps_per_sec / 1e12,
@@ -384,8 +392,17 @@ def main():
                                     + (" (QKV / FFN ran on the 5 PFLOP/s fp8 pipe: not a roofline fraction)" if args.fp8 else ""),
             "finite": finite,
             "mask": args.mask, "timestep_rows_per_sample": rows_u,
-            "host_enqueue_ms_per_step": host_enqueue * 1e3,
         }
+        if args.full:
+            result.update({
+                "vae_decode_sec": vae_sec, "vae_encode_sec_per_stream": enc_stream_sec, "conditioning_encode_sec_8_streams": enc_sec,
+                "conditioning_raster": raster,
+                "clip_end_to_end": clip,
+                "sec_per_clip": (enc_sec + prepare_sec + total_steps / steps_per_sec + vae_sec) if vae_sec is not None else None,
+                "sec_per_clip_from_tracks": ((enc_sec + prepare_sec + total_steps / steps_per_sec + vae_sec + raster["sec"])
+                                             if vae_sec is not None and raster and raster.get("sec") else None),
+                "host_enqueue_ms_per_step": host_enqueue * 1e3,
+            })
         if args.sage and not eng_sage:
             result["sage_ignored"] = "--sage / VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION was asked for but the engine ran the bf16 attention kernel (sequence parallelism)"
         if args.logit_scale is not None:

@@ -1,6 +1,6 @@
 """`python bench.py --gpus N` as the driver calls it (no torch.distributed.run environment): the parent starts the N ranks
 itself without touching the GPU, forwards rank 0's JSON line and carries the self-check of the multi-rank exchange.
-CPU: the launcher's refusal path.  GPU (one device): two and four ranks share cuda:0 under gloo -- the rank code path RCCL
+CPU: the launcher's refusal path, and --emulate-rank refused without --full.  GPU (one device): two and four ranks share cuda:0 under gloo -- the rank code path RCCL
 drives on a multi-GPU node; such a line is marked invalid as a measurement, its `check` is real."""
 import json
 import os
@@ -163,7 +163,7 @@ def test_probe_retries_a_candidate_whose_first_touch_was_over_budget():
 def test_one_gpu_line_carries_an_emulated_rank_of_four():
     """`bench.py --emulate-rank N` on one GPU: one rank's share of an N-GPU step per layout through the real engine, collectives as
     same-size device copies (flexam_amd.dist.LoopbackGroup); the line keeps its single-GPU measurement and gains `emulated_ranks`."""
-    r = _run(["--gpus", "1", *[a for a in SMALL if a != "--no-vae"], "--no-clip", "--emulate-rank", "4"], {})
+    r = _run(["--gpus", "1", *[a for a in SMALL if a != "--no-vae"], "--no-clip", "--full", "--emulate-rank", "4"], {})
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     em = res["emulated_ranks"]
@@ -190,9 +190,41 @@ def test_one_gpu_line_carries_an_emulated_rank_of_four():
     row = em["layouts"][1]
     assert row["sp_size"] == 4 and row["cfg_size"] == 1 and row["samples_per_rank"] == 2 and row["tokens_per_rank"] * 4 == 256 and row["ms_per_step"] > 0
     assert set(em["predicted_scaling_no_comm"]) == set(names) and "NOT a multi-GPU measurement" in em["what"]
-    # and without the flag a debug-size run (not the headline workload) does not emulate
-    r = _run(["--gpus", "1", *SMALL], {})
+    # and without the flag a debug-size run (not the headline workload) does not emulate, not even under --full
+    r = _run(["--gpus", "1", *SMALL, "--full"], {})
     assert r.returncode == 0 and "emulated_ranks" not in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+
+
+def test_emulate_rank_needs_full():
+    """An emulated rank runs after the timed region, which a plain run leaves out: asking for one without --full is refused before
+    any GPU work, never silently dropped."""
+    r = _run(["--gpus", "1", *SMALL, "--emulate-rank", "4"], {}, timeout=300)
+    assert r.returncode != 0
+    assert "--emulate-rank runs after the timed region: it needs --full" in r.stderr
+
+
+FULL_ONLY = ("host_enqueue_ms_per_step", "configs1_same_process", "roofline", "kernels", "cpu_baseline", "emulated_ranks", "vae_decode_sec",
+             "vae_encode_sec_per_stream", "conditioning_encode_sec_8_streams", "conditioning_raster", "clip_end_to_end", "sec_per_clip",
+             "sec_per_clip_from_tracks")
+
+
+@pytest.mark.gpu
+def test_plain_line_is_lean_and_full_adds_the_rest():
+    """A plain run measures only its headline: with none of the --no-* switches it still times no kernels, runs no CPU baseline, VAE,
+    rasteriser or clip, and (for a --mask line) no configs[1] steps.  --full brings all of them back into the same line."""
+    r = _run(["--gpus", "1", *[a for a in SMALL if not a.startswith("--no-")], "--mask", "blob"], {})
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert res["finite"] and res["steps"] == 2 and res["warmup"] == 1 and res["ms_per_step"] * res["value"] == pytest.approx(1e3)
+    assert res["metric"] == "denoise-steps/sec" and res["unit"] == "denoise-steps/sec" and res["higher_is_better"] and res["dtype"] == "bf16"
+    assert not [k for k in FULL_ONLY if k in res], res
+    r = _run(["--gpus", "1", *[a for a in SMALL if not a.startswith("--no-")], "--full"], {})
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert res["finite"] and res["host_enqueue_ms_per_step"] > 0
+    assert res["kernels"] and res["roofline"] and res["cpu_baseline"]["value"] > 0 and res["cpu_baseline"]["legs"]
+    assert res["vae_decode_sec"] > 0 and res["conditioning_raster"]["sec"] > 0 and res["clip_end_to_end"]["finite"] and res["sec_per_clip"] > 0
+    assert "emulated_ranks" not in res and "configs1_same_process" not in res       # debug size: not the headline; motion: no second config
 
 
 @pytest.mark.gpu
