@@ -177,7 +177,9 @@ __global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) {
   }
   i32x8 kf_pre = k_read(IC<1>{}, IC<0>{});
   int ks_nxt = ks_read(IC<1>{});
-  {   // the first reference (= ref0): a whole number 2^6 ... 2^7 below the row maximum of half tile 0
+  {   // the first reference (= ref0): a whole number 2^6 ... 2^7 below the row maximum of half tile 0's VALID keys -- a range whose
+      // only tile holds fewer than 32 keys has padding here (zero rows: score 0), which would otherwise set ref0 and flush P to zero
+    mask_half(0, s_a);
     float mx = s_a[0];
 #pragma unroll
     for (int e = 1; e < 16; ++e) mx = fmaxf(mx, s_a[e]);

@@ -5,9 +5,13 @@ within a tolerance; the tolerances below are the e4m3 format's: every operand el
 output differs from fp32 attention by 5 % rms; the bf16 kernel by 0.2 %."""
 import math
 import os
+import sys
 
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from mxfp8_restatement import mx_quant as _mx_quant  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 LOG2E = 1.4426950408889634
@@ -44,6 +48,27 @@ def test_mxfp8_attention_against_fp32_attention(H, B, Hh, L, splits):
     want = _ref(q, k, v)
     rel = float((o - want).norm() / want.norm())
     print(B, Hh, L, splits, "rel-RMS", rel)
+    assert torch.isfinite(o).all() and rel <= 6.5e-2
+
+
+@pytest.mark.parametrize("L,splits", [(20, None), (1040, (5, 0))])
+def test_mxfp8_attention_over_a_short_key_range_far_below_zero(H, L, splits):
+    """A key range whose only tile holds fewer than 32 keys (L = 20; the last of 5 ranges at L = 1040), every score 24 or more binades
+    below 0: the padding keys of the range's first half tile (zero rows, score 0) must not set the row reference, or P flushes to zero
+    and the output collapses towards 0 instead of being the weighted mean of V."""
+    g = torch.Generator().manual_seed(L)
+    q = torch.randn(1, L, 2, 128, generator=g) * 0.1
+    q[..., :8] = -1.0
+    k = torch.randn(1, L, 2, 128, generator=g) * 0.1
+    k[..., :8] = 4.0
+    v = torch.randn(1, L, 2, 128, generator=g) + 1.0
+    q, k, v = (t.to(torch.bfloat16).cuda() for t in (q, k, v))
+    kw = {} if splits is None else dict(kv_splits=splits[0], split_from_unit=splits[1])
+    o = H.attn_fwd_fp8(H.attn_fp8_pack(q, k, v), L, **kw).float()
+    want = _ref(q, k, v)
+    assert float(torch.einsum("blhd,bmhd->bhlm", q.float(), k.float()).max()) <= -24.0
+    rel = float((o - want).norm() / want.norm())
+    print(L, splits, "rel-RMS", rel)
     assert torch.isfinite(o).all() and rel <= 6.5e-2
 
 
@@ -97,19 +122,6 @@ def test_attention_seam_takes_the_reference_switch(H):
         assert torch.equal(attention(q, k, v, attention_type="SAGE_ATTENTION"), want)
     cross = attention(q, k[:, :77], v[:, :77], attention_type="SAGE_ATTENTION")      # Lq != Lk: the bf16 kernel
     assert torch.equal(cross, attention(q, k[:, :77], v[:, :77]))
-
-
-def _mx_quant(x32):
-    """OCP MX block quantisation as the pack kernel does it: x32 [..., 32] fp32 -> (e4m3 bytes [..., 32] uint8, E8M0 byte [...] uint8),
-    scale = the smallest power of two with amax / scale <= 448."""
-    amax = x32.abs().amax(dim=-1)
-    t = (amax / 448.0).float()
-    bits = t.view(torch.int32)
-    e = ((bits >> 23) & 255) + ((bits & 0x7FFFFF) != 0).int()
-    e = e.clamp(1, 253)
-    inv = ((254 - e) << 23).view(torch.float32)
-    q = (x32 * inv.unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
-    return q, e.to(torch.uint8)
 
 
 def test_pack_kernel_bytes_scales_and_layouts_exactly(H):
