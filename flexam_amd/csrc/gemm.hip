@@ -892,29 +892,37 @@ int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff,
   return flexam_check_launch(W8 ? "flexam_gemm_w8" : "flexam_gemm_bf16");
 }
 
-template <int EPI, typename OutT, int MT, bool W8 = false>
-int launch_mt(const GemmParams& p, const GemmWorkspace& g_ws, const int64_t* a_koff, hipStream_t s) {
-  return launch_shape<EPI, OutT, MT, 2, 4, W8>(p, g_ws, a_koff, s);
+// Length of a launch on pick_mt's scale: rounds of the concurrently resident workgroups (whole ones + the tail plan_split leaves)
+// x relative cost of one tile.
+double launch_cost(const GemmWorkspace& g_ws, int tiles, int nk, double tile_cost) {
+  int S, rem;
+  double tail;
+  plan_split(g_ws, tiles, nk, S, rem, &tail);
+  return (tiles / num_cus() + tail) * tile_cost;
 }
 
-// Tile height: rounds of 256 concurrently resident workgroups x relative cost of one tile (MT m-tiles of MFMA work
-// plus a fixed part for the W side, barriers and the epilogue); FLEXAM_GEMM_MT=8..4 forces a shape (tuning only).
+// The best 256-wide plan: tile heights MT = 8..4, a tile costing its MT m-tiles of MFMA work plus a fixed part for the W side,
+// barriers and the epilogue.  A smaller tile replaces a larger one only below `keep` x its cost; returns the cost of the plan kept.
+double best_256wide(const GemmWorkspace& g_ws, int M, int tiles_n, int nk, double keep, int* best_mt = nullptr) {
+  int best = 8;
+  double best_cost = 1e30;
+  for (int mt = 8; mt >= 4; --mt) {
+    const int tiles = (int)((long)((M + 32 * mt - 1) / (32 * mt)) * tiles_n);
+    const double cost = launch_cost(g_ws, tiles, nk, mt + 1.25);
+    if (cost < best_cost * keep) { best_cost = cost; best = mt; }
+  }
+  if (best_mt) *best_mt = best;
+  return best_cost;
+}
+
+// Tile height of the 256-wide shapes; FLEXAM_GEMM_MT=8..4 forces one (tuning only).
 int pick_mt(const GemmWorkspace& g_ws, int M, int tiles_n, int nk) {
   const char* e = getenv("FLEXAM_GEMM_MT");
   const int forced = e ? atoi(e) : 0;
   if (forced >= 4 && forced <= 8) return forced;
-  int best = 8;
-  double best_cost = 1e30;
-  const int G = num_cus();
-  for (int mt = 8; mt >= 4; --mt) {
-    const int tiles = (int)((long)((M + 32 * mt - 1) / (32 * mt)) * tiles_n);
-    int S, rem;
-    double tail;
-    plan_split(g_ws, tiles, nk, S, rem, &tail);
-    const double cost = (tiles / G + tail) * (mt + 1.25);
-    if (cost < best_cost * 0.97) { best_cost = cost; best = mt; }      // a smaller tile must win by > 3 %
-  }
-  return best;
+  int mt;
+  best_256wide(g_ws, M, tiles_n, nk, 0.97, &mt);                       // a smaller tile must win by > 3 %
+  return mt;
 }
 
 // caller's scratch -> workspace view; too small or NULL = no split-K
@@ -977,30 +985,66 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
     const int mode = e ? atoi(e) : 1;
     bool take = mode == 2;
     if (mode == 1) {
-      const int G = num_cus(), nk = p.K / BK;
-      double best256 = 1e30;
-      for (int mt = 8; mt >= 4; --mt) {
-        const int tiles = (int)((long)((p.M + 32 * mt - 1) / (32 * mt)) * p.tiles_n);
-        int S, rem;
-        double tail;
-        plan_split(g_ws, tiles, nk, S, rem, &tail);
-        best256 = fmin(best256, (tiles / G + tail) * (mt + 1.25));
-      }
+      const int nk = p.K / BK;
       const int tiles192 = (int)((long)((p.M + 191) / 192) * (p.N / 192));
-      int S, rem;
-      double tail;
-      plan_split(g_ws, tiles192, nk, S, rem, &tail);
-      take = (tiles192 / G + tail) * (0.75 * 6 + 1.1) < 0.95 * best256;
+      take = launch_cost(g_ws, tiles192, nk, 0.75 * 6 + 1.1) < 0.95 * best_256wide(g_ws, p.M, p.tiles_n, nk, 1.0);
     }
     if (take) return launch_shape<EPI, OutT, 6, 2, 3, W8>(p, g_ws, a_koff, s);
   }
   switch (pick_mt(g_ws, p.M, p.tiles_n, p.K / BK)) {
-    case 7: return launch_mt<EPI, OutT, 7, W8>(p, g_ws, a_koff, s);
-    case 6: return launch_mt<EPI, OutT, 6, W8>(p, g_ws, a_koff, s);
-    case 5: return launch_mt<EPI, OutT, 5, W8>(p, g_ws, a_koff, s);
-    case 4: return launch_mt<EPI, OutT, 4, W8>(p, g_ws, a_koff, s);
-    default: return launch_mt<EPI, OutT, 8, W8>(p, g_ws, a_koff, s);
+    case 7: return launch_shape<EPI, OutT, 7, 2, 4, W8>(p, g_ws, a_koff, s);
+    case 6: return launch_shape<EPI, OutT, 6, 2, 4, W8>(p, g_ws, a_koff, s);
+    case 5: return launch_shape<EPI, OutT, 5, 2, 4, W8>(p, g_ws, a_koff, s);
+    case 4: return launch_shape<EPI, OutT, 4, 2, 4, W8>(p, g_ws, a_koff, s);
+    default: return launch_shape<EPI, OutT, 8, 2, 4, W8>(p, g_ws, a_koff, s);
   }
+}
+
+// The two problem kinds -- argument checks, GemmParams, launch -- behind the bf16-W and e4m3-W (W8: ldw in bytes) entry points;
+// the messages name the entry point.  tiles_m depends on the tile height launch() picks.
+template <bool W8>
+int gemm_plain(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc, int64_t M, int64_t N,
+               int64_t K, int epilogue, int out_f32, const int64_t* a_koff, void* ws, int64_t ws_bytes, void* stream) {
+  const char* who = W8 ? "gemm_w8" : "gemm";
+  FX_REQUIRE(A && W && C, FLEXAM_E_ARG, "%s: null pointer", who);
+  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "%s: empty problem M=%ld N=%ld K=%ld", who, (long)M, (long)N, (long)K);
+  FX_REQUIRE(K % BK == 0, FLEXAM_E_SHAPE, "%s: K=%ld must be a multiple of %d (pad on the host)", who, (long)K, BK);
+  FX_REQUIRE(N % 4 == 0 && ldc % 4 == 0, FLEXAM_E_SHAPE, "%s: N=%ld and ldc=%ld must be multiples of 4", who, (long)N, (long)ldc);
+  FX_REQUIRE(lda % 8 == 0 && ldw % (W8 ? 16 : 8) == 0, FLEXAM_E_SHAPE,
+             W8 ? "gemm_w8: lda (elements) and ldw (bytes) must make 16-byte rows" : "gemm: lda/ldw must be multiples of 8 elements (16-byte rows)");
+  FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "%s: pointers must be 16-byte aligned", who);
+  FX_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU, FLEXAM_E_ARG, "%s: unknown epilogue %d", who, epilogue);
+  FX_REQUIRE(!out_f32 || epilogue == EPI_NONE, FLEXAM_E_ARG, "%s: f32 output supports no activation epilogue", who);
+  GemmParams p{};
+  p.A = (const bf16*)A; p.W = W; p.C = C; p.bias = bias;
+  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.tiles_n = (int)((N + BN - 1) / BN);
+  hipStream_t s = (hipStream_t)stream;
+  if (out_f32) return launch<EPI_NONE, float, W8>(p, ws, ws_bytes, a_koff, s);
+  return epilogue == EPI_GELU ? launch<EPI_GELU, bf16, W8>(p, ws, ws_bytes, a_koff, s) : launch<EPI_NONE, bf16, W8>(p, ws, ws_bytes, a_koff, s);
+}
+
+// Alignment: the e4m3-W form holds A, W, X and the workspace to 16 bytes, the bf16-W form only the workspace (as each always did).
+template <bool W8>
+int gemm_gate_residual(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* X, int64_t ldx,
+                       const float* gate, int64_t gate_ld, const int32_t* gate_row, int64_t rows_per_batch, int64_t M, int64_t N,
+                       int64_t K, const int64_t* a_koff, void* ws, int64_t ws_bytes, void* stream) {
+  const char* who = W8 ? "gemm_w8_gate_residual" : "gemm_gate_residual";
+  FX_REQUIRE(A && W && X, FLEXAM_E_ARG, "%s: null pointer", who);
+  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "%s: empty problem", who);
+  FX_REQUIRE(K % BK == 0 && N % 4 == 0 && ldx % 4 == 0, FLEXAM_E_SHAPE, "%s: K%%64, N%%4, ldx%%4 required", who);
+  FX_REQUIRE(lda % 8 == 0 && ldw % (W8 ? 16 : 8) == 0, FLEXAM_E_SHAPE,
+             W8 ? "gemm_w8_gate_residual: lda (elements) and ldw (bytes) must make 16-byte rows" : "gemm_gate_residual: lda/ldw must be multiples of 8");
+  if constexpr (W8) FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)X | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "%s: pointers must be 16-byte aligned", who);
+  FX_REQUIRE(!gate || gate_row || rows_per_batch > 0, FLEXAM_E_ARG, "%s: gate needs gate_row or rows_per_batch", who);
+  if constexpr (!W8) FX_REQUIRE((uintptr_t)ws % 16 == 0, FLEXAM_E_ARG, "%s: workspace must be 16-byte aligned", who);
+  GemmParams p{};
+  p.A = (const bf16*)A; p.W = W; p.C = nullptr; p.bias = bias;
+  p.lda = lda; p.ldw = ldw; p.ldc = 0; p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.tiles_n = (int)((N + BN - 1) / BN);
+  p.X = X; p.ldx = ldx; p.gate = gate; p.gate_ld = gate_ld; p.gate_row = gate_row;
+  p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
+  return launch<EPI_GATE_RESIDUAL, bf16, W8>(p, ws, ws_bytes, a_koff, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -1008,42 +1052,14 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
 extern "C" int flexam_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
                                 int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue, int out_f32,
                                 const int64_t* a_koff, void* ws, int64_t ws_bytes, void* stream) {
-  FX_REQUIRE(A && W && C, FLEXAM_E_ARG, "gemm: null pointer");
-  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "gemm: empty problem M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-  FX_REQUIRE(K % BK == 0, FLEXAM_E_SHAPE, "gemm: K=%ld must be a multiple of %d (pad on the host)", (long)K, BK);
-  FX_REQUIRE(N % 4 == 0 && ldc % 4 == 0, FLEXAM_E_SHAPE, "gemm: N=%ld and ldc=%ld must be multiples of 4", (long)N, (long)ldc);
-  FX_REQUIRE(lda % 8 == 0 && ldw % 8 == 0, FLEXAM_E_SHAPE, "gemm: lda/ldw must be multiples of 8 elements (16-byte rows)");
-  FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "gemm: pointers must be 16-byte aligned");
-  FX_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU, FLEXAM_E_ARG, "gemm: unknown epilogue %d", epilogue);
-  GemmParams p{};
-  p.A = (const bf16*)A; p.W = W; p.C = C; p.bias = bias;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);   // tiles_m depends on the tile height launch() picks
-  hipStream_t s = (hipStream_t)stream;
-  if (out_f32) {
-    FX_REQUIRE(epilogue == EPI_NONE, FLEXAM_E_ARG, "gemm: f32 output supports no activation epilogue");
-    return launch<EPI_NONE, float>(p, ws, ws_bytes, a_koff, s);
-  }
-  return epilogue == EPI_GELU ? launch<EPI_GELU, bf16>(p, ws, ws_bytes, a_koff, s) : launch<EPI_NONE, bf16>(p, ws, ws_bytes, a_koff, s);
+  return gemm_plain<false>(A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, out_f32, a_koff, ws, ws_bytes, stream);
 }
 
 extern "C" int flexam_gemm_bf16_gate_residual(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
                                               float* X, int64_t ldx, const float* gate, int64_t gate_ld,
                                               const int32_t* gate_row, int64_t rows_per_batch, int64_t M, int64_t N,
                                               int64_t K, const int64_t* a_koff, void* ws, int64_t ws_bytes, void* stream) {
-  FX_REQUIRE(A && W && X, FLEXAM_E_ARG, "gemm_gate_residual: null pointer");
-  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "gemm_gate_residual: empty problem");
-  FX_REQUIRE(K % BK == 0 && N % 4 == 0 && ldx % 4 == 0, FLEXAM_E_SHAPE, "gemm_gate_residual: K%%64, N%%4, ldx%%4 required");
-  FX_REQUIRE(lda % 8 == 0 && ldw % 8 == 0, FLEXAM_E_SHAPE, "gemm_gate_residual: lda/ldw must be multiples of 8");
-  FX_REQUIRE(!gate || gate_row || rows_per_batch > 0, FLEXAM_E_ARG, "gemm_gate_residual: gate needs gate_row or rows_per_batch");
-  GemmParams p{};
-  p.A = (const bf16*)A; p.W = W; p.C = nullptr; p.bias = bias;
-  p.lda = lda; p.ldw = ldw; p.ldc = 0; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);   // tiles_m depends on the tile height launch() picks
-  p.X = X; p.ldx = ldx; p.gate = gate; p.gate_ld = gate_ld; p.gate_row = gate_row;
-  p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-  FX_REQUIRE((uintptr_t)ws % 16 == 0, FLEXAM_E_ARG, "gemm_gate_residual: workspace must be 16-byte aligned");
-  return launch<EPI_GATE_RESIDUAL, bf16>(p, ws, ws_bytes, a_koff, (hipStream_t)stream);
+  return gemm_gate_residual<false>(A, lda, W, ldw, bias, X, ldx, gate, gate_ld, gate_row, rows_per_batch, M, N, K, a_koff, ws, ws_bytes, stream);
 }
 
 // e4m3 W (OCP bytes, ldw in bytes): the same problems, plans and epilogues as the bf16 pair above, bit-identical to them on W
@@ -1051,38 +1067,12 @@ extern "C" int flexam_gemm_bf16_gate_residual(const void* A, int64_t lda, const 
 extern "C" int flexam_gemm_w8(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc,
                               int64_t M, int64_t N, int64_t K, int epilogue, int out_f32, const int64_t* a_koff, void* ws,
                               int64_t ws_bytes, void* stream) {
-  FX_REQUIRE(A && W && C, FLEXAM_E_ARG, "gemm_w8: null pointer");
-  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "gemm_w8: empty problem M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
-  FX_REQUIRE(K % BK == 0, FLEXAM_E_SHAPE, "gemm_w8: K=%ld must be a multiple of %d (pad on the host)", (long)K, BK);
-  FX_REQUIRE(N % 4 == 0 && ldc % 4 == 0, FLEXAM_E_SHAPE, "gemm_w8: N=%ld and ldc=%ld must be multiples of 4", (long)N, (long)ldc);
-  FX_REQUIRE(lda % 8 == 0 && ldw % 16 == 0, FLEXAM_E_SHAPE, "gemm_w8: lda (elements) and ldw (bytes) must make 16-byte rows");
-  FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)C | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "gemm_w8: pointers must be 16-byte aligned");
-  FX_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU, FLEXAM_E_ARG, "gemm_w8: unknown epilogue %d", epilogue);
-  FX_REQUIRE(!out_f32 || epilogue == EPI_NONE, FLEXAM_E_ARG, "gemm_w8: f32 output supports no activation epilogue");
-  GemmParams p{};
-  p.A = (const bf16*)A; p.W = W; p.C = C; p.bias = bias;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);
-  hipStream_t s = (hipStream_t)stream;
-  if (out_f32) return launch<EPI_NONE, float, true>(p, ws, ws_bytes, a_koff, s);
-  return epilogue == EPI_GELU ? launch<EPI_GELU, bf16, true>(p, ws, ws_bytes, a_koff, s) : launch<EPI_NONE, bf16, true>(p, ws, ws_bytes, a_koff, s);
+  return gemm_plain<true>(A, lda, W, ldw, bias, C, ldc, M, N, K, epilogue, out_f32, a_koff, ws, ws_bytes, stream);
 }
 
 extern "C" int flexam_gemm_w8_gate_residual(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, float* X,
                                             int64_t ldx, const float* gate, int64_t gate_ld, const int32_t* gate_row,
                                             int64_t rows_per_batch, int64_t M, int64_t N, int64_t K, const int64_t* a_koff, void* ws,
                                             int64_t ws_bytes, void* stream) {
-  FX_REQUIRE(A && W && X, FLEXAM_E_ARG, "gemm_w8_gate_residual: null pointer");
-  FX_REQUIRE(M > 0 && N > 0 && K > 0, FLEXAM_E_SHAPE, "gemm_w8_gate_residual: empty problem");
-  FX_REQUIRE(K % BK == 0 && N % 4 == 0 && ldx % 4 == 0, FLEXAM_E_SHAPE, "gemm_w8_gate_residual: K%%64, N%%4, ldx%%4 required");
-  FX_REQUIRE(lda % 8 == 0 && ldw % 16 == 0, FLEXAM_E_SHAPE, "gemm_w8_gate_residual: lda (elements) and ldw (bytes) must make 16-byte rows");
-  FX_REQUIRE(((uintptr_t)A | (uintptr_t)W | (uintptr_t)X | (uintptr_t)ws) % 16 == 0, FLEXAM_E_ARG, "gemm_w8_gate_residual: pointers must be 16-byte aligned");
-  FX_REQUIRE(!gate || gate_row || rows_per_batch > 0, FLEXAM_E_ARG, "gemm_w8_gate_residual: gate needs gate_row or rows_per_batch");
-  GemmParams p{};
-  p.A = (const bf16*)A; p.W = W; p.C = nullptr; p.bias = bias;
-  p.lda = lda; p.ldw = ldw; p.ldc = 0; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);
-  p.X = X; p.ldx = ldx; p.gate = gate; p.gate_ld = gate_ld; p.gate_row = gate_row;
-  p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-  return launch<EPI_GATE_RESIDUAL, bf16, true>(p, ws, ws_bytes, a_koff, (hipStream_t)stream);
+  return gemm_gate_residual<true>(A, lda, W, ldw, bias, X, ldx, gate, gate_ld, gate_row, rows_per_batch, M, N, K, a_koff, ws, ws_bytes, stream);
 }

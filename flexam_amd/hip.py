@@ -11,82 +11,16 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 import torch
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libflexam_hip.so")
 
-EPI_NONE, EPI_GELU_TANH = 0, 1
-
 _P, _I, _L, _F = c_void_p, c_int, c_int64, c_float
-_SIGNATURES = {
-    "flexam_version": ([], c_int),
-    "flexam_arch": ([], c_char_p),
-    "flexam_last_error": ([], c_char_p),
-    "flexam_device_check": ([], c_int),
-    "flexam_device_cus": ([], c_int),
-    "flexam_set_cu_budget": ([_I], c_int),
-    "flexam_gemm_bf16": ([_P, _L, _P, _L, _P, _P, _L, _L, _L, _L, _I, _I, _P, _P, _L, _P], c_int),
-    "flexam_gemm_bf16_gate_residual": ([_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P, _L, _P], c_int),
-    "flexam_gemm_w8": ([_P, _L, _P, _L, _P, _P, _L, _L, _L, _L, _I, _I, _P, _P, _L, _P], c_int),
-    "flexam_gemm_w8_gate_residual": ([_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P, _P, _L, _P], c_int),
-    "flexam_quantize_rows_fp8": ([_P, _L, _P, _L, _P, _L, _I, _P], c_int),
-    "flexam_gemm_fp8": ([_P, _L, _P, _P, _L, _P, _P, _P, _L, _L, _L, _L, _I, _P], c_int),
-    "flexam_gemm_fp8_gate_residual": ([_P, _L, _P, _P, _L, _P, _P, _P, _L, _P, _L, _P, _L, _L, _L, _L, _P], c_int),
-    "flexam_gemm_fp8_gelu_q": ([_P, _L, _P, _P, _L, _P, _P, _P, _P, _L, _L, _L, _L, _P], c_int),
-    "flexam_attn_fwd": ([_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _P], c_int),
-    "flexam_attn_fwd_lastkey": ([_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _F, _P], c_int),
-    "flexam_attn_fwd_splitkv": ([_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P], c_int),
-    "flexam_attn_fwd_partial": ([_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P], c_int),
-    "flexam_attn_merge": ([_P, _L, _L, _I, _I, _I, _I, _F, _I, _P, _P, _P], c_int),
-    "flexam_attn_fp8_pack": ([_P, _L, _L, _P, _L, _L, _P, _L, _L, _P, _P, _P, _I, _I, _I, _I, _P], c_int),
-    "flexam_rmsnorm_rope_mx": ([_P, _L, _P, _P, _L, _P, _P, _P, _P, _L, _I, _F, _P, _P, _L, _L, _I, _I, _P], c_int),
-    "flexam_attn_fwd_fp8": ([_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
-    "flexam_attn_fwd_fp8_chunked": ([_P, _P, _P, _P, _L, _L, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
-    "flexam_ln_modulate": ([_P, _L, _L, _I, _F, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P], c_int),
-    "flexam_ln_modulate_fp8": ([_P, _L, _L, _I, _F, _P, _P, _L, _P, _L, _P, _P, _P, _L, _P, _P, _F, _F, _P], c_int),
-    "flexam_gate_residual": ([_P, _L, _P, _L, _P, _L, _P, _L, _L, _I, _P], c_int),
-    "flexam_rmsnorm_rope": ([_P, _L, _P, _L, _P, _P, _L, _P, _L, _P, _L, _I, _F, _P, _P, _L, _L, _I, _P], c_int),
-    "flexam_rmsnorm_rope_scatter": ([_P, _L, _P, _P, _L, _P, _P, _L, _P, _P, _P, _L, _L, _I, _L, _L, _I, _F, _P, _P, _L, _L, _I, _P], c_int),
-    "flexam_mod_table": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P], c_int),
-    "flexam_small_linear_f32": ([_P, _L, _P, _I, _L, _P, _P, _L, _I, _I, _I, _I, _P], c_int),
-    "flexam_sinusoid_embed": ([_P, _P, _I, _I, _P], c_int),
-    "flexam_patchify": ([_P, _I, _I, _I, _I, _I, _P, _L, _I, _L, _P], c_int),
-    "flexam_unpatchify": ([_P, _L, _L, _I, _I, _I, _I, _P, _I, _P], c_int),
-    "flexam_cfg_euler_blend": ([_P, _P, _L, _L, _F, _F, _P, _P, _P, _I, _I, _I, _I, _P], c_int),
-    "flexam_axpby_f32": ([_P, _F, _P, _F, _L, _P], c_int),
-    "flexam_checksum": ([_P, _L, _P, _P], c_int),
-    "flexam_cfg_velocity": ([_P, _P, _L, _L, _F, _P, _I, _I, _I, _I, _P], c_int),
-    "flexam_lincomb_f32": ([_P, _L, _I, _P, _P, _P], c_int),
-    "flexam_mask_blend_f32": ([_P, _P, _P, _I, _L, _P], c_int),
-    "flexam_pack_cl": ([_P, _I, _I, _I, _I, _I, _P, _I, _I, _P], c_int),
-    "flexam_unpack_cl": ([_P, _I, _L, _I, _I, _I, _I, _P, _P], c_int),
-    "flexam_groupnorm_silu_cl": ([_P, _L, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _I, _P, _I, _P], c_int),
-    "flexam_vae_prep_cl": ([_P, _I, _L, _I, _I, _I, _I, _P, _I, _P, _I, _I, _I, _P], c_int),
-    "flexam_upsample2x_cl": ([_P, _I, _L, _I, _I, _I, _I, _I, _P, _I, _P], c_int),
-    "flexam_dupup_add_cl": ([_P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _P], c_int),
-    "flexam_deinterleave_cl": ([_P, _I, _L, _I, _I, _I, _I, _P, _I, _P], c_int),
-    "flexam_tapsum_cl": ([_P, _L, _I, _I, _I, _I, _I, _P, _P, _L, _P], c_int),
-    "flexam_phase_dupup_cl": ([_P, _L, _L, _P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _P], c_int),
-    "flexam_softmax_rows": ([_P, _L, _L, _I, _F, _P, _L, _I, _P], c_int),
-    "flexam_scatter_add_cl": ([_P, _L, _P, _L, _I, _I, _I, _I, _P], c_int),
-    "flexam_vae_unpatchify_clamp": ([_P, _L, _I, _I, _I, _P, _I, _I, _F, _F, _P], c_int),
-    "flexam_pack_affine_cl": ([_P, _I, _I, _I, _I, _P, _P, _P, _I, _P], c_int),
-    "flexam_raster_keys": ([_P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P], c_int),
-    "flexam_raster_resolve": ([_P, _P, _L, _I, _I, _I, _I, _P, _P, _P], c_int),
-    "flexam_t5_norm": ([_P, _L, _L, _I, _F, _P, _P, _L, _I, _P], c_int),
-    "flexam_softmax_bias_rows": ([_P, _L, _L, _I, _F, _P, _L, _P, _P, _L, _I, _P], c_int),
-    "flexam_mul_bf16": ([_P, _P, _P, _L, _P], c_int),
-    "flexam_vae_patchify_cl": ([_P, _I, _I, _I, _I, _I, _P, _I, _I, _P], c_int),
-    "flexam_space_to_depth_cl": ([_P, _I, _L, _I, _I, _I, _I, _P, _I, _I, _P], c_int),
-    "flexam_avgdown_add_cl": ([_P, _L, _I, _I, _I, _I, _P, _L, _I, _I, _I, _I, _P], c_int),
-    "flexam_delay_us": ([_F, _P], c_int),
-    "flexam_fn_id": ([c_char_p], c_int),
-    "flexam_fn_count": ([], c_int),
-    "flexam_fn_name": ([_I], c_char_p),
-    "flexam_replay": ([_P, _L, _P, _P], c_int),
-    "flexam_edit_mask_blur": ([_P, _I, _I, _I, _P, _I, _P, _P, _P], c_int),
-    "flexam_edit_mask_hull": ([_P, _I, _I, _I, _P, _P, _P, _I, _P], c_int),
-    "flexam_edit_mask_dilate": ([_P, _P, _I, _I, _I, _P, _I, _P, _P], c_int),
-}
+_SIGNATURES = abi.signatures(abi.PROTOTYPES)        # {name: (argtypes, restype)} of include/flexam_hip.h, in header order
+_STREAM_ORDERED = frozenset(n for n, _ in abi.stream_ordered(abi.PROTOTYPES))
+_REPLAYABLE = frozenset(n for n, _ in abi.replayable(abi.PROTOTYPES))
+EPI_NONE, EPI_GELU_TANH = abi.CONSTANTS["FLEXAM_EPI_NONE"], abi.CONSTANTS["FLEXAM_EPI_GELU_TANH"]
 
 _lib = None
 
@@ -118,7 +52,7 @@ def lib():
 
 
 # ----------------------------------------------------------------------------- command lists (csrc/replay.hip)
-REPLAY_MAX_ARGS = 26
+REPLAY_MAX_ARGS = abi.CONSTANTS["FLEXAM_REPLAY_MAX_ARGS"]
 
 
 class _Arg(ctypes.Union):
@@ -177,8 +111,7 @@ class _Recorder:
     def __getattr__(self, name):
         real = _lib if _lib is not None else load_library()
         fn = getattr(real, name)
-        fid = _fn_id(name) if name.startswith("flexam_") and name not in ("flexam_fn_id", "flexam_fn_name", "flexam_fn_count", "flexam_replay") else -1
-        if fid < 0:
+        if name not in _REPLAYABLE:
             return fn
         if name in _NOT_RECORDABLE:
             raise RuntimeError(f"{name} takes host arrays and cannot be part of a recorded launch plan")
@@ -186,7 +119,7 @@ class _Recorder:
         if w is None:
             kinds = _SIGNATURES[name][0][:-1]
 
-            def w(*args, _fn=fn, _fid=fid, _kinds=kinds, _name=name):
+            def w(*args, _fn=fn, _fid=_fn_id(name), _kinds=kinds, _name=name):
                 rc = _fn(*args)
                 if rc == 0:
                     if len(args) != len(_kinds) + 1:
@@ -258,17 +191,21 @@ def host_op(fn):
 
 def delay_us(us: float):
     """Emulation aid: the current stream waits `us` microseconds (flexam_delay_us)."""
-    _check(lib().flexam_delay_us(float(us), _stream()), "flexam_delay_us")
+    _call("flexam_delay_us", float(us))
 
 
 def recording() -> bool:
     return _rec is not None
 
 
-def _check(rc: int, what: str):
+def _call(name: str, *args, stream=None):
+    """Calls entry point `name` through lib() (so a recorder stands in front of it); stream-ordered ones get the current stream (or
+    `stream`, where the caller already asked for it) as their last argument.  A non-zero return code raises."""
+    if name in _STREAM_ORDERED:
+        args += (_stream() if stream is None else stream,)
+    rc = getattr(lib(), name)(*args)
     if rc != 0:
-        msg = lib().flexam_last_error().decode()
-        raise RuntimeError(f"{what} failed with code {rc}: {msg}")
+        raise RuntimeError(f"{name} failed with code {rc}: {lib().flexam_last_error().decode()}")
 
 
 def _stream() -> int:
@@ -301,16 +238,16 @@ def _rows(t):
     return t.shape[0], t.shape[1], t.stride(0)
 
 
-BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
+BF16, F32, I32, I64, U8, F8 = torch.bfloat16, torch.float32, torch.int32, torch.int64, torch.uint8, torch.float8_e4m3fn
 
 
 def device_check():
-    _check(lib().flexam_device_check(), "flexam_device_check")
+    _call("flexam_device_check")
 
 
 def set_cu_budget(cus: int = 0):
     """Plan the library's persistent grids for `cus` CUs of the current device (0 = all); see flexam_set_cu_budget."""
-    _check(lib().flexam_set_cu_budget(int(cus)), "flexam_set_cu_budget")
+    _call("flexam_set_cu_budget", int(cus))
 
 
 def num_cus() -> int:
@@ -320,7 +257,7 @@ def num_cus() -> int:
 
 # ----------------------------------------------------------------------------- GEMM
 _GEMM_WS = {}
-GEMM_WS_BYTES = 256 * 256 * 256 * 4                 # FLEXAM_GEMM_WS_BYTES
+GEMM_WS_BYTES = abi.CONSTANTS["FLEXAM_GEMM_WS_BYTES"]
 WS_CACHE_SLOTS = 8                                  # (device, stream) pairs that keep their scratch; older ones are dropped
 
 
@@ -346,56 +283,51 @@ def _gemm_workspace(device, stream: int):
 
 
 def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, out_dtype=BF16, a_koff=None, m=None, k=None):
-    """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  a, w bf16 2-D views (row stride free); a float8_e4m3fn `w` (qfloat8 weight
-    storage) is read as such by gemm_w8.
+    """out[M,N] = epi(a[M,K] @ w[N,K]^T + bias).  a bf16, w bf16 or float8_e4m3fn (qfloat8 weight storage, read as such by
+    flexam_gemm_w8: no bf16 copy of w, bit-identical to the GEMM on w.to(bfloat16)); 2-D views, row stride free.
     With a_koff (int64 [K/64]) `a` is only a base view: rows are `m`, K = `k` (implicit conv)."""
-    if w.dtype == F8:
-        return gemm_w8(a, w, bias, out, epilogue, out_dtype, a_koff, m, k)
+    who, wdt = ("gemm_w8", F8) if w.dtype == F8 else ("gemm", BF16)
     am, ak, lda = _rows(a)
     wn, wk, ldw = _rows(w)
     M = am if m is None else m
     K = wk if k is None else k
     if a_koff is None and ak != K:
-        raise RuntimeError(f"gemm: K mismatch a {ak} vs w {K}")
+        raise RuntimeError(f"{who}: K mismatch a {ak} vs w {K}")
     if out is None:
         out = torch.empty(M, wn, device=a.device, dtype=out_dtype)
     om, on, ldc = _rows(out)
     if (om, on) != (M, wn):
-        raise RuntimeError(f"gemm: out shape {tuple(out.shape)} != ({M}, {wn})")
+        raise RuntimeError(f"{who}: out shape {tuple(out.shape)} != ({M}, {wn})")
     st = _stream()
     ws = _gemm_workspace(a.device, st)
-    _check(lib().flexam_gemm_bf16(_ptr(a, BF16), lda, _ptr(w, BF16), ldw, _ptr(bias, F32), _ptr(out), ldc, M, wn, K, epilogue,
-                                  1 if out.dtype == F32 else 0, _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_bf16")
+    _call("flexam_gemm_w8" if wdt == F8 else "flexam_gemm_bf16", _ptr(a, BF16), lda, _ptr(w, wdt), ldw, _ptr(bias, F32), _ptr(out), ldc, M,
+          wn, K, epilogue, 1 if out.dtype == F32 else 0, _ptr(a_koff, I64), _raw(ws), ws.numel(), stream=st)
     return out
 
 
 def gemm_gate_residual(a, w, bias, x, gate=None, gate_row=None, rows_per_batch=0, a_koff=None):
-    """x[M,N] (fp32, in place) += bf16(a @ w^T + bias) * gate[row].  With a_koff `a` is a base view
-    (implicit conv) and M, K come from x and w.  A float8_e4m3fn `w` goes to gemm_w8_gate_residual."""
-    if w.dtype == F8:
-        return gemm_w8_gate_residual(a, w, bias, x, gate, gate_row, rows_per_batch, a_koff)
+    """x[M,N] (fp32, in place) += bf16(a @ w^T + bias) * gate[row]; w bf16 or float8_e4m3fn as in gemm.  With a_koff `a` is a base
+    view (implicit conv) and M, K come from x and w."""
+    who, wdt = ("gemm_w8_gate_residual", F8) if w.dtype == F8 else ("gemm_gate_residual", BF16)
     am, ak, lda = _rows(a)
     N, K, ldw = _rows(w)
     M, xn, ldx = _rows(x)
     if (a_koff is None and (ak != K or am != M)) or xn != N:
-        raise RuntimeError("gemm_gate_residual: shape mismatch")
+        raise RuntimeError(f"{who}: shape mismatch")
     gate_ld = gate.stride(0) if gate is not None else 0
     st = _stream()
     ws = _gemm_workspace(a.device, st)
-    _check(lib().flexam_gemm_bf16_gate_residual(_ptr(a, BF16), lda, _ptr(w, BF16), ldw, _ptr(bias, F32), _ptr(x, F32), ldx,
-                                                _ptr(gate, F32), gate_ld, _ptr(gate_row, I32), rows_per_batch, M, N, K,
-                                                _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_bf16_gate_residual")
+    _call("flexam_gemm_w8_gate_residual" if wdt == F8 else "flexam_gemm_bf16_gate_residual", _ptr(a, BF16), lda, _ptr(w, wdt), ldw,
+          _ptr(bias, F32), _ptr(x, F32), ldx, _ptr(gate, F32), gate_ld, _ptr(gate_row, I32), rows_per_batch, M, N, K, _ptr(a_koff, I64),
+          _raw(ws), ws.numel(), stream=st)
     return x
 
 
 # ----------------------------------------------------------------------------- e4m3 weights, bf16 activations (qfloat8 modes)
-F8 = torch.float8_e4m3fn
-
-
-def _ptr_w8(w):
-    if w.dtype not in (F8, torch.uint8):
+def _e4m3(w):
+    if w.dtype not in (F8, U8):
         raise RuntimeError(f"flexam_amd.hip: expected float8_e4m3fn (or uint8 e4m3 bytes) weights, got {w.dtype}")
-    return _ptr(w)
+    return w.view(F8)
 
 
 def gemm_w8_takes(n: int) -> bool:
@@ -409,46 +341,16 @@ def gemm_w8_takes(n: int) -> bool:
 
 
 def gemm_w8(a, w, bias=None, out=None, epilogue=EPI_NONE, out_dtype=BF16, a_koff=None, m=None, k=None):
-    """gemm() with w [N, K] OCP e4m3 (float8_e4m3fn or uint8 bytes; a row slice of a fused buffer is fine): bit-identical to
-    gemm(a, w.to(bfloat16), ...), without a bf16 copy of w (flexam_gemm_w8)."""
-    am, ak, lda = _rows(a)
-    wn, wk, ldw = _rows(w)
-    M = am if m is None else m
-    K = wk if k is None else k
-    if a_koff is None and ak != K:
-        raise RuntimeError(f"gemm_w8: K mismatch a {ak} vs w {K}")
-    if out is None:
-        out = torch.empty(M, wn, device=a.device, dtype=out_dtype)
-    om, on, ldc = _rows(out)
-    if (om, on) != (M, wn):
-        raise RuntimeError(f"gemm_w8: out shape {tuple(out.shape)} != ({M}, {wn})")
-    st = _stream()
-    ws = _gemm_workspace(a.device, st)
-    _check(lib().flexam_gemm_w8(_ptr(a, BF16), lda, _ptr_w8(w), ldw, _ptr(bias, F32), _ptr(out), ldc, M, wn, K, epilogue,
-                                1 if out.dtype == F32 else 0, _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_w8")
-    return out
+    """gemm() for w [N, K] OCP e4m3 only: float8_e4m3fn, or the same bytes as uint8 (a row slice of a fused buffer is fine)."""
+    return gemm(a, _e4m3(w), bias, out, epilogue, out_dtype, a_koff, m, k)
 
 
 def gemm_w8_gate_residual(a, w, bias, x, gate=None, gate_row=None, rows_per_batch=0, a_koff=None):
-    """gemm_gate_residual() with w [N, K] OCP e4m3 (flexam_gemm_w8_gate_residual)."""
-    am, ak, lda = _rows(a)
-    N, K, ldw = _rows(w)
-    M, xn, ldx = _rows(x)
-    if (a_koff is None and (ak != K or am != M)) or xn != N:
-        raise RuntimeError("gemm_w8_gate_residual: shape mismatch")
-    gate_ld = gate.stride(0) if gate is not None else 0
-    st = _stream()
-    ws = _gemm_workspace(a.device, st)
-    _check(lib().flexam_gemm_w8_gate_residual(_ptr(a, BF16), lda, _ptr_w8(w), ldw, _ptr(bias, F32), _ptr(x, F32), ldx,
-                                              _ptr(gate, F32), gate_ld, _ptr(gate_row, I32), rows_per_batch, M, N, K,
-                                              _ptr(a_koff, I64), _raw(ws), ws.numel(), st), "flexam_gemm_w8_gate_residual")
-    return x
+    """gemm_gate_residual() for w [N, K] OCP e4m3 only (float8_e4m3fn or uint8 bytes)."""
+    return gemm_gate_residual(a, _e4m3(w), bias, x, gate, gate_row, rows_per_batch, a_koff)
 
 
 # ----------------------------------------------------------------------------- fp8 GEMM (BASELINE configs[4])
-U8 = torch.uint8
-
-
 def quantize_rows_fp8(x, q=None, scale=None):
     """x [M, K] bf16 rows -> (q [M, K] uint8 holding OCP e4m3 bytes, scale [M] fp32) with x ~ q * scale[:, None]."""
     M, K, ldx = _rows(x)
@@ -456,8 +358,7 @@ def quantize_rows_fp8(x, q=None, scale=None):
         q = torch.empty(M, K, device=x.device, dtype=U8)
     if scale is None:
         scale = torch.empty(M, device=x.device, dtype=F32)
-    _check(lib().flexam_quantize_rows_fp8(_ptr(x, BF16), ldx, _ptr(q, U8), q.stride(0), _ptr(scale, F32), M, K, _stream()),
-           "flexam_quantize_rows_fp8")
+    _call("flexam_quantize_rows_fp8", _ptr(x, BF16), ldx, _ptr(q, U8), q.stride(0), _ptr(scale, F32), M, K)
     return q, scale
 
 
@@ -469,8 +370,8 @@ def gemm_fp8(a8, a_scale, w8, w_scale, bias=None, out=None, epilogue=EPI_NONE):
         raise RuntimeError(f"gemm_fp8: K mismatch a {K} vs w {wk}")
     if out is None:
         out = torch.empty(M, N, device=a8.device, dtype=BF16)
-    _check(lib().flexam_gemm_fp8(_ptr(a8, U8), lda, _ptr(a_scale, F32), _ptr(w8, U8), ldw, _ptr(w_scale, F32), _ptr(bias, F32),
-                                 _ptr(out, BF16), out.stride(0), M, N, K, epilogue, _stream()), "flexam_gemm_fp8")
+    _call("flexam_gemm_fp8", _ptr(a8, U8), lda, _ptr(a_scale, F32), _ptr(w8, U8), ldw, _ptr(w_scale, F32), _ptr(bias, F32), _ptr(out, BF16),
+          out.stride(0), M, N, K, epilogue)
     return out
 
 
@@ -481,8 +382,8 @@ def gemm_fp8_gelu_q(a8, a_scale, w8, w_scale, bias, out_scale, q_out):
     qm, qn, ldq = _rows(q_out)
     if wk != K or qm != M or qn != N:
         raise RuntimeError("gemm_fp8_gelu_q: shape mismatch")
-    _check(lib().flexam_gemm_fp8_gelu_q(_ptr(a8, U8), lda, _ptr(a_scale, F32), _ptr(w8, U8), ldw, _ptr(w_scale, F32), _ptr(bias, F32),
-                                        _ptr(out_scale, F32), _ptr(q_out, U8), ldq, M, N, K, _stream()), "flexam_gemm_fp8_gelu_q")
+    _call("flexam_gemm_fp8_gelu_q", _ptr(a8, U8), lda, _ptr(a_scale, F32), _ptr(w8, U8), ldw, _ptr(w_scale, F32), _ptr(bias, F32),
+          _ptr(out_scale, F32), _ptr(q_out, U8), ldq, M, N, K)
     return q_out
 
 
@@ -493,9 +394,8 @@ def gemm_fp8_gate_residual(a8, a_scale, w8, w_scale, bias, x, gate=None, gate_ro
     xm, xn, ldx = _rows(x)
     if wk != K or xm != M or xn != N:
         raise RuntimeError("gemm_fp8_gate_residual: shape mismatch")
-    _check(lib().flexam_gemm_fp8_gate_residual(_ptr(a8, U8), lda, _ptr(a_scale, F32), _ptr(w8, U8), ldw, _ptr(w_scale, F32), _ptr(bias, F32),
-                                               _ptr(x, F32), ldx, _ptr(gate, F32), gate.stride(0) if gate is not None else 0,
-                                               _ptr(gate_row, I32), rows_per_batch, M, N, K, _stream()), "flexam_gemm_fp8_gate_residual")
+    _call("flexam_gemm_fp8_gate_residual", _ptr(a8, U8), lda, _ptr(a_scale, F32), _ptr(w8, U8), ldw, _ptr(w_scale, F32), _ptr(bias, F32),
+          _ptr(x, F32), ldx, _ptr(gate, F32), gate.stride(0) if gate is not None else 0, _ptr(gate_row, I32), rows_per_batch, M, N, K)
     return x
 
 
@@ -528,7 +428,7 @@ def attn_kv_splits(batch_heads: int, lq: int, lk: int, n_cu: int = 256) -> int:
 _ATTN_WS = {}
 
 
-ATTN_PRESCALED = -1.0      # flexam_hip.h FLEXAM_ATTN_PRESCALED
+ATTN_PRESCALED = abi.CONSTANTS["FLEXAM_ATTN_PRESCALED"]
 
 
 def attn_fwd_lastkey(q, k, v, last_key_multiplicity, out=None, softmax_scale=None, prescaled=False):
@@ -542,9 +442,8 @@ def attn_fwd_lastkey(q, k, v, last_key_multiplicity, out=None, softmax_scale=Non
     if out is None:
         out = torch.empty(B, Lq, H, D, device=q.device, dtype=BF16)
     scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
-    _check(lib().flexam_attn_fwd_lastkey(_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1),
-                                         _ptr(v, BF16), v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1),
-                                         B, H, Lq, Lk, D, scale, float(last_key_multiplicity), _stream()), "flexam_attn_fwd_lastkey")
+    _call("flexam_attn_fwd_lastkey", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, scale, float(last_key_multiplicity))
     return out
 
 
@@ -567,9 +466,8 @@ def attn_fwd(q, k, v, out=None, softmax_scale=None, kv_splits=None, split_from_u
     else:
         S, from_unit = int(kv_splits), (0 if split_from_unit is None else int(split_from_unit))
     if S <= 1:
-        _check(lib().flexam_attn_fwd(_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1),
-                                     _ptr(v, BF16), v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1),
-                                     B, H, Lq, Lk, D, scale, _stream()), "flexam_attn_fwd")
+        _call("flexam_attn_fwd", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+              v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, scale)
         return out
     n = units - from_unit
     st = _stream()
@@ -579,10 +477,9 @@ def attn_fwd(q, k, v, out=None, softmax_scale=None, kv_splits=None, split_from_u
         _ws_slot(_ATTN_WS, slot, lambda: (key, torch.empty(S, n, 256, D, device=q.device, dtype=F32),
                                           torch.empty(S, n, 256, 2, device=q.device, dtype=F32)))
     _, ws_o, ws_ml = _ws_slot(_ATTN_WS, slot, None)
-    _check(lib().flexam_attn_fwd_splitkv(_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1),
-                                         _ptr(v, BF16), v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1),
-                                         B, H, Lq, Lk, D, scale, S, from_unit, _ptr(ws_o, F32), _ptr(ws_ml, F32), _stream()),
-           "flexam_attn_fwd_splitkv")
+    _call("flexam_attn_fwd_splitkv", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, scale, S, from_unit, _ptr(ws_o, F32),
+          _ptr(ws_ml, F32))
     return out
 
 
@@ -612,9 +509,8 @@ def attn_fwd_partial(q, k, v, ws, slot0, kv_splits=1, softmax_scale=None, presca
     if slot0 + S > ws_o.shape[0] or ws_o.shape[1] != B * H * ((Lq + 255) // 256):
         raise RuntimeError("attn_fwd_partial: workspace too small for these slots / this query shape")
     scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
-    _check(lib().flexam_attn_fwd_partial(_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1),
-                                         _ptr(v, BF16), v.stride(0), v.stride(1), B, H, Lq, Lk, D, scale, S, slot0,
-                                         _ptr(ws_o, F32), _ptr(ws_ml, F32), _stream()), "flexam_attn_fwd_partial")
+    _call("flexam_attn_fwd_partial", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+          v.stride(0), v.stride(1), B, H, Lq, Lk, D, scale, S, slot0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
     return S
 
 
@@ -624,8 +520,8 @@ def attn_merge(out, ws, n_slots, softmax_scale=None, prescaled=False):
     if out.stride(3) != 1 or out.stride(2) != D:
         raise RuntimeError("attn_merge: heads must be packed along the row")
     scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
-    _check(lib().flexam_attn_merge(_ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, D, scale, n_slots, _ptr(ws[0], F32),
-                                   _ptr(ws[1], F32), _stream()), "flexam_attn_merge")
+    _call("flexam_attn_merge", _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, D, scale, n_slots, _ptr(ws[0], F32),
+          _ptr(ws[1], F32))
     return out
 
 
@@ -668,9 +564,8 @@ def attn_fp8_pack(q, k, v, bufs=None):
     _check_fp8_bufs(bufs, B, H, L, v.device, "attn_fp8_pack")
     q8, qs, kv8 = bufs
     qk = (lambda t: (t.stride(0), t.stride(1))) if q is not None else (lambda t: (0, 0))
-    _check(lib().flexam_attn_fp8_pack(_ptr(q, BF16), *qk(q), _ptr(k, BF16), *qk(k), _ptr(v, BF16),
-                                      v.stride(0), v.stride(1), _raw(q8), _raw(qs), _raw(kv8), B, H, L, D, _stream()),
-           "flexam_attn_fp8_pack")
+    _call("flexam_attn_fp8_pack", _ptr(q, BF16), *qk(q), _ptr(k, BF16), *qk(k), _ptr(v, BF16), v.stride(0), v.stride(1), _raw(q8), _raw(qs),
+          _raw(kv8), B, H, L, D)
     return bufs
 
 
@@ -682,9 +577,8 @@ def rmsnorm_rope_mx(q, wq, k, wk, bufs, rope_cos, rope_sin, tokens_per_batch, to
         raise RuntimeError(f"rmsnorm_rope_mx: {M} rows of {C} columns do not tile batches of {tokens_per_batch} tokens x {heads} heads x 128")
     _check_fp8_bufs(bufs, M // tokens_per_batch, heads, tokens_per_batch, q.device, "rmsnorm_rope_mx")
     q8, qs, kv8 = bufs
-    _check(lib().flexam_rmsnorm_rope_mx(_ptr(q, BF16), ldq, _ptr(wq, F32), _ptr(k, BF16), k.stride(0), _ptr(wk, F32), _raw(q8),
-                                        _raw(qs), _raw(kv8), M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32),
-                                        tokens_per_batch, token_offset, heads, 128, _stream()), "flexam_rmsnorm_rope_mx")
+    _call("flexam_rmsnorm_rope_mx", _ptr(q, BF16), ldq, _ptr(wq, F32), _ptr(k, BF16), k.stride(0), _ptr(wk, F32), _raw(q8), _raw(qs),
+          _raw(kv8), M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, heads, 128)
     return bufs
 
 
@@ -712,8 +606,8 @@ def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None):
             _ws_slot(_ATTN_WS, slot, lambda: (key, torch.empty(S, n, 256, D, device=q8.device, dtype=F32),
                                               torch.empty(S, n, 256, 2, device=q8.device, dtype=F32)))
         _, ws_o, ws_ml = _ws_slot(_ATTN_WS, slot, None)
-    _check(lib().flexam_attn_fwd_fp8(_raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D,
-                                     max(S, 1), from_unit if S > 1 else 0, _ptr(ws_o, F32), _ptr(ws_ml, F32), _stream()), "flexam_attn_fwd_fp8")
+    _call("flexam_attn_fwd_fp8", _raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D, max(S, 1),
+          from_unit if S > 1 else 0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
     return out
 
 
@@ -747,9 +641,8 @@ def attn_fwd_fp8_chunked(q8, qs, kv8_chunks, lq, lk, out=None):
             _ws_slot(_ATTN_WS, slot, lambda: (key, torch.empty(S, n, 256, D, device=q8.device, dtype=F32),
                                               torch.empty(S, n, 256, 2, device=q8.device, dtype=F32)))
         _, ws_o, ws_ml = _ws_slot(_ATTN_WS, slot, None)
-    _check(lib().flexam_attn_fwd_fp8_chunked(_raw(q8), _raw(qs), _raw(kv8_chunks), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, lq, lk,
-                                             chunk_tiles, D, max(S, 1), from_unit if S > 1 else 0, _ptr(ws_o, F32), _ptr(ws_ml, F32), _stream()),
-           "flexam_attn_fwd_fp8_chunked")
+    _call("flexam_attn_fwd_fp8_chunked", _raw(q8), _raw(qs), _raw(kv8_chunks), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, lq, lk,
+          chunk_tiles, D, max(S, 1), from_unit if S > 1 else 0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
     return out
 
 
@@ -761,9 +654,8 @@ def ln_modulate(x, out=None, eps=1e-6, shift=None, scale=None, row_index=None, r
     tab_ld = shift.stride(0) if shift is not None else 0
     if shift is not None and (shift.stride(-1) != 1 or scale.stride(-1) != 1 or scale.stride(0) != tab_ld):
         raise RuntimeError("ln_modulate: shift/scale must be row views of one table")
-    _check(lib().flexam_ln_modulate(_ptr(x, F32), ldx, M, C, eps, _ptr(shift, F32), _ptr(scale, F32), tab_ld,
-                                    _ptr(row_index, I32), rows_per_batch, _ptr(ln_w, F32), _ptr(ln_b, F32), _ptr(out, BF16),
-                                    out.stride(0), _stream()), "flexam_ln_modulate")
+    _call("flexam_ln_modulate", _ptr(x, F32), ldx, M, C, eps, _ptr(shift, F32), _ptr(scale, F32), tab_ld, _ptr(row_index, I32),
+          rows_per_batch, _ptr(ln_w, F32), _ptr(ln_b, F32), _ptr(out, BF16), out.stride(0))
     return out
 
 
@@ -774,18 +666,17 @@ def ln_modulate_fp8(x, q_out, row_scale, eps=1e-6, shift=None, scale=None, row_i
     next_wnorm >= max |w_j|_2, next_bias >= max |b_j| of that GEMM (see flexam_hip.h)."""
     M, C, ldx = _rows(x)
     tab_ld = shift.stride(0) if shift is not None else 0
-    _check(lib().flexam_ln_modulate_fp8(_ptr(x, F32), ldx, M, C, eps, _ptr(shift, F32), _ptr(scale, F32), tab_ld, _ptr(row_index, I32),
-                                        rows_per_batch, _ptr(ln_w, F32), _ptr(ln_b, F32), _ptr(q_out, torch.uint8), q_out.stride(0),
-                                        _ptr(row_scale, F32), _ptr(next_scale, F32), float(next_wnorm), float(next_bias), _stream()),
-           "flexam_ln_modulate_fp8")
+    _call("flexam_ln_modulate_fp8", _ptr(x, F32), ldx, M, C, eps, _ptr(shift, F32), _ptr(scale, F32), tab_ld, _ptr(row_index, I32),
+          rows_per_batch, _ptr(ln_w, F32), _ptr(ln_b, F32), _ptr(q_out, torch.uint8), q_out.stride(0), _ptr(row_scale, F32),
+          _ptr(next_scale, F32), float(next_wnorm), float(next_bias))
     return q_out, row_scale
 
 
 def gate_residual(x, y, gate=None, row_index=None, rows_per_batch=0):
     M, C, ldx = _rows(x)
     gate_ld = gate.stride(0) if gate is not None else 0
-    _check(lib().flexam_gate_residual(_ptr(x, F32), ldx, _ptr(y, BF16), y.stride(0), _ptr(gate, F32), gate_ld,
-                                      _ptr(row_index, I32), rows_per_batch, M, C, _stream()), "flexam_gate_residual")
+    _call("flexam_gate_residual", _ptr(x, F32), ldx, _ptr(y, BF16), y.stride(0), _ptr(gate, F32), gate_ld, _ptr(row_index, I32),
+          rows_per_batch, M, C)
     return x
 
 
@@ -795,11 +686,9 @@ def rmsnorm_rope(q, wq, k=None, wk=None, eps=1e-6, rope_cos=None, rope_sin=None,
     M, C, ldq = _rows(q)
     q_out = q if q_out is None else q_out
     k_out = k if k_out is None else k_out
-    _check(lib().flexam_rmsnorm_rope(_ptr(q, BF16), ldq, _ptr(q_out, BF16), q_out.stride(0), _ptr(wq, F32),
-                                     _ptr(k, BF16), k.stride(0) if k is not None else 0,
-                                     _ptr(k_out, BF16), k_out.stride(0) if k_out is not None else 0, _ptr(wk, F32),
-                                     M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset,
-                                     head_dim, _stream()), "flexam_rmsnorm_rope")
+    _call("flexam_rmsnorm_rope", _ptr(q, BF16), ldq, _ptr(q_out, BF16), q_out.stride(0), _ptr(wq, F32), _ptr(k, BF16),
+          k.stride(0) if k is not None else 0, _ptr(k_out, BF16), k_out.stride(0) if k_out is not None else 0, _ptr(wk, F32), M, C, eps,
+          _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, head_dim)
     return q_out, k_out
 
 
@@ -809,11 +698,10 @@ def rmsnorm_rope_scatter(q, wq, k, wk, v, q_out, k_out, v_out, ld_out, out_bs, c
     layout described in flexam_hip.h (element (m, col) -> (m // tpb) * out_bs + (m % tpb) * ld_out + (col // col_block) *
     block_stride + col % col_block)."""
     M, C, ldk = _rows(k)
-    _check(lib().flexam_rmsnorm_rope_scatter(_ptr(q, BF16), q.stride(0) if q is not None else 0, _ptr(wq, F32), _ptr(k, BF16), ldk,
-                                             _ptr(wk, F32), _ptr(v, BF16), v.stride(0) if v is not None else 0, _ptr(q_out, BF16),
-                                             _ptr(k_out, BF16), _ptr(v_out, BF16), ld_out, out_bs, col_block, block_stride, M, C, eps,
-                                             _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, head_dim,
-                                             _stream()), "flexam_rmsnorm_rope_scatter")
+    _call("flexam_rmsnorm_rope_scatter", _ptr(q, BF16), q.stride(0) if q is not None else 0, _ptr(wq, F32), _ptr(k, BF16), ldk,
+          _ptr(wk, F32), _ptr(v, BF16), v.stride(0) if v is not None else 0, _ptr(q_out, BF16), _ptr(k_out, BF16), _ptr(v_out, BF16),
+          ld_out, out_bs, col_block, block_stride, M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset,
+          head_dim)
 
 
 def mod_table(mod, e, out, rows_per_batch, scale_mask, mdens=None, dens=None, dens_slots=-1):
@@ -824,8 +712,8 @@ def mod_table(mod, e, out, rows_per_batch, scale_mask, mdens=None, dens=None, de
     for t in (mod, e, out, mdens, dens):
         if t is not None and not t.is_contiguous():
             raise RuntimeError("mod_table: tensors must be contiguous")
-    _check(lib().flexam_mod_table(_ptr(mod, F32), _ptr(e, F32), _ptr(mdens, F32), _ptr(dens, F32), _ptr(out, F32), nblk, R, nj,
-                                  nslot, C, rows_per_batch, scale_mask, dens_slots, _stream()), "flexam_mod_table")
+    _call("flexam_mod_table", _ptr(mod, F32), _ptr(e, F32), _ptr(mdens, F32), _ptr(dens, F32), _ptr(out, F32), nblk, R, nj, nslot, C,
+          rows_per_batch, scale_mask, dens_slots)
     return out
 
 
@@ -839,9 +727,8 @@ def small_linear(x, w, b=None, silu_in=False, out=None):
         out = torch.empty(M, N, device=x.device, dtype=F32)
     if w.dtype not in (BF16, F32):
         raise RuntimeError("small_linear: weight must be bf16 or fp32")
-    _check(lib().flexam_small_linear_f32(_ptr(x, F32), ldx, _ptr(w), 1 if w.dtype == BF16 else 0, ldw, _ptr(b, F32),
-                                         _ptr(out, F32), out.stride(0), M, N, K, 1 if silu_in else 0, _stream()),
-           "flexam_small_linear_f32")
+    _call("flexam_small_linear_f32", _ptr(x, F32), ldx, _ptr(w), 1 if w.dtype == BF16 else 0, ldw, _ptr(b, F32), _ptr(out, F32),
+          out.stride(0), M, N, K, 1 if silu_in else 0)
     return out
 
 
@@ -849,7 +736,7 @@ def sinusoid_embed(t, dim, out=None):
     R = t.numel()
     if out is None:
         out = torch.empty(R, dim, device=t.device, dtype=F32)
-    _check(lib().flexam_sinusoid_embed(_ptr(t.contiguous(), F32), _ptr(out, F32), R, dim, _stream()), "flexam_sinusoid_embed")
+    _call("flexam_sinusoid_embed", _ptr(t.contiguous(), F32), _ptr(out, F32), R, dim)
     return out
 
 
@@ -858,24 +745,21 @@ def patchify(src, dst, col0=0, row0=0):
     C, F, H, W = src.shape
     if not src.is_contiguous():
         raise RuntimeError("patchify: src must be contiguous")
-    _check(lib().flexam_patchify(_ptr(src), 1 if src.dtype == BF16 else 0, C, F, H, W, _ptr(dst, BF16), dst.stride(0), col0, row0,
-                                 _stream()), "flexam_patchify")
+    _call("flexam_patchify", _ptr(src), 1 if src.dtype == BF16 else 0, C, F, H, W, _ptr(dst, BF16), dst.stride(0), col0, row0)
     return dst
 
 
 def unpatchify(tok, tok0, C, F, H, W, out=None, dtype=F32):
     if out is None:
         out = torch.empty(C, F, H, W, device=tok.device, dtype=dtype)
-    _check(lib().flexam_unpatchify(_ptr(tok, F32), tok.stride(0), tok0, C, F, H, W, _ptr(out), 1 if out.dtype == BF16 else 0,
-                                   _stream()), "flexam_unpatchify")
+    _call("flexam_unpatchify", _ptr(tok, F32), tok.stride(0), tok0, C, F, H, W, _ptr(out), 1 if out.dtype == BF16 else 0)
     return out
 
 
 def cfg_euler_blend(tok_uncond, tok_cond, tok0, guidance, dt, latents, known=None, mask=None):
     C, F, H, W = latents.shape
-    _check(lib().flexam_cfg_euler_blend(_ptr(tok_uncond, F32), _ptr(tok_cond, F32), tok_uncond.stride(0), tok0, guidance, dt,
-                                        _ptr(latents, F32), _ptr(known, F32), _ptr(mask, F32), C, F, H, W, _stream()),
-           "flexam_cfg_euler_blend")
+    _call("flexam_cfg_euler_blend", _ptr(tok_uncond, F32), _ptr(tok_cond, F32), tok_uncond.stride(0), tok0, guidance, dt,
+          _ptr(latents, F32), _ptr(known, F32), _ptr(mask, F32), C, F, H, W)
     return latents
 
 
@@ -883,7 +767,7 @@ def axpby(y, a, x, b):
     """y = a*x + b*y (fp32, same shape, contiguous)."""
     if y.shape != x.shape or not y.is_contiguous() or not x.is_contiguous():
         raise RuntimeError("axpby: contiguous tensors of equal shape required")
-    _check(lib().flexam_axpby_f32(_ptr(y, F32), a, _ptr(x, F32), b, y.numel(), _stream()), "flexam_axpby_f32")
+    _call("flexam_axpby_f32", _ptr(y, F32), a, _ptr(x, F32), b, y.numel())
     return y
 
 
@@ -899,15 +783,15 @@ def checksums(tensors):
         return []
     out = torch.zeros(len(ts), 2, device=ts[0].device, dtype=I64)
     for i, t in enumerate(ts):
-        _check(lib().flexam_checksum(_ptr(t), t.numel() * t.element_size(), out[i].data_ptr(), _stream()), "flexam_checksum")
+        _call("flexam_checksum", _ptr(t), t.numel() * t.element_size(), out[i].data_ptr())
     return [tuple(r) for r in out.tolist()]
 
 
 def cfg_velocity(tok_uncond, tok_cond, tok0, guidance, out):
     """out [C,F,H,W] fp32 = unpatchify(u + g (c - u)); tok_cond None: out = unpatchify(u)."""
     C, F, H, W = out.shape
-    _check(lib().flexam_cfg_velocity(_ptr(tok_uncond, F32), _ptr(tok_cond, F32), tok_uncond.stride(0), tok0, guidance, _ptr(out, F32),
-                                     C, F, H, W, _stream()), "flexam_cfg_velocity")
+    _call("flexam_cfg_velocity", _ptr(tok_uncond, F32), _ptr(tok_cond, F32), tok_uncond.stride(0), tok0, guidance, _ptr(out, F32), C, F, H,
+          W)
     return out
 
 
@@ -921,8 +805,7 @@ def lincomb(out, terms):
         raise RuntimeError("lincomb: out must be fp32 contiguous")
     ptrs = (c_void_p * n)(*[t.data_ptr() for _, t in terms])
     coefs = (c_float * n)(*[float(c) for c, _ in terms])
-    _check(lib().flexam_lincomb_f32(_ptr(out, F32), out.numel(), n, ctypes.cast(ptrs, c_void_p), ctypes.cast(coefs, c_void_p),
-                                    _stream()), "flexam_lincomb_f32")
+    _call("flexam_lincomb_f32", _ptr(out, F32), out.numel(), n, ctypes.cast(ptrs, c_void_p), ctypes.cast(coefs, c_void_p))
     return out
 
 
@@ -932,7 +815,7 @@ def mask_blend(x, known, mask):
     fhw = x.numel() // C
     if mask.numel() != fhw or known.shape != x.shape:
         raise RuntimeError("mask_blend: shape mismatch")
-    _check(lib().flexam_mask_blend_f32(_ptr(x, F32), _ptr(known, F32), _ptr(mask, F32), C, fhw, _stream()), "flexam_mask_blend_f32")
+    _call("flexam_mask_blend_f32", _ptr(x, F32), _ptr(known, F32), _ptr(mask, F32), C, fhw)
     return x
 
 
@@ -942,8 +825,7 @@ def pack_cl(src, dst, c0=0):
     C, F, H, W = src.shape
     if not src.is_contiguous() or dst.shape[:3] != (F, H + 2, W + 2) or not dst.is_contiguous():
         raise RuntimeError("pack_cl: bad layout")
-    _check(lib().flexam_pack_cl(_ptr(src), 1 if src.dtype == BF16 else 0, C, F, H, W, _ptr(dst, BF16), dst.shape[3], c0, _stream()),
-           "flexam_pack_cl")
+    _call("flexam_pack_cl", _ptr(src), 1 if src.dtype == BF16 else 0, C, F, H, W, _ptr(dst, BF16), dst.shape[3], c0)
     return dst
 
 
@@ -951,8 +833,7 @@ def unpack_cl(src, C, F, H, W, out=None):
     """src [F*(H+2)*(W+2), ld] (fp32/bf16 rows) -> [C,F,H,W] fp32."""
     if out is None:
         out = torch.empty(C, F, H, W, device=src.device, dtype=F32)
-    _check(lib().flexam_unpack_cl(_ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, F, H, W, _ptr(out, F32), _stream()),
-           "flexam_unpack_cl")
+    _call("flexam_unpack_cl", _ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, F, H, W, _ptr(out, F32))
     return out
 
 
@@ -960,36 +841,33 @@ def groupnorm_silu_cl(x, C, F, H, W, groups, gamma, beta, dst, residual=None, ep
     """x [F*(H+2)*(W+2), ld] fp32 -> dst [F,H+2,W+2,Cp] bf16 interior; residual: bf16 padded image."""
     if stats is None:
         stats = torch.empty(2 * groups, device=x.device, dtype=F32)
-    _check(lib().flexam_groupnorm_silu_cl(_ptr(x, F32), x.stride(0), C, F, H, W, groups, eps, _ptr(gamma, F32), _ptr(beta, F32),
-                                          _ptr(stats, F32), _ptr(residual, BF16), residual.shape[-1] if residual is not None else 0,
-                                          _ptr(dst, BF16), dst.shape[-1], _stream()), "flexam_groupnorm_silu_cl")
+    _call("flexam_groupnorm_silu_cl", _ptr(x, F32), x.stride(0), C, F, H, W, groups, eps, _ptr(gamma, F32), _ptr(beta, F32),
+          _ptr(stats, F32), _ptr(residual, BF16), residual.shape[-1] if residual is not None else 0, _ptr(dst, BF16), dst.shape[-1])
     return dst
 
 
 # ----------------------------------------------------------------------------- VAE decoder helpers
 def vae_prep_cl(src, C, T, H, W, dst, mode=0, gamma=None, t0=0, compact=False):
     """src rows [T*(H+2)*(W+2), ld] (fp32/bf16) -> dst image [*, H+2, W+2, Cp] (frame offset t0) or compact [T*H*W, Cp]."""
-    _check(lib().flexam_vae_prep_cl(_ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, _ptr(gamma, F32), mode,
-                                    _ptr(dst, BF16), dst.shape[-1], t0, 1 if compact else 0, _stream()), "flexam_vae_prep_cl")
+    _call("flexam_vae_prep_cl", _ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, _ptr(gamma, F32), mode,
+          _ptr(dst, BF16), dst.shape[-1], t0, 1 if compact else 0)
     return dst
 
 
 def upsample2x_cl(src, C, T, H, W, dst, interleave=False):
-    _check(lib().flexam_upsample2x_cl(_ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, 1 if interleave else 0,
-                                      _ptr(dst, BF16), dst.shape[-1], _stream()), "flexam_upsample2x_cl")
+    _call("flexam_upsample2x_cl", _ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, 1 if interleave else 0,
+          _ptr(dst, BF16), dst.shape[-1])
     return dst
 
 
 def dupup_add_cl(x_main, Co, To, Ho, Wo, x_in, Ci, ft, drop):
-    _check(lib().flexam_dupup_add_cl(_ptr(x_main, F32), x_main.stride(0), Co, To, Ho, Wo, _ptr(x_in, F32), x_in.stride(0), Ci, ft, drop,
-                                     _stream()), "flexam_dupup_add_cl")
+    _call("flexam_dupup_add_cl", _ptr(x_main, F32), x_main.stride(0), Co, To, Ho, Wo, _ptr(x_in, F32), x_in.stride(0), Ci, ft, drop)
     return x_main
 
 
 def deinterleave_cl(src, C, T, H, W, dst):
     """src rows [T*(H+2)*(W+2), 2C] -> dst padded image [2T, H+2, W+2, Cp]: frame 2t + s = channels [sC, (s+1)C) of frame t."""
-    _check(lib().flexam_deinterleave_cl(_ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, _ptr(dst, BF16), dst.shape[-1],
-                                        _stream()), "flexam_deinterleave_cl")
+    _call("flexam_deinterleave_cl", _ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, _ptr(dst, BF16), dst.shape[-1])
     return dst
 
 
@@ -997,40 +875,36 @@ def phase_dupup_cl(phases, x_main, Co, To, Ho, Wo, x_in, Ci, ft, drop):
     """phases [4, rows of the padded (Ho/2, Wo/2) image, Co] fp32 -> x_main rows of the padded (Ho, Wo) image, + the DupUp3D shortcut of x_in."""
     if phases.dim() != 3 or phases.shape[0] != 4 or phases.stride(2) != 1 or phases.shape[2] != Co:
         raise RuntimeError("phase_dupup_cl: phases must be [4, rows, Co] fp32")
-    _check(lib().flexam_phase_dupup_cl(_ptr(phases, F32), phases.stride(1), phases.stride(0), _ptr(x_main, F32), x_main.stride(0), Co, To, Ho, Wo,
-                                       _ptr(x_in, F32), x_in.stride(0), Ci, ft, drop, _stream()), "flexam_phase_dupup_cl")
+    _call("flexam_phase_dupup_cl", _ptr(phases, F32), phases.stride(1), phases.stride(0), _ptr(x_main, F32), x_main.stride(0), Co, To, Ho,
+          Wo, _ptr(x_in, F32), x_in.stride(0), Ci, ft, drop)
     return x_main
 
 
 def tapsum_cl(y, T, H, W, kt, Co, bias, out):
     """y [(kt - 1 + T) * (H+2) * (W+2), >= kt*9*Co] fp32 per-tap products -> out rows [T * (H+2) * (W+2), Co] fp32 (interior positions)."""
-    _check(lib().flexam_tapsum_cl(_ptr(y, F32), y.stride(0), T, H, W, kt, Co, _ptr(bias, F32), _ptr(out, F32), out.stride(0), _stream()),
-           "flexam_tapsum_cl")
+    _call("flexam_tapsum_cl", _ptr(y, F32), y.stride(0), T, H, W, kt, Co, _ptr(bias, F32), _ptr(out, F32), out.stride(0))
     return out
 
 
 def softmax_rows(s, scale, out, n_valid):
     M = s.shape[0]
-    _check(lib().flexam_softmax_rows(_ptr(s, F32), s.stride(0), M, n_valid, scale, _ptr(out, BF16), out.stride(0), out.shape[1], _stream()),
-           "flexam_softmax_rows")
+    _call("flexam_softmax_rows", _ptr(s, F32), s.stride(0), M, n_valid, scale, _ptr(out, BF16), out.stride(0), out.shape[1])
     return out
 
 
 def scatter_add_cl(x, y, C, T, H, W):
-    _check(lib().flexam_scatter_add_cl(_ptr(x, F32), x.stride(0), _ptr(y, BF16), y.stride(0), C, T, H, W, _stream()), "flexam_scatter_add_cl")
+    _call("flexam_scatter_add_cl", _ptr(x, F32), x.stride(0), _ptr(y, BF16), y.stride(0), C, T, H, W)
     return x
 
 
 def vae_unpatchify_clamp(src, T, H, W, video, f0, lo=-1.0, hi=1.0):
-    _check(lib().flexam_vae_unpatchify_clamp(_ptr(src, F32), src.stride(0), T, H, W, _ptr(video, F32), video.shape[1], f0, lo, hi, _stream()),
-           "flexam_vae_unpatchify_clamp")
+    _call("flexam_vae_unpatchify_clamp", _ptr(src, F32), src.stride(0), T, H, W, _ptr(video, F32), video.shape[1], f0, lo, hi)
     return video
 
 
 def pack_affine_cl(src, mul, add, dst):
     C, T, H, W = src.shape
-    _check(lib().flexam_pack_affine_cl(_ptr(src.contiguous(), F32), C, T, H, W, _ptr(mul, F32), _ptr(add, F32), _ptr(dst, BF16),
-                                       dst.shape[-1], _stream()), "flexam_pack_affine_cl")
+    _call("flexam_pack_affine_cl", _ptr(src.contiguous(), F32), C, T, H, W, _ptr(mul, F32), _ptr(add, F32), _ptr(dst, BF16), dst.shape[-1])
     return dst
 
 
@@ -1038,21 +912,18 @@ def pack_affine_cl(src, mul, add, dst):
 def vae_patchify_cl(video, f0, T, dst, t0=0):
     """video [3, Ftot, 2H, 2W] fp32 frames f0..f0+T -> dst image [*, H+2, W+2, Cp] frames t0.., 12 channels (c r q)."""
     _, ftot, h2, w2 = video.shape
-    _check(lib().flexam_vae_patchify_cl(_ptr(video, F32), ftot, f0, T, h2 // 2, w2 // 2, _ptr(dst, BF16), dst.shape[-1], t0, _stream()),
-           "flexam_vae_patchify_cl")
+    _call("flexam_vae_patchify_cl", _ptr(video, F32), ftot, f0, T, h2 // 2, w2 // 2, _ptr(dst, BF16), dst.shape[-1], t0)
     return dst
 
 
 def space_to_depth_cl(src, C, T, H, W, dst, Cs, t0=0):
     """src rows [T*(H+2)*(W+2), ld] -> dst image [*, H/2+2, W/2+2, 4*Cs]."""
-    _check(lib().flexam_space_to_depth_cl(_ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, _ptr(dst, BF16), Cs, t0,
-                                          _stream()), "flexam_space_to_depth_cl")
+    _call("flexam_space_to_depth_cl", _ptr(src), 1 if src.dtype == BF16 else 0, src.stride(0), C, T, H, W, _ptr(dst, BF16), Cs, t0)
     return dst
 
 
 def avgdown_add_cl(x_main, Co, To, Ho, Wo, x_in, Ci, Ti, ft, fs):
-    _check(lib().flexam_avgdown_add_cl(_ptr(x_main, F32), x_main.stride(0), Co, To, Ho, Wo, _ptr(x_in, F32), x_in.stride(0), Ci, Ti, ft, fs,
-                                       _stream()), "flexam_avgdown_add_cl")
+    _call("flexam_avgdown_add_cl", _ptr(x_main, F32), x_main.stride(0), Co, To, Ho, Wo, _ptr(x_in, F32), x_in.stride(0), Ci, Ti, ft, fs)
     return x_main
 
 
@@ -1060,8 +931,7 @@ def avgdown_add_cl(x_main, Co, To, Ho, Wo, x_in, Ci, Ti, ft, fs):
 def t5_norm(x, w, out, eps=1e-6):
     """x [M, C] fp32 rows -> out [M, C] (bf16 or fp32) = w * x * rsqrt(mean(x^2) + eps)."""
     M, C, ldx = _rows(x)
-    _check(lib().flexam_t5_norm(_ptr(x, F32), ldx, M, C, eps, _ptr(w, F32), _ptr(out), out.stride(0), 1 if out.dtype == F32 else 0,
-                                _stream()), "flexam_t5_norm")
+    _call("flexam_t5_norm", _ptr(x, F32), ldx, M, C, eps, _ptr(w, F32), _ptr(out), out.stride(0), 1 if out.dtype == F32 else 0)
     return out
 
 
@@ -1069,9 +939,8 @@ def softmax_bias_rows(s, out, n_valid, scale=1.0, bias=None, key_mask=None):
     """out [M, Npad] bf16 = softmax(scale * s[:, :n_valid] + bias) over keys with key_mask != 0 (uniform over the n_valid keys when
     every key is masked, as in the reference); columns n_valid .. Npad are 0."""
     M = s.shape[0]
-    _check(lib().flexam_softmax_bias_rows(_ptr(s, F32), s.stride(0), M, n_valid, scale, _ptr(bias, F32), bias.stride(0) if bias is not None else 0,
-                                          _ptr(key_mask, F32), _ptr(out, BF16), out.stride(0), out.shape[1], _stream()),
-           "flexam_softmax_bias_rows")
+    _call("flexam_softmax_bias_rows", _ptr(s, F32), s.stride(0), M, n_valid, scale, _ptr(bias, F32),
+          bias.stride(0) if bias is not None else 0, _ptr(key_mask, F32), _ptr(out, BF16), out.stride(0), out.shape[1])
     return out
 
 
@@ -1080,7 +949,7 @@ def mul_bf16(a, b, out=None):
         out = torch.empty_like(a)
     if a.shape != b.shape or not (a.is_contiguous() and b.is_contiguous() and out.is_contiguous()):
         raise RuntimeError("mul_bf16: contiguous bf16 tensors of equal shape required")
-    _check(lib().flexam_mul_bf16(_ptr(a, BF16), _ptr(b, BF16), _ptr(out, BF16), a.numel(), _stream()), "flexam_mul_bf16")
+    _call("flexam_mul_bf16", _ptr(a, BF16), _ptr(b, BF16), _ptr(out, BF16), a.numel())
     return out
 
 
@@ -1102,8 +971,7 @@ def raster_keys(points, visible, height, width, half, y_min=0, mask=None, keys=N
         keys = torch.empty(T, height, width, device=points.device, dtype=torch.int64)
     elif keys.shape != (T, height, width) or keys.dtype != torch.int64 or not keys.is_contiguous():
         raise RuntimeError("raster_keys: keys must be a contiguous int64 [T, H, W] buffer")
-    _check(lib().flexam_raster_keys(_ptr(points, F32), _ptr(visible, U8), T, N, height, width, half, y_min, _ptr(mask, F32), _ptr(keys), _stream()),
-           "flexam_raster_keys")
+    _call("flexam_raster_keys", _ptr(points, F32), _ptr(visible, U8), T, N, height, width, half, y_min, _ptr(mask, F32), _ptr(keys))
     keys.raster_points = N                         # the point count these keys index: raster_resolve holds its colour table to it
     return keys
 
@@ -1129,8 +997,7 @@ def raster_resolve(keys, colors, out_u8=None, out_f32=None, want_u8=False, want_
     for o, shp in ((out_u8, (T, H, W, 3)), (out_f32, (3, T, H, W))):
         if o is not None and (tuple(o.shape) != shp or not o.is_contiguous()):
             raise RuntimeError(f"raster_resolve: output must be contiguous {shp}, got {tuple(o.shape)}")
-    _check(lib().flexam_raster_resolve(_ptr(keys, torch.int64), _ptr(colors, U8), stride, N, T, H, W, _ptr(out_u8, U8), _ptr(out_f32, F32), _stream()),
-           "flexam_raster_resolve")
+    _call("flexam_raster_resolve", _ptr(keys, torch.int64), _ptr(colors, U8), stride, N, T, H, W, _ptr(out_u8, U8), _ptr(out_f32, F32))
     return out_u8, out_f32
 
 
@@ -1155,8 +1022,7 @@ def edit_mask_blur(src, weights, out=None):
     elif tuple(out.shape) != (n, H, W) or out.dtype != U8 or not out.is_contiguous():
         raise RuntimeError(f"edit_mask_blur: out must be contiguous uint8 {(n, H, W)}")
     tmp = torch.empty(n, H, W, device=src.device, dtype=F32)
-    _check(lib().flexam_edit_mask_blur(_ptr(src, U8), n, H, W, _ptr(weights, torch.float64), weights.numel() - 1, _ptr(tmp, F32),
-                                       _ptr(out, U8), _stream()), "flexam_edit_mask_blur")
+    _call("flexam_edit_mask_blur", _ptr(src, U8), n, H, W, _ptr(weights, torch.float64), weights.numel() - 1, _ptr(tmp, F32), _ptr(out, U8))
     return out
 
 
@@ -1169,8 +1035,7 @@ def edit_mask_hull(binary):
     nruns = torch.empty(n, H, device=binary.device, dtype=torch.int32)
     slots = min(n, EDIT_MASK_SLOTS)
     ws = torch.empty(slots, 5, H, S, device=binary.device, dtype=torch.int32)
-    _check(lib().flexam_edit_mask_hull(_ptr(binary, U8), n, H, W, _ptr(runs, torch.int32), _ptr(nruns, torch.int32), _raw(ws), slots,
-                                       _stream()), "flexam_edit_mask_hull")
+    _call("flexam_edit_mask_hull", _ptr(binary, U8), n, H, W, _ptr(runs, torch.int32), _ptr(nruns, torch.int32), _raw(ws), slots)
     return runs, nruns
 
 
@@ -1188,6 +1053,6 @@ def edit_mask_dilate(runs, nruns, width, half_widths, out=None):
         out = torch.empty(n, H, width, device=runs.device, dtype=U8)
     elif tuple(out.shape) != (n, H, width) or out.dtype != U8 or not out.is_contiguous():
         raise RuntimeError(f"edit_mask_dilate: out must be contiguous uint8 {(n, H, width)}")
-    _check(lib().flexam_edit_mask_dilate(_ptr(runs, torch.int32), _ptr(nruns, torch.int32), n, H, width, _ptr(half_widths, torch.int32),
-                                         half_widths.numel() - 1, _ptr(out, U8), _stream()), "flexam_edit_mask_dilate")
+    _call("flexam_edit_mask_dilate", _ptr(runs, torch.int32), _ptr(nruns, torch.int32), n, H, width, _ptr(half_widths, torch.int32),
+          half_widths.numel() - 1, _ptr(out, U8))
     return out

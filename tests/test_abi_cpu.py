@@ -134,3 +134,89 @@ def test_recorder_builds_the_words_the_call_was_made_with(libpath, monkeypatch):
     assert (seg[0].a[0].p, seg[0].a[1].f, seg[0].a[2].p, seg[0].a[3].f, seg[0].a[4].i) == (4096, 1.5, 8192, -2.0, 77)
     seg2 = plan.items[2][1]
     assert (seg2[0].a[0].p, seg2[0].a[1].f, seg2[0].a[4].i) == (16, 0.25, 5)
+
+
+def test_binding_is_derived_from_the_header_type_for_type():
+    """hip._SIGNATURES comes from flexam_amd/abi.py's parse of the header.  Literal expectations for entry points that together cover
+    the whole type vocabulary and the awkward spots (24 mixed arguments, adjacent floats, `const char*` in and out, no parameters)."""
+    from ctypes import c_char_p, c_float as F, c_int as I, c_int64 as L, c_void_p as P
+    from flexam_amd import hip
+    want = {
+        "flexam_rmsnorm_rope_scatter": ([P, L, P, P, L, P, P, L, P, P, P, L, L, I, L, L, I, F, P, P, L, L, I, P], I),
+        "flexam_attn_fwd_lastkey": ([P, L, L, P, L, L, P, L, L, P, L, L, I, I, I, I, I, F, F, P], I),
+        "flexam_axpby_f32": ([P, F, P, F, L, P], I),
+        "flexam_fn_id": ([c_char_p], I),
+        "flexam_fn_name": ([I], c_char_p),
+        "flexam_last_error": ([], c_char_p),
+        "flexam_version": ([], I),
+        "flexam_replay": ([P, L, P, P], I),
+    }
+    for name, sig in want.items():
+        assert hip._SIGNATURES[name] == sig, name
+    assert (hip._P, hip._I, hip._L, hip._F) == (P, I, L, F)
+
+
+def test_int_and_int64_positions_follow_the_header():
+    """A c_int where the header says int64_t truncates a stride without failing: for every entry point, the positions the header types
+    `int64_t` are c_int64 in the binding and the `int` ones c_int -- read from the header text here, not through the parser."""
+    from ctypes import c_int, c_int64
+    from flexam_amd import hip
+    text = re.sub(r"/\*.*?\*/", " ", open(os.path.join(ROOT, "include", "flexam_hip.h")).read(), flags=re.S)
+    found = re.findall(r"\b(flexam_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)
+    assert [n for n, _ in found] == list(hip._SIGNATURES), "binding keys are the header's prototypes, in header order"
+    n64 = n32 = 0
+    for name, params in found:
+        params = [" ".join(p.split()) for p in params.split(",")] if params.strip() not in ("", "void") else []
+        argtypes = hip._SIGNATURES[name][0]
+        assert len(argtypes) == len(params), name
+        for j, prm in enumerate(params):
+            if re.fullmatch(r"int64_t \w+", prm):
+                assert argtypes[j] is c_int64, (name, j, prm)
+                n64 += 1
+            elif re.fullmatch(r"int \w+", prm):
+                assert argtypes[j] is c_int, (name, j, prm)
+                n32 += 1
+            else:
+                assert argtypes[j] not in (c_int, c_int64), (name, j, prm)
+    assert n64 >= 150 and n32 >= 200, (n64, n32)
+
+
+@pytest.mark.parametrize("proto", ["int flexam_bad(double x, void* stream);", "int flexam_bad(const void* p, unsigned n);",
+                                   "int flexam_bad(size_t n);", "int flexam_bad(flexam_arg a, void* stream);",
+                                   "int flexam_bad(const int n);", "int flexam_bad(int32_t n);", "int flexam_bad(int);",
+                                   "double flexam_bad(int n);", "void* flexam_bad(void);", "int64_t flexam_bad(void);",
+                                   "int flexam_bad(int (*cb)(int), void* stream);"])
+def test_parser_refuses_types_outside_the_vocabulary(proto):
+    """The vocabulary is closed (int, int64_t, float, const char*, pointers; int or const char* returned): anything else raises with
+    the function's name instead of falling back to some ctypes default."""
+    from flexam_amd import abi
+    ok = "int flexam_ok(const float* const* t, int64_t n, float f, const char* s, void* stream);\n"
+    assert [n for n, _, _ in abi.prototypes(ok)] == ["flexam_ok"]
+    with pytest.raises(ValueError, match="flexam_bad"):
+        abi.prototypes(ok + proto)
+
+
+def test_header_constants_are_read_not_evaluated():
+    from flexam_amd import abi, hip
+    c = abi.constants("#define A 3\n#define B (-2)\n#define C (-1.0f)\n#define D (256 * 262144)  /* note */\n#define GUARD\n")
+    assert c == {"A": 3, "B": -2, "C": -1.0, "D": 67108864} and isinstance(c["C"], float) and isinstance(c["D"], int)
+    for bad in ("#define X (1 << 20)", "#define X sizeof(int)", "#define X 1.0", "#define X (2 + 2)", "#define X Y"):
+        with pytest.raises(ValueError, match="X"):
+            abi.constants(bad + "\n")
+    assert (hip.EPI_NONE, hip.EPI_GELU_TANH, hip.GEMM_WS_BYTES, hip.REPLAY_MAX_ARGS, hip.ATTN_PRESCALED) == (0, 1, 64 << 20, 26, -1.0)
+    assert abi.CONSTANTS["FLEXAM_E_ARG"] == -1 and abi.CONSTANTS["FLEXAM_HIP_VERSION"] == 2
+
+
+def test_recorder_takes_recordable_from_the_header(libpath):
+    """What a recorder records is what the generator makes replayable -- the header's stream-ordered prototypes -- except
+    flexam_lincomb_f32, which reads host arrays during the call."""
+    from flexam_amd import abi, gen_replay, hip
+    header = open(abi.HEADER).read()
+    assert hip._REPLAYABLE == set(gen_replay.arg_kinds(header)) and hip._STREAM_ORDERED == hip._REPLAYABLE | {"flexam_replay"}
+    assert hip._NOT_RECORDABLE == ("flexam_lincomb_f32",) and "flexam_lincomb_f32" in hip._REPLAYABLE
+    lib = hip.load_library(libpath)
+    with hip.record():
+        with pytest.raises(RuntimeError, match="host arrays"):
+            hip.lib().flexam_lincomb_f32
+        assert hip.lib().flexam_device_cus is lib.flexam_device_cus and hip.lib().flexam_replay is lib.flexam_replay
+        assert hip.lib().flexam_mul_bf16 is not lib.flexam_mul_bf16
