@@ -6,7 +6,8 @@ Exports the reference's names (FlexAM/models/__init__.py, FlexAM/pipeline/__init
     Wan2_2FunControlPipeline_FlexAM, attention
 and, for the step in front of the sampler, `visualize_tracking_DELTA` (pipelines.py:1852: tracks -> conditioning videos), and the
 qfloat8 helpers of FlexAM/utils/fp8_optimization.py (`convert_model_weight_to_float8`, `convert_weight_dtype_wrapper`, ...), and
-demo.py's edit masks (`generate_mask_fg_tracking_for_validation`, `generate_mask_bg_tracking_for_validation`).
+demo.py's edit masks (`generate_mask_fg_tracking_for_validation`, `generate_mask_bg_tracking_for_validation`), and the edit tracks
+of pipelines.py (`CameraMotionGenerator`, `ObjectMotionGenerator`, `convert_moge_to_delta_format`; `moge_tracks` fuses demo.py:222-266).
 Arithmetic runs in libflexam_hip.so (hand-written gfx950 HIP kernels, C ABI in
 include/flexam_hip.h); this package is the host-side mirror of the reference interface.
 """
@@ -14,7 +15,8 @@ __all__ = ["Wan2_2Transformer3DModel_FlexAM", "WanTransformer3DModel_FlexAM", "A
            "Wan2_2FunControlPipeline_FlexAM", "FlowMatchEulerDiscreteScheduler", "FlowUniPCMultistepScheduler",
            "FlowDPMSolverMultistepScheduler", "WanT5EncoderModel", "attention", "visualize_tracking_DELTA",
            "replace_parameters_by_name", "convert_model_weight_to_float8", "autocast_model_forward", "convert_weight_dtype_wrapper",
-           "generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation"]
+           "generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation",
+           "CameraMotionGenerator", "ObjectMotionGenerator", "convert_moge_to_delta_format", "moge_tracks"]
 
 
 def __getattr__(name):
@@ -51,5 +53,8 @@ def __getattr__(name):
         return visualize_tracking_DELTA
     if name in ("generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation"):
         from . import edit_masks as m
+        return getattr(m, name)
+    if name in ("CameraMotionGenerator", "ObjectMotionGenerator", "convert_moge_to_delta_format", "moge_tracks"):
+        from . import motion as m
         return getattr(m, name)
     raise AttributeError(name)

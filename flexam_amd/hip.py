@@ -1056,3 +1056,121 @@ def edit_mask_dilate(runs, nruns, width, half_widths, out=None):
     _call("flexam_edit_mask_dilate", _ptr(runs, torch.int32), _ptr(nruns, torch.int32), n, H, width, _ptr(half_widths, torch.int32),
           half_widths.numel() - 1, _ptr(out, U8))
     return out
+
+
+# ----------------------------------------------------------------------------- edit tracks: camera / object motion (csrc/motion.hip)
+MOTION_CHUNK = abi.CONSTANTS["FLEXAM_MOTION_CHUNK"]
+F64 = torch.float64
+
+
+def _points3(t, what, dims=(2, 3), dtypes=(F32,)):
+    if t.dim() not in dims or t.shape[-1] != 3 or t.dtype not in dtypes or not t.is_contiguous():
+        raise RuntimeError(f"{what}: contiguous points [..., 3] of {dtypes} required, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _bytes_mask(m, shape, what):
+    if m.dtype == torch.bool:
+        m = m.view(U8)
+    if m.dtype != U8 or tuple(m.shape) != tuple(shape) or not m.is_contiguous():
+        raise RuntimeError(f"{what}: contiguous bool / uint8 mask {tuple(shape)} required, got {tuple(m.shape)} {m.dtype}")
+    return m
+
+
+def _motion_select(name, points, mask, extra):
+    n = points.shape[0]
+    flags = torch.empty(n, device=points.device, dtype=U8)
+    ws = torch.empty(4 * ((n + MOTION_CHUNK - 1) // MOTION_CHUNK), device=points.device, dtype=F64)
+    sums = torch.empty(4, device=points.device, dtype=F64)
+    _call(name, _ptr(points, F32), n, _ptr(mask, U8), *extra, _ptr(flags, U8), _raw(ws), ws.numel() * 8, _ptr(sums, F64))
+    return flags.view(torch.bool), sums
+
+
+def motion_select_map(points, mask):
+    """points [N, 3] fp32, mask [N] bool -> (flags [N] bool = mask & no NaN coordinate, sums [4] fp64 = sum x, y, z and the number of the
+    flagged points, in a fixed summation order)."""
+    _points3(points, "motion_select_map", dims=(2,))
+    return _motion_select("flexam_motion_select_map", points, _bytes_mask(mask, (points.shape[0],), "motion_select_map"), ())
+
+
+def motion_select_pixels(points, mask):
+    """points [N, 3] fp32 (first-frame pixel positions), mask [Hm, Wm] bool -> (flags [N] = the mask at the rounded, clamped positions, sums)."""
+    _points3(points, "motion_select_pixels", dims=(2,))
+    if mask.dim() != 2:
+        raise RuntimeError(f"motion_select_pixels: mask [Hm, Wm] required, got {tuple(mask.shape)}")
+    return _motion_select("flexam_motion_select_pixels", points, _bytes_mask(mask, mask.shape, "motion_select_pixels"), tuple(mask.shape))
+
+
+def motion_compact(mask):
+    """mask [N] bool -> (index [N] int32 whose first `count` entries are the set positions in ascending order, count [1] int32), both on the device."""
+    if mask.dim() != 1:
+        raise RuntimeError(f"motion_compact: mask [N] required, got {tuple(mask.shape)}")
+    mask = _bytes_mask(mask, mask.shape, "motion_compact")
+    n = mask.numel()
+    index = torch.empty(n, device=mask.device, dtype=I32)
+    count = torch.empty(1, device=mask.device, dtype=I32)
+    ws = torch.empty((n + MOTION_CHUNK - 1) // MOTION_CHUNK, device=mask.device, dtype=I32)
+    _call("flexam_motion_compact", _ptr(mask, U8), n, _ptr(index, I32), _ptr(count, I32), _raw(ws), ws.numel() * 4)
+    return index, count
+
+
+def _rows34(m, T, rows, cols, dtype, what):
+    if m is None:
+        return None
+    if tuple(m.shape) != (T, rows, cols) or m.dtype != dtype or not m.is_contiguous():
+        raise RuntimeError(f"{what}: contiguous {dtype} [{T}, {rows}, {cols}] required, got {tuple(m.shape)} {m.dtype}")
+    return m
+
+
+def motion_transform(src, T, flags=None, motion=None, pose=None, intr=None, scale=(1.0, 1.0), index=None, count=None, out=None):
+    """src [T, N, 3] or [N, 3] (one map for all T frames) fp32 -> out [T, M, 3]: object affine motion [T, 3, 4] on the flagged points (all
+    when flags is None), camera pose [T, 3, 4] + intrinsics [3, 3] + perspective division, (u, v) scale, gathered through index[:count]
+    (M = count; without an index M = N).  See flexam_motion_transform_f32."""
+    _points3(src, "motion_transform")
+    n = src.shape[-2]
+    stride = 0 if src.dim() == 2 else n * 3
+    if src.dim() == 3 and src.shape[0] != T:
+        raise RuntimeError(f"motion_transform: {src.shape[0]} source frames for T = {T}")
+    if flags is not None:
+        flags = _bytes_mask(flags, (n,), "motion_transform")
+    motion = _rows34(motion, T, 3, 4, F32, "motion_transform: motion")
+    pose = _rows34(pose, T, 3, 4, F32, "motion_transform: pose")
+    if intr is not None and (tuple(intr.shape) != (3, 3) or intr.dtype != F32 or not intr.is_contiguous()):
+        raise RuntimeError(f"motion_transform: intr must be contiguous fp32 [3, 3], got {tuple(intr.shape)} {intr.dtype}")
+    if index is not None and (index.dtype != I32 or index.dim() != 1 or index.numel() < count or not index.is_contiguous()):
+        raise RuntimeError("motion_transform: index must be a contiguous int32 vector of at least `count` entries")
+    m = n if index is None else int(count)
+    if out is None:
+        out = torch.empty(T, m, 3, device=src.device, dtype=F32)
+    elif tuple(out.shape) != (T, m, 3) or out.dtype != F32 or not out.is_contiguous():
+        raise RuntimeError(f"motion_transform: out must be contiguous fp32 {(T, m, 3)}")
+    if m == 0:
+        return out
+    _call("flexam_motion_transform_f32", _ptr(src, F32), stride, T, n, _ptr(flags, U8), _ptr(motion, F32), _ptr(pose, F32), _ptr(intr, F32),
+          float(scale[0]), float(scale[1]), _ptr(index, I32), m, _ptr(out, F32))
+    return out
+
+
+def motion_unproject(points, kinv, rinv, tvec):
+    """s2w_vggt's point arithmetic: points [T, N, 3] fp32 or fp64 (u, v, z), kinv / rinv [T, 3, 3], tvec [T, 3] fp64 -> world points in the
+    dtype of `points` (computed in double); z <= 0 gives zeros."""
+    _points3(points, "motion_unproject", dims=(3,), dtypes=(F32, F64))
+    T, n, _ = points.shape
+    _rows34(kinv, T, 3, 3, F64, "motion_unproject: kinv")
+    _rows34(rinv, T, 3, 3, F64, "motion_unproject: rinv")
+    if tuple(tvec.shape) != (T, 3) or tvec.dtype != F64 or not tvec.is_contiguous():
+        raise RuntimeError(f"motion_unproject: tvec must be contiguous fp64 {(T, 3)}")
+    out = torch.empty_like(points)
+    _call("flexam_motion_unproject_f64", _ptr(points), int(points.dtype == F32), T, n, _ptr(kinv, F64), _ptr(rinv, F64), _ptr(tvec, F64), _ptr(out))
+    return out
+
+
+def motion_project(points, pose, intr):
+    """w2s_vggt's point arithmetic: world points [T, N, 3] fp32 or fp64, pose [T, 3, 4], intr [T, 3, 3] fp64 -> (u, v, depth) fp64; depth <= 0 gives zeros."""
+    _points3(points, "motion_project", dims=(3,), dtypes=(F32, F64))
+    T, n, _ = points.shape
+    _rows34(pose, T, 3, 4, F64, "motion_project: pose")
+    _rows34(intr, T, 3, 3, F64, "motion_project: intr")
+    out = torch.empty(T, n, 3, device=points.device, dtype=F64)
+    _call("flexam_motion_project_f64", _ptr(points), int(points.dtype == F32), T, n, _ptr(pose, F64), _ptr(intr, F64), _ptr(out, F64))
+    return out

@@ -424,6 +424,42 @@ int flexam_edit_mask_hull(const unsigned char* bin, int n, int H, int W, unsigne
 int flexam_edit_mask_dilate(const unsigned* runs, const int* nruns, int n, int H, int W, const int* half_widths, int radius, unsigned char* out,
                             void* stream);
 
+/* Edit tracks: camera and object motion on the 3-D tracks (flexam_amd/motion.py; csrc/motion.hip).  Replaces the per-point half of
+ * pipelines.py:195-850 CameraMotionGenerator (w2s_moge :512-530, s2w_vggt :356-417, w2s_vggt :419-510), :852-1038 ObjectMotionGenerator
+ * (_get_points_in_mask :857-876, apply_motion :937-945, 1010-1038) and :1255-1291 convert_moge_to_delta_format, i.e. demo.py:216-358;
+ * the [T, 4, 4] matrices are made on the host and arrive as device arrays of their first three rows.  Points are (x, y, z) triples.
+ * motion_select_map:    flags[n] = mask[n] != 0 and no coordinate of points[n] is NaN (:939).
+ * motion_select_pixels: flags[n] = mask[clamp(round(y_n), 0, mask_h - 1)][clamp(round(x_n), 0, mask_w - 1)] != 0, halves rounded to even,
+ *   NaN -> 0 (:867-874); points = the first frame [N, 3].
+ *   Both also leave sums[0..2] = the sums of the selected points' x, y, z and sums[3] = their number, accumulated in double in a fixed
+ *   order (one partial per FLEXAM_MOTION_CHUNK points, combined by index): the same bits on every run.  ws: 32 bytes per started chunk.
+ * motion_compact: index[0 .. *count) = the positions n with mask[n] != 0, ascending (the order of a boolean-mask gather, :1282); the
+ *   rest of index [N] is left alone.  ws: 4 bytes per started chunk.  N < 2^31.
+ * motion_transform_f32: out[t][m] for t < T, m < M from source point n = index[m] (index NULL: n = m, M == N) of frame t (src +
+ *   t * src_frame_stride floats; stride 0 = one [N, 3] map for all frames), in this order, each step rounded to float32 (k = 0..3 fmaf chain):
+ *     motion != NULL and (flags == NULL or flags[n]):  p = motion[t] (p, 1)                     (motion [T][3][4])
+ *     pose != NULL (then intr != NULL):                 c = pose[t] (p, 1); h = intr c; p = (h_x / h_z, h_y / h_z, c_z)   (pose [T][3][4], intr [3][3])
+ *     p = (p_x * scale_u, p_y * scale_v, p_z)
+ *   A fused call gives the bits of the same steps run as separate calls.
+ * motion_unproject_f64 (s2w_vggt): out[t][n] = rinv[t] (kinv[t] (u, v, 1) * z - tvec[t]) where z > 0, else (0, 0, 0); points and out
+ *   [T, N, 3] are both float32 (points_f32 != 0: computed in double, rounded once) or both double; kinv, rinv [T][3][3], tvec [T][3] double.
+ * motion_project_f64 (w2s_vggt): c = pose[t] (p, 1); out[t][n] = (intr[t] (c / (c_z + 1e-10)))_xy, c_z where c_z > 0, else (0, 0, 0);
+ *   points float32 or double, out double; pose [T][3][4], intr [T][3][3] double.
+ * double pointers must be 8-byte, float / int pointers 4-byte aligned. */
+#define FLEXAM_MOTION_CHUNK 1024
+int flexam_motion_select_map(const float* points, int64_t N, const unsigned char* mask, unsigned char* flags, double* ws, int64_t ws_bytes,
+                             double* sums, void* stream);
+int flexam_motion_select_pixels(const float* points, int64_t N, const unsigned char* mask, int mask_h, int mask_w, unsigned char* flags,
+                                double* ws, int64_t ws_bytes, double* sums, void* stream);
+int flexam_motion_compact(const unsigned char* mask, int64_t N, int* index, int* count, int* ws, int64_t ws_bytes, void* stream);
+int flexam_motion_transform_f32(const float* src, int64_t src_frame_stride, int T, int64_t N, const unsigned char* flags, const float* motion,
+                                const float* pose, const float* intr, float scale_u, float scale_v, const int* index, int64_t M, float* out,
+                                void* stream);
+int flexam_motion_unproject_f64(const void* points, int points_f32, int T, int64_t N, const double* kinv, const double* rinv,
+                                const double* tvec, void* out, void* stream);
+int flexam_motion_project_f64(const void* points, int points_f32, int T, int64_t N, const double* pose, const double* intr, double* out,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
