@@ -7,11 +7,12 @@
 // (FlexAM/models/wan_transformer3d_FlexAM.py:242-244,261,363-365,370,415-416) and cuDNN
 // Conv3d/Conv2d (FlexAM/models/wan_vae3_8.py:39-47,94,99).
 //
+// The skeleton this kernel shares with gemm_fp8.hip, and the pieces of it the two share as code, are in gemm_tile.h.
 // MI355X mapping (MI355X_MICROARCH.md / cdna_hip_programming.md section 5):
 //  * 256x256x64 tile per 512-thread workgroup (8 waves = 2(M) x 4(N), 128x64 outputs per wave),
 //    one workgroup per CU, accumulators in 128 VGPRs per lane; shorter tiles (224..128 rows) are picked
 //    when they fill the last round of 256 CUs (pick_mt).
-//  * both operands staged HBM/L2 -> LDS with 16-byte global_load_lds (no VGPR round trip), two
+//  * both operands staged HBM/L2 -> LDS with 16-byte LDS-DMA (no VGPR round trip), two
 //    LDS buffers (2 x 64 KiB); tile rows are 128 B so the 16-B chunk index is XOR-swizzled with
 //    (row>>1)&7 on the *source* address (the LDS image must stay lane-linear for LDS-DMA) and
 //    again on the ds_read_b128 fragment reads: conflict-free per tools/lds_sim.py.
@@ -37,8 +38,11 @@
 
 #include "common.h"
 #include "flexam_hip.h"
+#include "gemm_tile.h"
 
 namespace {
+
+using namespace gemm_tile;
 
 constexpr int BN = 256, BK = 64;
 constexpr int TILE_BYTES = 256 * BK * 2;   // 32 KiB per operand tile (A: up to 256 rows)
@@ -66,11 +70,6 @@ struct GemmParams {
   float* ws;
   int x_nt;                // gate-residual epilogue: X leaves / arrives with non-temporal hints (launch() decides: only when X is larger than the Infinity Cache can keep)
 };
-
-template <int V>
-using IC = std::integral_constant<int, V>;
-
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GATE_RESIDUAL = 2 };
 
 // 8 OCP e4m3 values (byte j = element j) -> the 8 bf16 of an MFMA operand fragment; exact (every e4m3 value, subnormals and -0
 // included, is a bf16 value; the NaN codes 0x7F / 0xFF come out as NaN)
@@ -154,18 +153,12 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   asm volatile("" : "+s"(wave));
   const int wm = wave / WNW, wn = wave % WNW;
 
-  // ---- persistent workgroups over an XCD-aware, grouped tile order: workgroup w lives on XCD w & 7 (round-robin
-  // dispatch); that XCD owns a contiguous chunk of the tile list and its gridDim/8 workgroups walk the chunk with
-  // stride gridDim/8, so the tiles resident on an XCD at any time are neighbours in the list (shared A / W panels in
-  // its L2) and a workgroup pays its launch latency once, not once per tile.
-  // Whole tiles (units < split_full) are chunked per XCD as described; the K slices of the tail tiles (units >= split_full)
-  // are dealt round-robin over all workgroups afterwards, so every XCD gets the same amount of tail work.
-  const int nwg = p.split_full;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-  const int chunk0 = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int chunk_n = q8 + (xcd < r8 ? 1 : 0);
-  const int local = blockIdx.x >> 3;
-  const int n_whole = TAIL ? 0 : (local < chunk_n ? (chunk_n - local + per_xcd - 1) / per_xcd : 0);
+  // ---- persistent workgroups over an XCD-aware, grouped tile order (XcdWalk).  Whole tiles (units < split_full) are chunked per
+  // XCD; the K slices of the tail tiles (units >= split_full) are dealt round-robin over all workgroups afterwards, so every XCD
+  // gets the same amount of tail work.
+  const XcdWalk walk(p.split_full);
+  const int chunk0 = walk.chunk0, local = walk.local, per_xcd = walk.per_xcd;
+  const int n_whole = TAIL ? 0 : walk.n_units;
   const int n_tail = !TAIL ? 0 : ((int)blockIdx.x < p.units - p.split_full ? (p.units - p.split_full - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0);
   auto nth_unit = [&](int j) -> int {       // j-th work unit of this workgroup, -1 past the end
     if (j < n_whole) return chunk0 + local + j * per_xcd;
@@ -186,7 +179,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
   };
   // ---- staging addresses: thread -> (row = i*64 + tid/8, LDS slot = tid%8), source chunk = slot ^ swz(row).
   // Byte offsets from the tile's first row fit 32 bits (256 rows x row stride), so a piece's source is
-  // (uniform 64-bit tile base + K offset) + one VGPR: the scalar-base form of global_load_lds.
+  // (uniform 64-bit tile base + K offset) + one VGPR: the scalar-base form of the LDS-DMA (lds_dma_b128).
   uint32_t a_off[PA], w_off[PW];
   const char *a_tile, *w_tile;
   auto stage_setup = [&](int m0, int n0) {
@@ -242,7 +235,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
       if (pb) {
         const uint32_t voff = (uint32_t)min(n0 + wn * (16 * NTW) + fresh_lane(), p.N - 1) * 4u;
         const uint32_t dst = (uint32_t)(uintptr_t)LDS_PTR(smem) + BIAS_OFF + (slot * 8 + wave) * 256;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(pb), "s"(dst) : "memory");
+        lds_dma_b32(voff, pb, dst);
       }
     }
   };
@@ -262,7 +255,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
         for (int h = 0; h < (16 * MT > 64 ? 2 : 1); ++h) {
           const uint32_t voff = (uint32_t)min(m0 + wm * (16 * MT) + 64 * h + fresh_lane(), p.M - 1) * 4u;
           const uint32_t dst = (uint32_t)(uintptr_t)LDS_PTR(smem) + GROW_OFF + ((slot * 8 + wave) * 128 + 64 * h) * 4;
-          asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(voff), "s"(pg), "s"(dst) : "memory");
+          lds_dma_b32(voff, pg, dst);
         }
       }
     }
@@ -314,14 +307,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     const char* sbase = i < PA ? a_tile + ka * 2 : w_tile + kw * WB;
     const uint32_t voff = i < PA ? a_off[i] : w_off[i - PA];
     const uint32_t dst = (uint32_t)(uintptr_t)LDS_PTR(buf) + (i < PA ? i * 8192 : A_BYTES + (i - PA) * 8192) + wave * 1024;
-    // M0 (the LDS base of the DMA) is written and NOT restored: nothing else in this kernel uses it (gfx9+ LDS instructions do not;
-    // tools/isa_loopwaits.py lists any other M0 reader of the listing), and the save / restore pair was 2 of the 6 scalar
-    // instructions of every piece
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(dst) : "memory");
-  };
-  auto wait_barrier = [&](auto n_c) {                  // at most N of this wave's vector-memory operations still in flight, then barrier
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_c)::value) : "memory");
-    __syncthreads();
+    lds_dma_b128(voff, sbase, dst);
   };
   // fragment j (< NF = MT + NTW) of the set of K half hf: j < NTW -> W n-tile j, else A m-tile j - NTW, all 32 deep
   auto frag = [&](const char* buf, int hf, int j) -> bf16x8 {
@@ -432,8 +418,6 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     __builtin_amdgcn_sched_barrier(0);
     kcol_next = kcol_a(kb0 + kb + 3);
   };
-  using T_ = std::integral_constant<bool, true>;
-  using F_ = std::integral_constant<bool, false>;
   int kb = 0;
   if (counted) { block(0, T_{}, T_{}, IC<PEND>{}); kb = 1; }     // K block 1 has landed; the epilogue stores may still be in flight
   for (; kb + 2 < nkl; ++kb) block(kb, T_{}, T_{}, IC<0>{});
@@ -473,7 +457,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     for (int t = 0; t < NRT; ++t)
 #pragma unroll
       for (int v = 0; v < NV; ++v) *(f32x4*)(slab + ((t * NV + v) * 512 + te) * 4) = accv(t, v);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): the stores are drained here (pend stays false)
+    wait_vm<0>();                // vmcnt(0): the stores are drained here (pend stays false)
     continue;
   }
   if constexpr (!TAIL) {
@@ -621,7 +605,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
       }
       // every load of this epilogue has been consumed; saying so with an instruction the compiler's wait bookkeeping sees keeps
       // it from putting a vmcnt(0) of its own in front of the next unit's first register reuse (behind the stores)
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (PEND & 15) | ((PEND >> 4) << 14));
+      wait_vm<PEND>();
       pend = true;                                     // PEND = 4 MT stores per wave, issued after the next unit's K blocks
       continue;                                        // next tile of this persistent workgroup
     }
@@ -658,7 +642,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
           else *(bf16x8*)(crow + (int64_t)(t * RT + 8 * i) * p.ldc) = o8;
         }
       }
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (PEND & 15) | ((PEND >> 4) << 14));   // see the gate-residual path
+      wait_vm<PEND>();   // see the gate-residual path
       pend = true;                                     // PEND = 2 MT stores per wave, issued after the next unit's K blocks
       continue;                                        // next tile of this persistent workgroup
     }
@@ -717,7 +701,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     };
     if (p.gate) rmw_rows(std::integral_constant<bool, true>{});
     else rmw_rows(std::integral_constant<bool, false>{});
-    __builtin_amdgcn_s_waitcnt(0x0F70);                // vmcnt(0): an unknown number of stores, drained here (pend stays false)
+    wait_vm<0>();                // vmcnt(0): an unknown number of stores, drained here (pend stays false)
     continue;
   }
 #pragma unroll
@@ -759,7 +743,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
       }
     }
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);                  // vmcnt(0): edge tiles / fp32 outputs issue an unknown number of stores, drained here (pend stays false)
+  wait_vm<0>();                  // vmcnt(0): edge tiles / fp32 outputs issue an unknown number of stores, drained here (pend stays false)
   }   // !TAIL
   }   // tile loop
 }
@@ -818,50 +802,15 @@ __global__ __launch_bounds__(512) void gemm_splitk_finish_kernel(GemmParams p) {
   }
 }
 
-// scratch for the tail split-K, handed in by the caller with every launch (nothing is retained between calls):
-// slabs of 256 x 256 fp32, no initialisation needed
-struct GemmWorkspace {
-  float* slabs = nullptr;
-  int64_t n_slabs = 0;
-};
-
-int num_cus() { return flexam_num_cus(); }
-
-// Tail split-K plan: `rem` = tiles of the last, partial round of the CUs.  Cutting each of them into S K slices turns that
-// round into ceil(rem*S/G) passes of 1/S of a tile; every pass parks 256 KiB of partial sums per workgroup (~4 K blocks of main
-// loop), and the finish launch costs a kernel boundary plus rem * S slabs read chip-wide (~4 + 0.03 * rem * S K blocks).  S (<= 8,
-// slabs must fit the workspace) minimises the sum; with K = 3072 (48 K blocks) the hand-off eats most of the gain, with
-// K = 14336 the tail shrinks to ~0.4 tile times.  `cost` = resulting length of the tail in tile times (1.0 without a split).
-void plan_split(const GemmWorkspace& g_ws, int tiles, int nk, int& S, int& rem, double* cost = nullptr) {
-  const int G = num_cus();
-  static const int enabled = [] { const char* e = getenv("FLEXAM_GEMM_SPLITK"); return e ? atoi(e) : 1; }();
-  rem = tiles % G;
-  S = 1;
-  double best = rem ? 1.0 : 0.0;
-  if (enabled && g_ws.slabs && rem) {
-    for (int s = 2; s <= 8 && s <= nk / 8 && (int64_t)rem * s <= g_ws.n_slabs; ++s) {
-      const int passes = (rem * s + G - 1) / G;
-      const double c = passes * (1.0 / s + 4.0 / nk) + (4.0 + 0.03 * rem * s) / nk;
-      if (c < best - 0.05) { best = c; S = s; }
-    }
-  }
-  if (cost) *cost = best;
-}
-
 template <int EPI, typename OutT, int MT, int WMW = 2, int NTW = 4, bool W8 = false>
 int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff, hipStream_t s) {
   auto kern = gemm_bf16_kernel<EPI, OutT, MT, false, WMW, NTW, W8>;
-  static bool attr_set[FLEXAM_MAX_DEVICES] = {};          // per device: the attribute belongs to the device's copy of the code object
+  static bool lds_set[FLEXAM_MAX_DEVICES] = {}, tail_lds_set[FLEXAM_MAX_DEVICES] = {};
   // two K-block buffers (128 KiB) + one row tile of bf16 outputs per wave + two bias slots + two gate-row slots per wave; the tall
   // 160-wide shape: two buffers of [384 rows of A | 3 pieces of W] (144 KiB), no staging
   const int smem = WMW * 16 * MT > 256 ? 2 * (WMW * 16 * MT * 128 + ((8 / WMW) * NTW * 16 + 63) / 64 * 8192)
                                        : 4 * TILE_BYTES + 8 * 16 * 128 + 2 * 8 * 256 + 2 * 8 * 512;
-  const int dev = flexam_current_device();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return flexam_fail(FLEXAM_E_LAUNCH, "gemm: cannot raise dynamic LDS to %d bytes", smem);
-    attr_set[dev] = true;
-  }
+  if (int rc = set_dynamic_lds_once((const void*)kern, smem, "gemm", lds_set)) return rc;
   p.tiles_m = (p.M + WMW * 16 * MT - 1) / (WMW * 16 * MT);
   p.tiles_n = (p.N + (8 / WMW) * NTW * 16 - 1) / ((8 / WMW) * NTW * 16);
   const int tiles = p.tiles_m * p.tiles_n;
@@ -871,58 +820,15 @@ int launch_shape(GemmParams p, const GemmWorkspace& g_ws, const int64_t* a_koff,
   p.split_full = split_s > 1 ? tiles - rem : tiles;
   p.units = p.split_full + (split_s > 1 ? rem * split_s : 0);
   p.ws = g_ws.slabs;
-  auto grid_for_units = [&](int nwg) {
-    int grid = (nwg + 7) / 8 * 8;                        // a multiple of 8 so that blockIdx & 7 is the XCD
-    if (grid > num_cus()) grid = num_cus();              // one persistent workgroup per CU (156 of its 160 KiB of LDS)
-    return grid;
-  };
-  if (p.split_full > 0) hipLaunchKernelGGL(kern, dim3(grid_for_units(p.split_full)), dim3(512), smem, s, p, a_koff);
+  if (p.split_full > 0) hipLaunchKernelGGL(kern, dim3(persistent_grid(p.split_full)), dim3(512), smem, s, p, a_koff);
   if (split_s > 1) {
     // the K slices of the tail tiles, then (stream-ordered) their sum in slice order + the epilogue
     auto tail = gemm_bf16_kernel<EPI_NONE, float, MT, true, WMW, NTW, W8>;
-    static bool tail_attr[FLEXAM_MAX_DEVICES] = {};
-    if (!tail_attr[dev]) {
-      if (hipFuncSetAttribute((const void*)tail, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-        return flexam_fail(FLEXAM_E_LAUNCH, "gemm: cannot raise dynamic LDS to %d bytes", smem);
-      tail_attr[dev] = true;
-    }
-    hipLaunchKernelGGL(tail, dim3(grid_for_units(rem * split_s)), dim3(512), smem, s, p, a_koff);
+    if (int rc = set_dynamic_lds_once((const void*)tail, smem, "gemm", tail_lds_set)) return rc;
+    hipLaunchKernelGGL(tail, dim3(persistent_grid(rem * split_s)), dim3(512), smem, s, p, a_koff);
     hipLaunchKernelGGL((gemm_splitk_finish_kernel<EPI, OutT, MT, WMW, NTW>), dim3(rem * MT), dim3(512), 0, s, p);
   }
   return flexam_check_launch(W8 ? "flexam_gemm_w8" : "flexam_gemm_bf16");
-}
-
-// Length of a launch on pick_mt's scale: rounds of the concurrently resident workgroups (whole ones + the tail plan_split leaves)
-// x relative cost of one tile.
-double launch_cost(const GemmWorkspace& g_ws, int tiles, int nk, double tile_cost) {
-  int S, rem;
-  double tail;
-  plan_split(g_ws, tiles, nk, S, rem, &tail);
-  return (tiles / num_cus() + tail) * tile_cost;
-}
-
-// The best 256-wide plan: tile heights MT = 8..4, a tile costing its MT m-tiles of MFMA work plus a fixed part for the W side,
-// barriers and the epilogue.  A smaller tile replaces a larger one only below `keep` x its cost; returns the cost of the plan kept.
-double best_256wide(const GemmWorkspace& g_ws, int M, int tiles_n, int nk, double keep, int* best_mt = nullptr) {
-  int best = 8;
-  double best_cost = 1e30;
-  for (int mt = 8; mt >= 4; --mt) {
-    const int tiles = (int)((long)((M + 32 * mt - 1) / (32 * mt)) * tiles_n);
-    const double cost = launch_cost(g_ws, tiles, nk, mt + 1.25);
-    if (cost < best_cost * keep) { best_cost = cost; best = mt; }
-  }
-  if (best_mt) *best_mt = best;
-  return best_cost;
-}
-
-// Tile height of the 256-wide shapes; FLEXAM_GEMM_MT=8..4 forces one (tuning only).
-int pick_mt(const GemmWorkspace& g_ws, int M, int tiles_n, int nk) {
-  const char* e = getenv("FLEXAM_GEMM_MT");
-  const int forced = e ? atoi(e) : 0;
-  if (forced >= 4 && forced <= 8) return forced;
-  int mt;
-  best_256wide(g_ws, M, tiles_n, nk, 0.97, &mt);                       // a smaller tile must win by > 3 %
-  return mt;
 }
 
 // caller's scratch -> workspace view; too small or NULL = no split-K
@@ -970,7 +876,7 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
       if constexpr (W8) {
         return flexam_fail(FLEXAM_E_SHAPE, "gemm_w8: N=%d takes the 160-wide tile of the bf16 GEMM, which has no e4m3 form", p.N);
       } else {
-        if (tiles_tall >= 4L * num_cus()) return launch_shape<EPI, OutT, EPI == EPI_GATE_RESIDUAL ? 5 : 6, 4, 5>(p, g_ws, a_koff, s);
+        if (tiles_tall >= 4L * flexam_num_cus()) return launch_shape<EPI, OutT, EPI == EPI_GATE_RESIDUAL ? 5 : 6, 4, 5>(p, g_ws, a_koff, s);
         return launch_shape<EPI, OutT, 4, 4, 5>(p, g_ws, a_koff, s);
       }
     }
@@ -987,11 +893,11 @@ int launch(const GemmParams& p_, void* ws, int64_t ws_bytes, const int64_t* a_ko
     if (mode == 1) {
       const int nk = p.K / BK;
       const int tiles192 = (int)((long)((p.M + 191) / 192) * (p.N / 192));
-      take = launch_cost(g_ws, tiles192, nk, 0.75 * 6 + 1.1) < 0.95 * best_256wide(g_ws, p.M, p.tiles_n, nk, 1.0);
+      take = launch_cost(g_ws, tiles192, nk, 0.75 * 6 + 1.1) < 0.95 * best_256wide(g_ws, p.M, p.tiles_n, nk, 1.0, 8, 4);
     }
     if (take) return launch_shape<EPI, OutT, 6, 2, 3, W8>(p, g_ws, a_koff, s);
   }
-  switch (pick_mt(g_ws, p.M, p.tiles_n, p.K / BK)) {
+  switch (pick_mt(g_ws, p.M, p.tiles_n, p.K / BK, 8, 4)) {      // FLEXAM_GEMM_MT=8..4 forces one (tuning only)
     case 7: return launch_shape<EPI, OutT, 7, 2, 4, W8>(p, g_ws, a_koff, s);
     case 6: return launch_shape<EPI, OutT, 6, 2, 4, W8>(p, g_ws, a_koff, s);
     case 5: return launch_shape<EPI, OutT, 5, 2, 4, W8>(p, g_ws, a_koff, s);

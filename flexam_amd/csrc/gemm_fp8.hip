@@ -7,9 +7,10 @@
 // Per-row dynamic scales for the activations (flexam_quantize_rows_fp8: absmax / 448), per-output-channel scales for the weights,
 // fp32 accumulation on v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales (E8M0 127): 2x the bf16 MFMA rate.
 //
-// Structure = gemm.hip's with K counted in BYTES: a 128-byte row segment is 64 bf16 or 128 fp8 values, so the LDS image, the
-// XOR swizzle, the LDS-DMA staging, the two K-block buffers, the persistent XCD-aware tile walk, the counted-vmcnt hand-over
-// between units and the LDS-staged epilogues are the same.  What differs is the K block's inner order: one 16x16x128 MFMA
+// Structure = gemm.hip's with K counted in BYTES (a 128-byte row segment is 64 bf16 or 128 fp8 values); the skeleton both follow --
+// the LDS image and its XOR swizzle, the LDS-DMA staging, the two K-block buffers, the persistent XCD-aware tile walk, the
+// counted-vmcnt hand-over between units, the LDS-staged epilogues -- is described once, in gemm_tile.h, which also holds the pieces
+// the two files share as code.  What differs is the K block's inner order: one 16x16x128 MFMA
 // consumes a lane group's 32 contiguous bytes (16-byte chunks 2g and 2g+1 of the row segment) of BOTH operands, so the block is
 // cut by m-tiles instead of by K halves:
 //   phase A: MFMAs of m-tiles [0, H0) while the A fragments of m-tiles [H0, MT) are read from `cur`
@@ -23,8 +24,11 @@
 
 #include "common.h"
 #include "flexam_hip.h"
+#include "gemm_tile.h"
 
 namespace {
+
+using namespace gemm_tile;
 
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
@@ -53,11 +57,6 @@ struct Gemm8Params {
   int units;
 };
 
-template <int V>
-using IC = std::integral_constant<int, V>;
-
-enum { EPI_NONE = 0, EPI_GELU = 1, EPI_GATE_RESIDUAL = 2, EPI_GELU_Q = 3 };      // GELU_Q: GELU, then e4m3 / out_scale[m] (the next GEMM's A operand)
-
 template <int EPI, int MT>
 __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
   constexpr int RT = 16, NRT = MT, NG = 4, NV = 4, NTW = 4;
@@ -75,12 +74,8 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
   asm volatile("" : "+s"(wave));
   const int wm = wave >> 2, wn = wave & 3;
 
-  const int nwg = p.units;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = blockIdx.x & 7, per_xcd = gridDim.x >> 3;
-  const int chunk0 = xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
-  const int chunk_n = q8 + (xcd < r8 ? 1 : 0);
-  const int local = blockIdx.x >> 3;
-  const int n_units = local < chunk_n ? (chunk_n - local + per_xcd - 1) / per_xcd : 0;
+  const XcdWalk walk(p.units);
+  const int chunk0 = walk.chunk0, local = walk.local, per_xcd = walk.per_xcd, n_units = walk.n_units;
   auto tile_origin = [&](int bid, int& m0, int& n0) {
     const int GM = p.gm;
     const int per_group = GM * p.tiles_n;
@@ -133,11 +128,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
     const char* sbase = (i < PA ? a_tile : w_tile) + kbyte;
     const uint32_t voff = i < PA ? a_off[i] : w_off[i - PA];
     const uint32_t dst = (uint32_t)(uintptr_t)LDS_PTR(buf) + (i < PA ? i * 8192 : TILE_BYTES + (i - PA) * 8192) + wave * 1024;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sbase), "s"(dst) : "memory");
-  };
-  auto wait_barrier = [&](auto n_c) {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(decltype(n_c)::value) : "memory");
-    __syncthreads();
+    lds_dma_b128(voff, sbase, dst);
   };
   // fragment = 32 bytes (two 16-byte reads) of W n-tile j (j < 4) or A m-tile j - 4
   auto frag = [&](const char* buf, int j, i32x8& f) {
@@ -162,8 +153,6 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
                                                                      0x7F7F7F7F);
     }
   };
-  using T_ = std::integral_constant<bool, true>;
-  using F_ = std::integral_constant<bool, false>;
 
   if (!staged) {
 #pragma unroll
@@ -194,16 +183,16 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
     const int mr = m0 + wm * (16 * MT) + le0;
     const float* pb = p.bias;
     asm volatile("" : "+s"(pb));
-    if (pb) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(ncol4), "s"(pb), "s"(dst) : "memory");
+    if (pb) lds_dma_b32(ncol4, pb, dst);
     else ((float*)(smem + 4 * TILE_BYTES + 8 * STG_WAVE + wave * 1024))[le0] = 0.f;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(ncol4), "s"(p.sw), "s"(dst + 256) : "memory");
+    lds_dma_b32(ncol4, p.sw, dst + 256);
     const uint32_t r0 = (uint32_t)min(mr, p.M - 1) * 4u, r1 = (uint32_t)min(mr + 64, p.M - 1) * 4u;
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(r0), "s"(p.sa), "s"(dst + 512) : "memory");
-    if (16 * MT > 64) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(r1), "s"(p.sa), "s"(dst + 768) : "memory");
+    lds_dma_b32(r0, p.sa, dst + 512);
+    if (16 * MT > 64) lds_dma_b32(r1, p.sa, dst + 768);
     if constexpr (EPI == EPI_GELU_Q) {                   // the output row scales of the wave's 16 MT rows: a second kilobyte per wave
       const uint32_t dst2 = (uint32_t)(uintptr_t)LDS_PTR(smem) + 4 * TILE_BYTES + 8 * STG_WAVE + 8 * 1024 + wave * 512;
-      asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(r0), "s"(p.so), "s"(dst2) : "memory");
-      if (16 * MT > 64) asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1" ::"v"(r1), "s"(p.so), "s"(dst2 + 256) : "memory");
+      lds_dma_b32(r0, p.so, dst2);
+      if (16 * MT > 64) lds_dma_b32(r1, p.so, dst2 + 256);
     }
   }
   frag_setup();
@@ -346,7 +335,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
       if (!p.gate) rmw(IC<0>{});
       else if (p.gate_row) rmw(IC<1>{});
       else rmw(IC<2>{});
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (PEND & 15) | ((PEND >> 4) << 14));
+      wait_vm<PEND>();
       pend = true;
       continue;
     }
@@ -372,7 +361,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
         const u32x4 o = *(const u32x4*)(stg + rd_row * 64 + ((rd_c ^ ((rd_row >> 1) & 3)) << 4));
         __builtin_nontemporal_store(o, (u32x4*)(crow + (int64_t)(t * 16) * p.ldc));
       }
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (PEND & 15) | ((PEND >> 4) << 14));
+      wait_vm<PEND>();
       pend = true;
       continue;
     }
@@ -392,7 +381,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
         *(int*)((uint8_t*)p.C + (int64_t)m * p.ldc + n) = w;
       }
     }
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vm<0>();
     continue;
   }
   if constexpr (EPI != EPI_GATE_RESIDUAL && EPI != EPI_GELU_Q) {
@@ -420,7 +409,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
           *(bf16x8*)(crow + (int64_t)(t * 16 + 8 * i) * p.ldc) = o8;
         }
       }
-      __builtin_amdgcn_s_waitcnt(0x0F70 | (PEND & 15) | ((PEND >> 4) << 14));
+      wait_vm<PEND>();
       pend = true;
       continue;
     }
@@ -461,7 +450,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
       }
     }
   }
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  wait_vm<0>();
   }   // tile loop
 }
 
@@ -498,39 +487,20 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16* __re
   }
 }
 
-int pick_mt8(int M, int tiles_n) {
-  const char* e = getenv("FLEXAM_GEMM_MT");
-  const int forced = e ? atoi(e) : 0;
-  if (forced >= 4 && forced <= 7) return forced;
-  int best = 7;
-  double best_cost = 1e30;
-  const int G = flexam_num_cus();
-  // 224-row tiles at most: a 256-row instance would keep 64 A + 32 W fragment registers next to 128 accumulators and spill
-  // (it ran at 1.5-1.7 PF against 2.1-2.2 for MT = 7 at the FFN2 shapes, tools/fp8_ffn2_sweep.py, and is no longer compiled)
-  for (int mt = 7; mt >= 4; --mt) {
-    const int tiles = (int)((long)((M + 32 * mt - 1) / (32 * mt)) * tiles_n);
-    const double cost = ((tiles + G - 1) / G) * (mt + 1.25);
-    if (cost < best_cost * 0.97) { best_cost = cost; best = mt; }
-  }
-  return best;
-}
+// Tile height: the bf16 GEMM's chooser without a split-K workspace (a launch costs ceil(tiles / CUs) x (MT + 1.25)), over MT = 7..4.
+// 224-row tiles at most: a 256-row instance would keep 64 A + 32 W fragment registers next to 128 accumulators and spill
+// (it ran at 1.5-1.7 PF against 2.1-2.2 for MT = 7 at the FFN2 shapes, tools/fp8_ffn2_sweep.py, and is no longer compiled)
+int pick_mt8(int M, int tiles_n) { return pick_mt(GemmWorkspace{}, M, tiles_n, 0, 7, 4); }
 
 template <int EPI, int MT>
 int launch_shape8(Gemm8Params p, hipStream_t s) {
   auto kern = gemm_fp8_kernel<EPI, MT>;
-  static bool attr_set[FLEXAM_MAX_DEVICES] = {};
+  static bool lds_set[FLEXAM_MAX_DEVICES] = {};
   const int smem = 4 * TILE_BYTES + 8 * 16 * 128 + 8 * 1024 + (EPI == EPI_GELU_Q ? 8 * 512 : 0);      // K-block buffers, output staging, epilogue constants (+ output row scales)
-  const int dev = flexam_current_device();
-  if (!attr_set[dev]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return flexam_fail(FLEXAM_E_LAUNCH, "gemm_fp8: cannot raise dynamic LDS to %d bytes", smem);
-    attr_set[dev] = true;
-  }
+  if (int rc = set_dynamic_lds_once((const void*)kern, smem, "gemm_fp8", lds_set)) return rc;
   p.tiles_m = (p.M + 32 * MT - 1) / (32 * MT);
   p.units = p.tiles_m * p.tiles_n;
-  int grid = (p.units + 7) / 8 * 8;
-  if (grid > flexam_num_cus()) grid = flexam_num_cus();
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, s, p);
+  hipLaunchKernelGGL(kern, dim3(persistent_grid(p.units)), dim3(512), smem, s, p);
   return flexam_check_launch("flexam_gemm_fp8");
 }
 
@@ -554,6 +524,16 @@ int check8(const void* A, int64_t lda, const void* W, int64_t ldw, const float* 
   return FLEXAM_OK;
 }
 
+// the fields every entry point fills (ld* in bytes == elements); the output / residual fields are the entry point's own
+Gemm8Params make_params8(const void* A, int64_t lda, const float* a_scale, const void* W, int64_t ldw, const float* w_scale,
+                         const float* bias, int64_t M, int64_t N, int64_t K) {
+  Gemm8Params p{};
+  p.A = (const uint8_t*)A; p.W = (const uint8_t*)W; p.bias = bias; p.sa = a_scale; p.sw = w_scale;
+  p.lda = lda; p.ldw = ldw; p.M = (int)M; p.N = (int)N; p.K = (int)K;
+  p.tiles_n = (int)((N + BN - 1) / BN);
+  return p;
+}
+
 }  // namespace
 
 extern "C" int flexam_quantize_rows_fp8(const void* x, int64_t ldx, void* q, int64_t ldq, float* scale, int64_t M, int K, void* stream) {
@@ -570,10 +550,8 @@ extern "C" int flexam_gemm_fp8(const void* A, int64_t lda, const float* a_scale,
   if (int rc = check8(A, lda, W, ldw, a_scale, w_scale, M, N, K)) return rc;
   FX_REQUIRE(C && ldc % 4 == 0 && (uintptr_t)C % 16 == 0, FLEXAM_E_ARG, "gemm_fp8: bad output");
   FX_REQUIRE(epilogue == EPI_NONE || epilogue == EPI_GELU, FLEXAM_E_ARG, "gemm_fp8: unknown epilogue %d", epilogue);
-  Gemm8Params p{};
-  p.A = (const uint8_t*)A; p.W = (const uint8_t*)W; p.C = C; p.bias = bias; p.sa = a_scale; p.sw = w_scale;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldc; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);
+  Gemm8Params p = make_params8(A, lda, a_scale, W, ldw, w_scale, bias, M, N, K);
+  p.C = C; p.ldc = ldc;
   return epilogue == EPI_GELU ? launch8<EPI_GELU>(p, (hipStream_t)stream) : launch8<EPI_NONE>(p, (hipStream_t)stream);
 }
 
@@ -582,10 +560,8 @@ extern "C" int flexam_gemm_fp8_gelu_q(const void* A, int64_t lda, const float* a
                                       void* stream) {
   if (int rc = check8(A, lda, W, ldw, a_scale, w_scale, M, N, K)) return rc;
   FX_REQUIRE(Q && out_scale && ldq % 16 == 0 && (uintptr_t)Q % 16 == 0, FLEXAM_E_ARG, "gemm_fp8_gelu_q: bad output (e4m3 rows, 16-byte aligned)");
-  Gemm8Params p{};
-  p.A = (const uint8_t*)A; p.W = (const uint8_t*)W; p.C = Q; p.bias = bias; p.sa = a_scale; p.sw = w_scale; p.so = out_scale;
-  p.lda = lda; p.ldw = ldw; p.ldc = ldq; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);
+  Gemm8Params p = make_params8(A, lda, a_scale, W, ldw, w_scale, bias, M, N, K);
+  p.C = Q; p.ldc = ldq; p.so = out_scale;
   return launch8<EPI_GELU_Q>(p, (hipStream_t)stream);
 }
 
@@ -596,10 +572,7 @@ extern "C" int flexam_gemm_fp8_gate_residual(const void* A, int64_t lda, const f
   if (int rc = check8(A, lda, W, ldw, a_scale, w_scale, M, N, K)) return rc;
   FX_REQUIRE(X && ldx % 4 == 0, FLEXAM_E_ARG, "gemm_fp8_gate_residual: bad residual");
   FX_REQUIRE(!gate || gate_row || rows_per_batch > 0, FLEXAM_E_ARG, "gemm_fp8_gate_residual: gate needs gate_row or rows_per_batch");
-  Gemm8Params p{};
-  p.A = (const uint8_t*)A; p.W = (const uint8_t*)W; p.bias = bias; p.sa = a_scale; p.sw = w_scale;
-  p.lda = lda; p.ldw = ldw; p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_n = (int)((N + BN - 1) / BN);
+  Gemm8Params p = make_params8(A, lda, a_scale, W, ldw, w_scale, bias, M, N, K);
   p.X = X; p.ldx = ldx; p.gate = gate; p.gate_ld = gate_ld; p.gate_row = gate_row;
   p.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
   return launch8<EPI_GATE_RESIDUAL>(p, (hipStream_t)stream);
