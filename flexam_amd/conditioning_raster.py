@@ -17,6 +17,11 @@ Split of the work: the O(T N) colour tables (percentiles, clips, the colormap) a
 reference writes them so the bytes agree; the O(T N squares) drawing is HIP.  There is no CPU drawing path: without the HIP library
 `flexam_amd.hip` raises.
 
+Tracks that arrive as a CUDA float32 tensor (flexam_amd.motion leaves them there) stay on the device: the percentiles are exact order
+statistics from csrc/raster_colors.hip, interpolated with numpy's own arithmetic (`_percentile_index`), the tables are HIP kernels, and
+what comes back to the host is the valid counts and three flags per selection.  The bytes are those of the host path.  Every other
+input (numpy, CPU tensors, float64) takes the host path.
+
 Differences from the reference, all at its undefined corners: points of EQUAL depth are ordered by index (lower index on top) where the
 reference's order is numpy's unstable argsort; the random blue channel / random z code it draws when every depth is zero takes an explicit
 `generator` (default: numpy's global state, like the reference); `save_tracking=True` (mp4 files through moviepy) and `mask_path`
@@ -105,12 +110,7 @@ def _tracking_colors(first_frame_pts: np.ndarray, height: int, width: int, gener
     colors[:, 1] = (np.clip((first_frame_pts[:, 1] - 0) / (height - 0), 0, 1) * 255).astype(np.uint8)
     z_values = first_frame_pts[:, 2]
     if np.all(z_values == 0):
-        # the reference draws from numpy's global state (np.random.randint, pipelines.py:1536); an explicit generator of either numpy
-        # kind makes the corner reproducible: np.random.Generator (default_rng) has `integers`, np.random.RandomState `randint`
-        if generator is not None and hasattr(generator, "integers"):
-            colors[:, 2] = generator.integers(0, 256, n, dtype=np.uint8)
-        else:
-            colors[:, 2] = (generator if generator is not None else np.random).randint(0, 256, n, dtype=np.uint8)
+        colors[:, 2] = _random_blue(n, generator)
     else:
         inv_z = 1 / (z_values + 1e-10)
         p2, p98 = np.percentile(inv_z, 2), np.percentile(inv_z, 98)
@@ -141,24 +141,102 @@ def _depth_colors(points: np.ndarray, vis: np.ndarray) -> np.ndarray:
     return out
 
 
-def apply_cosine_positional_encoding(pred_tracks_with_depth, height: int, width: int, L: int = 4, generator: Optional[torch.Generator] = None):
-    """pipelines.py:1577-1641, the reference's own torch expressions on whatever device the tracks live on: list of L tensors [T, N, 3]."""
-    pts = pred_tracks_with_depth if isinstance(pred_tracks_with_depth, torch.Tensor) else torch.as_tensor(np.asarray(pred_tracks_with_depth))
-    x_n = torch.clamp((pts[:, :, 0] - 0) / (width - 0), 0, 1)
-    y_n = torch.clamp((pts[:, :, 1] - 0) / (height - 0), 0, 1)
+def _on_device(points) -> bool:
+    """The device-resident path is for float32 tracks that already live on a GPU; everything else is the host path."""
+    return isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32
+
+
+def _percentile_index(n: int, q: int, scalar_form: bool) -> Tuple[int, int, float]:
+    """Where np.percentile(a, q) of n float32 values looks: (lower rank, upper rank, weight), by numpy's `_QuantileMethods['linear']`
+    (virtual index (n - 1) q), `_get_indexes` and `_get_gamma` as written.  The two call forms differ: with a scalar q
+    (`np.percentile(a, 2)`) the quantile is q / float32(100) and the index, the weight and later the interpolation are float32 --
+    at n = 4e7 the index itself is rounded; with an array q (`np.percentile(a, [2, 98])`) they are float64."""
+    quantile = np.asanyarray(np.true_divide(q if scalar_form else np.asarray([q]), np.float32(100)))
+    virtual = np.asanyarray((n - 1) * quantile).reshape(())
+    previous = np.floor(virtual)
+    nxt = previous + 1
+    if virtual >= n - 1:
+        previous = nxt = -1
+    if virtual < 0:
+        previous = nxt = 0
+    previous, nxt = np.asanyarray(previous).astype(np.intp), np.asanyarray(nxt).astype(np.intp)
+    gamma = np.asanyarray(np.asanyarray(virtual - previous), dtype=virtual.dtype)
+    return int(previous) % max(n, 1), int(nxt) % max(n, 1), float(gamma)
+
+
+def _device_percentiles(points: torch.Tensor, segments: int, seg_len: int, vis: Optional[torch.Tensor], inverse: bool, scalar_form: bool):
+    """The (2nd, 98th) percentiles of the depths (or `inverse` depths) of `segments` runs of `seg_len` points, over the visible ones:
+    (percentiles [segments, 2] on the device -- float32 for np.percentile's scalar form, float64 for its array form -- and the
+    selection's info [segments, 4] on the host: counts and flags, the only thing that is read back)."""
+    _, info = hip.select_ranks(points, 2, segments, seg_len, None, vis, inverse)
+    host = info.cpu()
+    plan = [[_percentile_index(n, q, scalar_form) for q in (2, 98)] for n in host[:, 0].tolist()]
+    ranks = torch.tensor([[r for lo, hi, _ in row for r in (lo, hi)] for row in plan], dtype=torch.int64).to(points.device)
+    gamma = torch.tensor([[g for _, _, g in row] for row in plan], dtype=torch.float64).to(points.device)
+    values, info = hip.select_ranks(points, 2, segments, seg_len, ranks, vis, inverse)
+    return hip.select_lerp(values, gamma, info, scalar_form), host
+
+
+def _random_blue(n: int, generator) -> np.ndarray:
+    # the reference draws from numpy's global state (np.random.randint, pipelines.py:1536); an explicit generator of either numpy
+    # kind makes the corner reproducible: np.random.Generator (default_rng) has `integers`, np.random.RandomState `randint`
+    if generator is not None and hasattr(generator, "integers"):
+        return generator.integers(0, 256, n, dtype=np.uint8)
+    return (generator if generator is not None else np.random).randint(0, 256, n, dtype=np.uint8)
+
+
+def _tracking_colors_device(points: torch.Tensor, height: int, width: int, generator=None) -> torch.Tensor:
+    """`_tracking_colors` of points[0] for tracks on the device: [N, 3] uint8 there."""
+    first = points[0]
+    pct, info = _device_percentiles(points, 1, points.shape[1], None, True, True)
+    if not int(info[0, 2]):                            # every depth of the first frame is 0: the blue channel is the caller's generator's
+        return hip.raster_colors_tracking(first, height, width, blue=torch.from_numpy(_random_blue(first.shape[0], generator)).to(points.device))
+    return hip.raster_colors_tracking(first, height, width, pct=pct.reshape(2))
+
+
+def _depth_colors_device(points: torch.Tensor, vis: Optional[torch.Tensor]) -> torch.Tensor:
+    """`_depth_colors` for tracks on the device: [T, N, 3] uint8 there."""
+    pct, _ = _device_percentiles(points, points.shape[0], points.shape[1], vis, False, False)
+    lut = torch.from_numpy(_spectral_bytes_table()).to(points.device)
+    return hip.raster_colors_depth(points, vis, pct, lut)
+
+
+def _cosine_codes(pts: torch.Tensor, height: int, width: int, L: int, generator, frames: Optional[int] = None):
+    """pipelines.py:1577-1641 for the first `frames` frames (None: all).  The depth code is normalised over the WHOLE clip whatever
+    `frames` is; only frame 0 of a code ever colours a video, so the videos ask for one frame."""
+    sel = pts if frames is None else pts[:frames]
+    x_n = torch.clamp((sel[:, :, 0] - 0) / (width - 0), 0, 1)
+    y_n = torch.clamp((sel[:, :, 1] - 0) / (height - 0), 0, 1)
     z = pts[:, :, 2]
-    if torch.all(z == 0):
-        z_n = torch.rand_like(z) if generator is None else torch.rand(z.shape, generator=generator, dtype=z.dtype, device=generator.device).to(z.device)
+    if _on_device(pts):
+        pct, info = _device_percentiles(pts.contiguous(), 1, pts.shape[0] * pts.shape[1], None, True, True)
+        all_zero, p2_t, p98_t = not int(info[0, 2]), pct[0, 0], pct[0, 1]
     else:
-        inv_z = 1 / (z + 1e-10)
-        inv_np = inv_z.detach().cpu().numpy()
-        p2, p98 = np.percentile(inv_np, 2), np.percentile(inv_np, 98)
-        p2_t = torch.tensor(p2, device=inv_z.device, dtype=inv_z.dtype)
-        p98_t = torch.tensor(p98, device=inv_z.device, dtype=inv_z.dtype)
+        all_zero = bool(torch.all(z == 0))
+    if all_zero:
+        z_n = torch.rand_like(z) if generator is None else torch.rand(z.shape, generator=generator, dtype=z.dtype, device=generator.device).to(z.device)
+        z_n = z_n[:sel.shape[0]]
+    else:
+        if _on_device(pts):
+            inv_z = 1 / (sel[:, :, 2] + 1e-10)
+        else:
+            inv_z = 1 / (z + 1e-10)
+            inv_np = inv_z.detach().cpu().numpy()
+            p2, p98 = np.percentile(inv_np, 2), np.percentile(inv_np, 98)
+            p2_t = torch.tensor(p2, device=inv_z.device, dtype=inv_z.dtype)
+            p98_t = torch.tensor(p98, device=inv_z.device, dtype=inv_z.dtype)
+            inv_z = inv_z[:sel.shape[0]]
         z_n = torch.clamp((inv_z - p2_t) / (p98_t - p2_t + 1e-10), 0, 1)
-    norm = torch.zeros_like(pts)
+    norm = torch.zeros_like(sel)
     norm[:, :, 0], norm[:, :, 1], norm[:, :, 2] = x_n, y_n, z_n
     return [torch.cos(((2 ** i) * np.pi) * norm) for i in range(L)]
+
+
+def apply_cosine_positional_encoding(pred_tracks_with_depth, height: int, width: int, L: int = 4, generator: Optional[torch.Generator] = None):
+    """pipelines.py:1577-1641, the reference's own torch expressions on whatever device the tracks live on: list of L tensors [T, N, 3].
+    For float32 tracks on a GPU the two percentiles of the inverse depth come from the device selection; nothing is copied to the host."""
+    pts = pred_tracks_with_depth if isinstance(pred_tracks_with_depth, torch.Tensor) else torch.as_tensor(np.asarray(pred_tracks_with_depth))
+    return _cosine_codes(pts, height, width, L, generator)
 
 
 class _Frames:
@@ -166,11 +244,14 @@ class _Frames:
     pipelines.py:1211) and the one the cosine and depth videos share (y >= 0) -- and with equal square sizes they differ only in the
     points of image row 0, so each is rasterised once and resolved with as many colour tables as there are videos."""
 
-    def __init__(self, points: np.ndarray, vis: np.ndarray, height: int, width: int, mask, device):
+    def __init__(self, points, vis, height: int, width: int, mask, device):
         self.t_n, self.n = points.shape[:2]
         self.h, self.w, self.device = height, width, device
-        self.points = torch.from_numpy(self._kernel_points(points)).to(device)
-        self.vis = torch.from_numpy(np.ascontiguousarray(vis).view(np.uint8)).to(device)
+        if isinstance(points, torch.Tensor):          # float32 tracks on the device (`_device_inputs`): used in place, visibility already there
+            self.points, self.vis = points, vis
+        else:
+            self.points = torch.from_numpy(self._kernel_points(points)).to(device)
+            self.vis = torch.from_numpy(np.ascontiguousarray(vis).view(np.uint8)).to(device)
         self.mask = mask
         self._keys: Dict[Tuple[int, int], torch.Tensor] = {}
 
@@ -202,8 +283,8 @@ class _Frames:
             self._keys[k] = hip.raster_keys(self.points, self.vis, self.h, self.w, half, y_min, self.mask)
         return self._keys[k]
 
-    def video(self, colors: np.ndarray, half: int, y_min: int, as_bytes: bool = False) -> torch.Tensor:
-        c = torch.from_numpy(np.ascontiguousarray(colors)).to(self.device)
+    def video(self, colors, half: int, y_min: int, as_bytes: bool = False) -> torch.Tensor:
+        c = colors if isinstance(colors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(colors)).to(self.device)
         u8, f32 = hip.raster_resolve(self.keys(half, y_min), c, want_u8=as_bytes, want_f32=not as_bytes)
         return u8 if as_bytes else f32.unsqueeze(0)          # [T, H, W, 3] bytes, or [1, 3, T, H, W] = _convert_frames_to_tensor(..).unsqueeze(0)
 
@@ -214,9 +295,44 @@ def _device(device):
     return torch.device(device)
 
 
+def _device_inputs(points: torch.Tensor, vis_mask, device):
+    """The device path's (points, visibility, device): float32 [T, N, 3] contiguous on its GPU (on `device`, if one is named), and the
+    visibility as bytes [T, N] there, uploaded once -- None (everything visible) stays None."""
+    if points.dim() != 3 or points.shape[2] != 3:
+        raise ValueError(f"points must be [T, N, 3] (u, v, depth), got {tuple(points.shape)}")
+    points = points.detach()
+    if device is not None:
+        points = points.to(device)
+    points = points.contiguous()
+    if vis_mask is None:
+        return points, None, points.device
+    if isinstance(vis_mask, torch.Tensor):
+        vis = vis_mask.detach()
+        if vis.dim() == 3 and vis.shape[2] == 1:
+            vis = vis.squeeze(-1)
+        if tuple(vis.shape) != tuple(points.shape[:2]):
+            raise ValueError(f"vis_mask must be [T, N] = {tuple(points.shape[:2])}, got {tuple(vis.shape)}")
+        vis = (vis.to(points.device) != 0).contiguous().view(torch.uint8)
+    else:
+        vis = torch.from_numpy(_prepare_vis_mask(vis_mask, points.shape).view(np.uint8)).to(points.device)
+    return points, vis, points.device
+
+
+def _cosine_colors(enc, n_points: int):
+    """The colour table of one encoding level from frame 0 of its code: on the device when the code is float32 there."""
+    if _on_device(enc):
+        return hip.raster_colors_cosine(enc[0].contiguous())
+    first = enc[0].detach().cpu().numpy() if isinstance(enc, torch.Tensor) else np.asarray(enc[0])
+    return _generate_colors_from_points(first, n_points)
+
+
 def fun_visualize_tracking_with_depth(pred_tracks_with_depth, pred_visibility, height, width, point_wise=4, mask_video=None,
                                       generate_type="full_edit", device=None, generator=None) -> torch.Tensor:
     """pipelines.py:1501-1575.  Returns the frames as ONE uint8 tensor [T, H, W, 3] on the GPU (the reference: a list of T numpy frames)."""
+    if _on_device(pred_tracks_with_depth):
+        points, vis, dev = _device_inputs(pred_tracks_with_depth, pred_visibility, device)
+        fr = _Frames(points, vis, height, width, _mask_for(mask_video, generate_type, points.shape[0], height, width, dev), dev)
+        return fr.video(_tracking_colors_device(points, height, width, generator), point_wise // 2, 1, as_bytes=True)
     points = _as_numpy_points(pred_tracks_with_depth)
     vis = _prepare_vis_mask(pred_visibility, points.shape)
     dev = _device(device)
@@ -229,15 +345,17 @@ def _visualize_cosine_encoded_tracking(encoded_tracks_list, original_points, vis
     """pipelines.py:1730-1761: {level: [1, 3, T, H, W]}.  Positions are the ORIGINAL points; the squares are +-2 whatever point_wise is."""
     if save_tracking:
         raise NotImplementedError("save_tracking=True writes mp4 files through moviepy in the reference (pipelines.py:1755-1757): not part of this build")
-    points = _as_numpy_points(original_points)
-    vis = _prepare_vis_mask(vis_mask, points.shape)
-    dev = _device(device)
-    fr = _frames or _Frames(points, vis, height, width, _mask_for(mask_video, generate_type, points.shape[0], height, width, dev), dev)
-    out = {}
-    for i, enc in enumerate(encoded_tracks_list):
-        first = enc[0].detach().cpu().numpy() if isinstance(enc, torch.Tensor) else np.asarray(enc[0])
-        out[i] = fr.video(_generate_colors_from_points(first, points.shape[1]), 2, 0)
-    return out
+    if _frames is not None:
+        fr = _frames
+    elif _on_device(original_points):
+        points, vis, dev = _device_inputs(original_points, vis_mask, device)
+        fr = _Frames(points, vis, height, width, _mask_for(mask_video, generate_type, points.shape[0], height, width, dev), dev)
+    else:
+        points = _as_numpy_points(original_points)
+        vis = _prepare_vis_mask(vis_mask, points.shape)
+        dev = _device(device)
+        fr = _Frames(points, vis, height, width, _mask_for(mask_video, generate_type, points.shape[0], height, width, dev), dev)
+    return {i: fr.video(_cosine_colors(enc, fr.n), 2, 0) for i, enc in enumerate(encoded_tracks_list)}
 
 
 def _visualize_depth_tracking(points, vis_mask, height, width, point_wise=4, save_tracking=False, mask_video=None, generate_type="full_edit",
@@ -245,6 +363,10 @@ def _visualize_depth_tracking(points, vis_mask, height, width, point_wise=4, sav
     """pipelines.py:1763-1820: [1, 3, T, H, W]."""
     if save_tracking:
         raise NotImplementedError("save_tracking=True writes mp4 files through moviepy in the reference (pipelines.py:1814-1818): not part of this build")
+    if _on_device(points):
+        pts, vis, dev = _device_inputs(points, vis_mask, device) if _frames is None else (_frames.points, _frames.vis, _frames.device)
+        fr = _frames or _Frames(pts, vis, height, width, _mask_for(mask_video, generate_type, pts.shape[0], height, width, dev), dev)
+        return fr.video(_depth_colors_device(pts, vis), point_wise // 2, 0)
     pts = _as_numpy_points(points)
     vis = _prepare_vis_mask(vis_mask, pts.shape)
     dev = _device(device)
@@ -264,6 +386,14 @@ def visualize_tracking_DELTA(points, vis_mask=None, save_tracking=False, point_w
     if mask_path is not None:
         raise NotImplementedError("mask_path: decode the mask video yourself and pass mask_video [T, H, W] (1 = keep; invert it for background_edit "
                                   "as pipelines.py:1835-1837 does)")
+    if _on_device(points):
+        pts, vis, dev = _device_inputs(points, vis_mask, device)
+        fr = _Frames(pts, vis, height, width, _mask_for(mask_video, generate_type, pts.shape[0], height, width, dev), dev)
+        tracking_video = fr.video(_tracking_colors_device(pts, height, width, generator), point_wise // 2, 1)
+        encoded = _cosine_codes(pts, height, width, cos_level, torch_generator, frames=1)          # frame 0 is all a video reads of a code
+        cos_video_dict = _visualize_cosine_encoded_tracking(encoded, pts, vis, height, width, False, device=dev, _frames=fr)
+        depth_video = _visualize_depth_tracking(pts, vis, height, width, point_wise, False, device=dev, _frames=fr)
+        return tracking_video, cos_video_dict, depth_video
     pts = _as_numpy_points(points)
     vis = _prepare_vis_mask(vis_mask, pts.shape)
     dev = _device(device)

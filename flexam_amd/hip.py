@@ -1174,3 +1174,89 @@ def motion_project(points, pose, intr):
     out = torch.empty(T, n, 3, device=points.device, dtype=F64)
     _call("flexam_motion_project_f64", _ptr(points), int(points.dtype == F32), T, n, _ptr(pose, F64), _ptr(intr, F64), _ptr(out, F64))
     return out
+
+
+# ----------------------------------------------------------------------------- colour tables of the conditioning videos (csrc/raster_colors.hip)
+SELECT_MAX_RANKS = abi.CONSTANTS["FLEXAM_SELECT_MAX_RANKS"]
+SELECT_WS_SEGMENT_BYTES = abi.CONSTANTS["FLEXAM_SELECT_WS_SEGMENT_BYTES"]
+
+
+def select_ranks(src, comp, segments, seg_len, ranks=None, mask=None, inverse=False):
+    """Exact order statistics of float32 values on the device (flexam_select_f32).  src: contiguous fp32 [..., C]; value (s, i) is
+    component `comp` of row s * seg_len + i, through 1 / (x + 1e-10) when `inverse`; mask: bool / uint8 with one entry per row of the
+    segments, None = all valid; ranks: int64 [segments, K] on the device, or None to count only.
+    -> (values fp32 [segments, K] or None, info int64 [segments, 4] = valid count, a valid NaN, a valid value != 0 before the transform, 0)."""
+    if src.dim() < 1 or src.dtype != F32 or not src.is_contiguous():
+        raise RuntimeError(f"select_ranks: contiguous fp32 values [..., C] required, got {tuple(src.shape)} {src.dtype}")
+    stride = src.shape[-1]
+    rows = segments * seg_len
+    if segments <= 0 or seg_len <= 0 or stride == 0 or rows > src.numel() // stride:
+        raise RuntimeError(f"select_ranks: {segments} segments of {seg_len} rows from {src.numel() // max(stride, 1)} rows")
+    if mask is not None:
+        mask = mask.view(U8) if mask.dtype == torch.bool else mask
+        if mask.dtype != U8 or not mask.is_contiguous() or mask.numel() < rows:
+            raise RuntimeError(f"select_ranks: a contiguous bool / uint8 mask of at least {rows} entries required, got {tuple(mask.shape)} {mask.dtype}")
+    values, k = None, 0
+    if ranks is not None:
+        if ranks.dim() != 2 or ranks.shape[0] != segments or ranks.dtype != I64 or not ranks.is_contiguous() or ranks.device != src.device:
+            raise RuntimeError(f"select_ranks: ranks must be contiguous int64 [{segments}, K] on the values' device, got {tuple(ranks.shape)} {ranks.dtype}")
+        k = ranks.shape[1]
+        values = torch.empty(segments, k, device=src.device, dtype=F32)
+    info = torch.empty(segments, 4, device=src.device, dtype=I64)
+    ws = torch.empty(segments * SELECT_WS_SEGMENT_BYTES // 4, device=src.device, dtype=I32)
+    _call("flexam_select_f32", _ptr(src, F32), stride, int(comp), int(bool(inverse)), _ptr(mask, U8), segments, seg_len, _ptr(ranks, I64), k,
+          _ptr(values, F32), _ptr(info, I64), _raw(ws), ws.numel() * 4)
+    return values, info
+
+
+def select_lerp(values, gamma, info, f32_form):
+    """values fp32 [S, 2 Q] = (lower, upper) pairs of select_ranks, gamma fp64 [S, Q], info of the same select_ranks call -> the
+    percentiles [S, Q] with numpy's `_lerp` arithmetic: fp32 (`f32_form`, np.percentile with a scalar q) or fp64 (an array q)."""
+    S = values.shape[0]
+    if values.dim() != 2 or values.shape[1] % 2 or values.dtype != F32 or not values.is_contiguous():
+        raise RuntimeError(f"select_lerp: contiguous fp32 values [S, 2 Q] required, got {tuple(values.shape)} {values.dtype}")
+    Q = values.shape[1] // 2
+    if tuple(gamma.shape) != (S, Q) or gamma.dtype != F64 or not gamma.is_contiguous() or tuple(info.shape) != (S, 4) or not info.is_contiguous():
+        raise RuntimeError(f"select_lerp: gamma must be contiguous fp64 {(S, Q)} and info int64 {(S, 4)}")
+    out = torch.empty(S, Q, device=values.device, dtype=F32 if f32_form else F64)
+    _call("flexam_select_lerp", _ptr(values, F32), _ptr(gamma, F64), _ptr(info, I64), S, Q, int(bool(f32_form)), _ptr(out))
+    return out
+
+
+def raster_colors_tracking(first_frame, height, width, pct=None, blue=None):
+    """first_frame [N, 3] fp32 (u, v, depth), pct fp32 [2] = the (2nd, 98th) percentile of its inverse depths, or blue uint8 [N] -> colours uint8 [N, 3]."""
+    _points3(first_frame, "raster_colors_tracking", dims=(2,))
+    n = first_frame.shape[0]
+    if (pct is None) == (blue is None):
+        raise RuntimeError("raster_colors_tracking: either the percentiles or the blue channel")
+    if pct is not None and (pct.numel() != 2 or pct.dtype != F32 or not pct.is_contiguous()):
+        raise RuntimeError("raster_colors_tracking: pct must be 2 contiguous fp32 values")
+    if blue is not None and (tuple(blue.shape) != (n,) or blue.dtype != U8 or not blue.is_contiguous()):
+        raise RuntimeError(f"raster_colors_tracking: blue must be contiguous uint8 {(n,)}")
+    out = torch.empty(n, 3, device=first_frame.device, dtype=U8)
+    _call("flexam_raster_colors_tracking", _ptr(first_frame, F32), n, height, width, _ptr(pct, F32), _ptr(blue, U8), _ptr(out, U8))
+    return out
+
+
+def raster_colors_depth(points, visible, pct, lut):
+    """points [T, N, 3] fp32, visible [T, N] bool / uint8 or None, pct fp64 [T, 2] (per-frame 2nd / 98th percentile of the visible
+    depths), lut uint8 [258, 3] -> colours uint8 [T, N, 3]; rows of invisible points are 0."""
+    _points3(points, "raster_colors_depth", dims=(3,))
+    T, n, _ = points.shape
+    if visible is not None:
+        visible = _bytes_mask(visible, (T, n), "raster_colors_depth")
+    if tuple(pct.shape) != (T, 2) or pct.dtype != F64 or not pct.is_contiguous():
+        raise RuntimeError(f"raster_colors_depth: pct must be contiguous fp64 {(T, 2)}")
+    if tuple(lut.shape) != (258, 3) or lut.dtype != U8 or not lut.is_contiguous():
+        raise RuntimeError("raster_colors_depth: lut must be contiguous uint8 [258, 3]")
+    out = torch.empty(T, n, 3, device=points.device, dtype=U8)
+    _call("flexam_raster_colors_depth", _ptr(points, F32), _ptr(visible, U8), T, n, _ptr(pct, F64), _ptr(lut, U8), _ptr(out, U8))
+    return out
+
+
+def raster_colors_cosine(code):
+    """code [N, 3] fp32 (one frame of a cosine encoding) -> colours uint8 [N, 3] = clip((code + 1) / 2, 0, 1) * 255, truncated."""
+    _points3(code, "raster_colors_cosine", dims=(2,))
+    out = torch.empty(code.shape[0], 3, device=code.device, dtype=U8)
+    _call("flexam_raster_colors_cosine", _ptr(code, F32), code.shape[0], _ptr(out, U8))
+    return out

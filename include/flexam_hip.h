@@ -460,6 +460,40 @@ int flexam_motion_unproject_f64(const void* points, int points_f32, int T, int64
 int flexam_motion_project_f64(const void* points, int points_f32, int T, int64_t N, const double* pose, const double* intr, double* out,
                               void* stream);
 
+/* Colour tables of the conditioning videos on the device (flexam_amd/conditioning_raster.py; csrc/raster_colors.hip): what
+ * pipelines.py:1523-1545 (tracking), :1775-1792 (depth) and :1675-1692 (cosine codes -> bytes) compute with np.percentile on the host.
+ * select_f32: exact order statistics.  Value (s, i), s < S, i < seg_len, is src[((s * seg_len + i) * stride + comp)], through
+ *   transform (0: as it is; 1: 1 / (x + 1e-10f), both steps rounded to float32); it is VALID when mask == NULL or
+ *   mask[s * seg_len + i] != 0.  Per segment: info[s][0] = number of valid values n, info[s][1] = 1 if a valid (transformed) value is
+ *   NaN, info[s][2] = 1 if a valid value is != 0 BEFORE the transform (NaN counts), info[s][3] = 0; and, for K > 0,
+ *   values[s][k] = the element of rank min(max(ranks[s][k], 0), n - 1) of the valid values in ascending order (NaN last, -0 before
+ *   +0; n = 0: NaN).  K = 0 (ranks, values NULL) counts only.  Radix select on an order-preserving 32-bit code, 8 bits a pass:
+ *   workgroups histogram the values under each rank's prefix in LDS and flush with integer atomics, a one-workgroup-per-segment
+ *   kernel picks the bins between passes: the same bits on every run.  stride 1 .. 64, comp < stride, K <= FLEXAM_SELECT_MAX_RANKS,
+ *   S <= 65535, seg_len < 2^31; ws: FLEXAM_SELECT_WS_SEGMENT_BYTES per segment (the call clears it); ranks [S][K] int64 on the device.
+ * select_lerp: numpy's `_lerp` between neighbouring order statistics.  values [S][Q][2] = (lower, upper) as select_f32 leaves them for
+ *   ranks (lo_0, hi_0, lo_1, hi_1, ..), gamma [S][Q] double = the weights; d = upper - lower in float32; out[s][q] =
+ *   gamma >= 0.5 ? upper - d (1 - gamma) : lower + d gamma, evaluated in double into double out (f32_form = 0: np.percentile(a, [..])
+ *   of float32 data) or in float32 into float out (f32_form != 0: np.percentile(a, scalar)); NaN where info[s][1] or info[s][0] == 0.
+ * raster_colors_tracking: colors[N][3] from the first frame's points [N][3]: (clip(u / W), clip(v / H), clip((1 / (z + 1e-10) - p2) /
+ *   (p98 - p2 + 1e-10))) * 255 truncated, all float32 and correctly rounded, NaN -> 0; pct = (p2, p98) float on the device.  With
+ *   blue [N] != NULL that is the third byte instead (the all-zero-depth route, whose bytes the caller's generator draws).
+ * raster_colors_depth: colors[T][N][3]: 0 where visible[t][n] == 0 (NULL: all visible), else lut[index of
+ *   (clip(z, p2_t, p98_t) - p2_t) / (p98_t - p2_t)] in double where p98_t > p2_t, lut[0] otherwise; pct [T][2] double; lut [258][3] =
+ *   256 colormap entries + under + over (matplotlib's Colormap.__call__ indexing: int(x * 256), 256 -> 255, NaN -> black).
+ * raster_colors_cosine: colors[N][3] = clip((code + 1) / 2, 0, 1) * 255 truncated, float32, NaN -> 0; code [N][3].
+ * colors must be 4-byte aligned. */
+#define FLEXAM_SELECT_MAX_RANKS 8
+#define FLEXAM_SELECT_WS_SEGMENT_BYTES 8320
+int flexam_select_f32(const float* src, int stride, int comp, int transform, const unsigned char* mask, int S, int64_t seg_len,
+                      const int64_t* ranks, int K, float* values, int64_t* info, void* ws, int64_t ws_bytes, void* stream);
+int flexam_select_lerp(const float* values, const double* gamma, const int64_t* info, int S, int Q, int f32_form, void* out, void* stream);
+int flexam_raster_colors_tracking(const float* points, int64_t N, int H, int W, const float* pct, const unsigned char* blue,
+                                  unsigned char* colors, void* stream);
+int flexam_raster_colors_depth(const float* points, const unsigned char* visible, int T, int64_t N, const double* pct,
+                               const unsigned char* lut, unsigned char* colors, void* stream);
+int flexam_raster_colors_cosine(const float* code, int64_t N, unsigned char* colors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
