@@ -94,8 +94,8 @@ class DiTEngine:
         self.patch = tuple(c["patch_size"])
         self.out_dim, self.in_dim = c["out_dim"], c["in_dim"]
         self.text_len, self.freq_dim = c["text_len"], c["freq_dim"]
-        if self.hd != 128:
-            raise RuntimeError(f"flexam_amd: head_dim {self.hd} unsupported by the HIP attention kernel (128 only)")
+        if self.hd != hip.ATTN_HEAD_DIM:
+            raise RuntimeError(f"flexam_amd: head_dim {self.hd} unsupported by the HIP attention kernel ({hip.ATTN_HEAD_DIM} only)")
         if self.patch != (1, 2, 2):
             raise RuntimeError("flexam_amd: only patch_size (1,2,2) is implemented")
         self.device = model.patch_embedding.weight.device
@@ -418,7 +418,7 @@ class DiTEngine:
         # RECORDS (one per 64 keys) instead of bf16 rows, so every chunk is a whole number of 64-key tiles: the padding unit is 64 x ranks
         sage_asked = env.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION"
         sage_gather = sage_asked and self.fused and sp > 1 and sp_mode == "allgather" and overlap == 0 and pieces == 1
-        unit = sp * 64 if sage_gather else sp
+        unit = sp * hip.ATTN_KV_TILE if sage_gather else sp
         Lp = -(-L // unit) * unit
         # the reference reads the switch at every attention call (attention_utils.py:195); quantised self-attention on one rank: MXFP8
         # operands of the rank's tokens.  Sequence parallel with the all-to-all over heads: every rank ends up with ALL tokens of its
@@ -442,7 +442,7 @@ class DiTEngine:
         lc = Lp // sp
         return _Mode(B=B, Lp=Lp, lc=lc, tok0=self.sp_rank * lc, R=R, rows_per_batch=rows_per_batch, only_row=only_row,
                      per_layer=per_layer, share0=bool(share0), sage=bool(sage), sage_gather=bool(sage_gather),
-                     sage_fused=bool(sage) and self.nh == 24 and self.hd == 128,
+                     sage_fused=bool(sage) and self.nh == 24 and self.hd == hip.ATTN_HEAD_DIM,
                      fp8=self.fp8, fp8_oproj=self.fp8 and env.get("FLEXAM_FP8_OPROJ", "0") == "1",
                      ffn_apriori=env.get("FLEXAM_FP8_FFN_APRIORI", "1") != "0",
                      sp=sp, rank=self.sp_rank, sp_mode=sp_mode, sp_pieces=pieces, sp_overlap_level=overlap,
@@ -869,18 +869,6 @@ class DiTEngine:
         hip.host_op(lambda: wait("back", range(B)))
         return recv2.view(sp * B * lc, G), ws["a2a_koff"]
 
-    @staticmethod
-    def _splits_for(units: int, tiles: int, n_cu: int = 256) -> int:
-        """Key ranges per work unit for a partial-attention call: fill whole rounds of the CUs, every range >= 8 key tiles."""
-        best, best_cost = 1, float(-(-units // n_cu))
-        for s in range(2, 9):
-            if tiles // s < 8:
-                break
-            cost = -(-units * s // n_cu) / s + 0.04
-            if cost < best_cost * 0.97:
-                best, best_cost = s, cost
-        return best
-
     def _proj(self, hbuf, a8sa, layer, p, wname, bname, rows, out):
         """out = h @ W[rows]^T + b[rows]: bf16 MFMA, or fp8 MFMA on the row-quantised h (`a8sa` = (bytes, row scales)) with the
         per-channel scales of the same weight rows."""
@@ -913,9 +901,10 @@ class DiTEngine:
         if "kv_send" not in ws:
             ws["kv_send"] = torch.empty(G, B, lc, 2 * cb, device=dev, dtype=BF16)
             ws["kv_cat"] = torch.empty(G, B, L, 2 * cb, device=dev, dtype=BF16)
-            units = B * hg * ((lc + 255) // 256)
+            units = hip.attn_units(B * hg, lc)
             ranges = [n_loc, min(tok0, Lr), max(0, Lr - tok0 - lc)]                      # local, before, after
-            ws["kv_splits"] = [self._splits_for(units, (n + 63) // 64) if n else 0 for n in ranges]
+            # no CU count passed: these ranges are planned for the planner's default of 256 CUs, whatever FLEXAM_CU_BUDGET says
+            ws["kv_splits"] = [hip.attn_partial_splits(units, hip.attn_kv_tiles(n)) if n else 0 for n in ranges]
             ws["kv_part"] = hip.attn_partial_workspace(B, hg, lc, sum(hip.attn_effective_splits(n, s) for n, s in zip(ranges, ws["kv_splits"]) if n), dev)
         cd = self.cond
         send, cat = ws["kv_send"], ws["kv_cat"]

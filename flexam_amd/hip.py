@@ -276,10 +276,13 @@ def _ws_slot(cache: dict, key, make):
     return hit
 
 
+def _ws_key(device, stream: int):
+    return (device.index if device.index is not None else torch.cuda.current_device(), stream)
+
+
 def _gemm_workspace(device, stream: int):
     """Tail split-K scratch (64 MiB of partial-sum slabs) handed to every GEMM call, per (device, stream)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), stream)
-    return _ws_slot(_GEMM_WS, key, lambda: torch.empty(GEMM_WS_BYTES, device=device, dtype=torch.uint8))
+    return _ws_slot(_GEMM_WS, _ws_key(device, stream), lambda: torch.empty(GEMM_WS_BYTES, device=device, dtype=torch.uint8))
 
 
 def gemm(a, w, bias=None, out=None, epilogue=EPI_NONE, out_dtype=BF16, a_koff=None, m=None, k=None):
@@ -400,13 +403,31 @@ def gemm_fp8_gate_residual(a8, a_scale, w8, w_scale, bias, x, gate=None, gate_ro
 
 
 # ----------------------------------------------------------------------------- attention
+# The kernels' geometry, from the header (tests/test_abi_cpu.py holds the header to QBLK, KVBLK, HD and REC_BYTES of the sources): a
+# work unit is ATTN_Q_BLOCK query rows of one (batch, head), keys go in tiles of ATTN_KV_TILE, an MXFP8 record holds one key tile
+ATTN_Q_BLOCK = abi.CONSTANTS["FLEXAM_ATTN_Q_BLOCK"]
+ATTN_KV_TILE = abi.CONSTANTS["FLEXAM_ATTN_KV_TILE"]
+ATTN_HEAD_DIM = abi.CONSTANTS["FLEXAM_ATTN_HEAD_DIM"]
+ATTN8_REC_BYTES = abi.CONSTANTS["FLEXAM_ATTN8_REC_BYTES"]
+ATTN_PRESCALED = abi.CONSTANTS["FLEXAM_ATTN_PRESCALED"]
+
+
+def attn_units(batch_heads: int, lq: int) -> int:
+    """Work units of a launch: one per (batch, head) and block of ATTN_Q_BLOCK query rows."""
+    return batch_heads * -(-lq // ATTN_Q_BLOCK)
+
+
+def attn_kv_tiles(lk: int) -> int:
+    return -(-lk // ATTN_KV_TILE)
+
+
 def attn_split_plan(batch_heads: int, lq: int, lk: int, n_cu: int = 256):
     """(kv_splits, split_from_unit) for flexam_attn_fwd_splitkv.  W = batch_heads * ceil(lq/256) work units of ceil(lk/64) key
     tiles; the launch takes ceil(W/n_cu) rounds.  Cutting only the units of the last, partial round into S key ranges turns
     that round into ceil(rem*S/n_cu)/S of a round (+ 4 % per pass for the partial outputs and the merge); S is kept only if the
     whole launch gets more than 2 % shorter and every range keeps at least 8 key tiles."""
-    w = batch_heads * ((lq + 255) // 256)
-    tiles = (lk + 63) // 64
+    w = attn_units(batch_heads, lq)
+    tiles = attn_kv_tiles(lk)
     full, rem = (w // n_cu) * n_cu, w % n_cu
     if rem == 0:
         return 1, w
@@ -421,14 +442,62 @@ def attn_split_plan(batch_heads: int, lq: int, lk: int, n_cu: int = 256):
     return (best, full) if best > 1 else (1, w)
 
 
-def attn_kv_splits(batch_heads: int, lq: int, lk: int, n_cu: int = 256) -> int:
-    return attn_split_plan(batch_heads, lq, lk, n_cu)[0]
+def attn_partial_splits(units: int, tiles: int, n_cu: int = 256) -> int:
+    """Key ranges per work unit for a partial-attention call: fill whole rounds of the CUs, every range >= 8 key tiles."""
+    best, best_cost = 1, float(-(-units // n_cu))
+    for s in range(2, 9):
+        if tiles // s < 8:
+            break
+        cost = -(-units * s // n_cu) / s + 0.04
+        if cost < best_cost * 0.97:
+            best, best_cost = s, cost
+    return best
+
+
+def attn_effective_splits(lk: int, splits: int) -> int:
+    """Key ranges a request for `splits` really gives: ranges hold whole 64-key tiles, empty trailing ranges are dropped."""
+    tiles = attn_kv_tiles(lk)
+    splits = max(1, min(int(splits), tiles))
+    per = -(-tiles // splits)
+    return -(-tiles // per)
+
+
+def _packed_heads(who, *tensors):
+    """[B, L, H, D] views (None skipped) whose heads lie side by side in a row, as the kernels address them: column h * D."""
+    D = tensors[0].shape[3]
+    for t in tensors:
+        if t is not None and (t.stride(3) != 1 or t.stride(2) != D):
+            raise RuntimeError(f"{who}: heads must be packed along the row (stride(2) == head_dim, stride(3) == 1)")
+
+
+def _softmax_scale(softmax_scale, prescaled, head_dim):
+    return ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else head_dim ** -0.5)
+
+
+def _split_request(kv_splits, split_from_unit, batch_heads, lq, lk):
+    """(S, from_unit) of a split-KV launch.  kv_splits None: attn_split_plan (only the last, partial round of the CUs is split); an
+    explicit kv_splits splits every unit unless split_from_unit is given too."""
+    if kv_splits is None:
+        return attn_split_plan(batch_heads, lq, lk, num_cus())
+    return int(kv_splits), (0 if split_from_unit is None else int(split_from_unit))
+
+
+def _partials(slots, units, device):
+    """(ws_o, ws_ml): per slot, unit and query row the un-normalised output and the (reference, row sum) pair of a partial softmax."""
+    return (torch.empty(slots, units, ATTN_Q_BLOCK, ATTN_HEAD_DIM, device=device, dtype=F32),
+            torch.empty(slots, units, ATTN_Q_BLOCK, 2, device=device, dtype=F32))
 
 
 _ATTN_WS = {}
 
 
-ATTN_PRESCALED = abi.CONSTANTS["FLEXAM_ATTN_PRESCALED"]
+def _split_scratch(device, stream: int, S: int, n: int):
+    """(ws_o, ws_ml) of a split-KV launch that cuts n units into S key ranges: per-shape scratch per (device, stream), reused across
+    launches (stream-ordered) and re-made when the shape changes."""
+    key = _ws_key(device, stream)
+    if key in _ATTN_WS and _ATTN_WS[key][0] != (S, n):
+        del _ATTN_WS[key]
+    return _ws_slot(_ATTN_WS, key, lambda: ((S, n), *_partials(S, n, device)))[1:]
 
 
 def attn_fwd_lastkey(q, k, v, last_key_multiplicity, out=None, softmax_scale=None, prescaled=False):
@@ -436,14 +505,12 @@ def attn_fwd_lastkey(q, k, v, last_key_multiplicity, out=None, softmax_scale=Non
     flexam_hip.h); same layouts as attn_fwd, no split-KV (short contexts)."""
     B, Lq, H, D = q.shape
     Lk = k.shape[1]
-    for t in (q, k, v):
-        if t.stride(3) != 1 or t.stride(2) != D:
-            raise RuntimeError("attn_fwd_lastkey: heads must be packed along the row (stride(2) == head_dim, stride(3) == 1)")
+    _packed_heads("attn_fwd_lastkey", q, k, v)
     if out is None:
         out = torch.empty(B, Lq, H, D, device=q.device, dtype=BF16)
-    scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
     _call("flexam_attn_fwd_lastkey", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
-          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, scale, float(last_key_multiplicity))
+          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, _softmax_scale(softmax_scale, prescaled, D),
+          float(last_key_multiplicity))
     return out
 
 
@@ -454,46 +521,22 @@ def attn_fwd(q, k, v, out=None, softmax_scale=None, kv_splits=None, split_from_u
     prescaled: q already carries softmax_scale * log2(e) (folded into its producer before the rounding to bf16)."""
     B, Lq, H, D = q.shape
     Lk = k.shape[1]
-    for t in (q, k, v):
-        if t.stride(3) != 1 or t.stride(2) != D:
-            raise RuntimeError("attn_fwd: heads must be packed along the row (stride(2) == head_dim, stride(3) == 1)")
+    _packed_heads("attn_fwd", q, k, v)
     if out is None:
         out = torch.empty(B, Lq, H, D, device=q.device, dtype=BF16)
-    scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
-    units = B * H * ((Lq + 255) // 256)
-    if kv_splits is None:
-        S, from_unit = attn_split_plan(B * H, Lq, Lk, num_cus())
-    else:
-        S, from_unit = int(kv_splits), (0 if split_from_unit is None else int(split_from_unit))
+    S, from_unit = _split_request(kv_splits, split_from_unit, B * H, Lq, Lk)
+    args = (_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16), v.stride(0), v.stride(1),
+            _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, _softmax_scale(softmax_scale, prescaled, D))
     if S <= 1:
-        _call("flexam_attn_fwd", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
-              v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, scale)
+        _call("flexam_attn_fwd", *args)
         return out
-    n = units - from_unit
-    st = _stream()
-    slot, key = (q.device.index if q.device.index is not None else torch.cuda.current_device(), st), (S, n)
-    if _ATTN_WS.get(slot, (None,))[0] != key:   # per-shape scratch per (device, stream), reused across launches (stream-ordered)
-        _ATTN_WS.pop(slot, None)
-        _ws_slot(_ATTN_WS, slot, lambda: (key, torch.empty(S, n, 256, D, device=q.device, dtype=F32),
-                                          torch.empty(S, n, 256, 2, device=q.device, dtype=F32)))
-    _, ws_o, ws_ml = _ws_slot(_ATTN_WS, slot, None)
-    _call("flexam_attn_fwd_splitkv", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
-          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, Lk, D, scale, S, from_unit, _ptr(ws_o, F32),
-          _ptr(ws_ml, F32))
+    ws_o, ws_ml = _split_scratch(q.device, _stream(), S, attn_units(B * H, Lq) - from_unit)
+    _call("flexam_attn_fwd_splitkv", *args, S, from_unit, _ptr(ws_o, F32), _ptr(ws_ml, F32))
     return out
 
 
-def attn_effective_splits(lk: int, splits: int) -> int:
-    """Key ranges a request for `splits` really gives: ranges hold whole 64-key tiles, empty trailing ranges are dropped."""
-    tiles = (lk + 63) // 64
-    splits = max(1, min(int(splits), tiles))
-    per = -(-tiles // splits)
-    return -(-tiles // per)
-
-
 def attn_partial_workspace(B, H, Lq, n_slots, device):
-    units = B * H * ((Lq + 255) // 256)
-    return (torch.empty(n_slots, units, 256, 128, device=device, dtype=F32), torch.empty(n_slots, units, 256, 2, device=device, dtype=F32))
+    return _partials(n_slots, attn_units(B * H, Lq), device)
 
 
 def attn_fwd_partial(q, k, v, ws, slot0, kv_splits=1, softmax_scale=None, prescaled=False):
@@ -501,38 +544,34 @@ def attn_fwd_partial(q, k, v, ws, slot0, kv_splits=1, softmax_scale=None, presca
     returns the number of slots written."""
     B, Lq, H, D = q.shape
     Lk = k.shape[1]
-    for t in (q, k, v):
-        if t.stride(3) != 1 or t.stride(2) != D:
-            raise RuntimeError("attn_fwd_partial: heads must be packed along the row (stride(2) == head_dim, stride(3) == 1)")
+    _packed_heads("attn_fwd_partial", q, k, v)
     S = attn_effective_splits(Lk, kv_splits)
     ws_o, ws_ml = ws
-    if slot0 + S > ws_o.shape[0] or ws_o.shape[1] != B * H * ((Lq + 255) // 256):
+    if slot0 + S > ws_o.shape[0] or ws_o.shape[1] != attn_units(B * H, Lq):
         raise RuntimeError("attn_fwd_partial: workspace too small for these slots / this query shape")
-    scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
     _call("flexam_attn_fwd_partial", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
-          v.stride(0), v.stride(1), B, H, Lq, Lk, D, scale, S, slot0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
+          v.stride(0), v.stride(1), B, H, Lq, Lk, D, _softmax_scale(softmax_scale, prescaled, D), S, slot0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
     return S
 
 
 def attn_merge(out, ws, n_slots, softmax_scale=None, prescaled=False):
     """out [B, Lq, H, 128] bf16 = the softmax over the union of the key sets of workspace slots 0 .. n_slots - 1."""
     B, Lq, H, D = out.shape
-    if out.stride(3) != 1 or out.stride(2) != D:
-        raise RuntimeError("attn_merge: heads must be packed along the row")
-    scale = ATTN_PRESCALED if prescaled else (softmax_scale if softmax_scale is not None else D ** -0.5)
-    _call("flexam_attn_merge", _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, D, scale, n_slots, _ptr(ws[0], F32),
-          _ptr(ws[1], F32))
+    _packed_heads("attn_merge", out)
+    _call("flexam_attn_merge", _ptr(out, BF16), out.stride(0), out.stride(1), B, H, Lq, D, _softmax_scale(softmax_scale, prescaled, D),
+          n_slots, _ptr(ws[0], F32), _ptr(ws[1], F32))
     return out
 
 
-ATTN8_REC_BYTES = 18432
+def _fp8_operands(B, H, L):
+    """(shape, dtype) of q8, qs and kv8 (see flexam_hip.h): e4m3 query rows, four E8M0 scale bytes per row, one record per key tile."""
+    lp = attn_units(1, L) * ATTN_Q_BLOCK               # query rows come in whole blocks
+    return ((B, H, lp, ATTN_HEAD_DIM), U8), ((B, H, lp), I32), ((B, H, attn_kv_tiles(L), ATTN8_REC_BYTES), U8)
 
 
 def attn_fp8_buffers(B, H, L, device):
     """(q8, qs, kv8) for attn_fp8_pack / attn_fwd_fp8 at this shape (see flexam_hip.h)."""
-    lp, tiles = -(-L // 256) * 256, -(-L // 64)
-    return (torch.zeros(B, H, lp, 128, device=device, dtype=torch.uint8), torch.zeros(B, H, lp, device=device, dtype=torch.int32),
-            torch.zeros(B, H, tiles, ATTN8_REC_BYTES, device=device, dtype=torch.uint8))      # zeros: rmsnorm_rope_mx never writes the padding rows
+    return tuple(torch.zeros(shape, device=device, dtype=dt) for shape, dt in _fp8_operands(B, H, L))      # zeros: rmsnorm_rope_mx never writes the padding rows
 
 
 def _check_fp8_bufs(bufs, B, H, L, device, who):
@@ -542,10 +581,7 @@ def _check_fp8_bufs(bufs, B, H, L, device, who):
     here ever writes."""
     if not isinstance(bufs, (tuple, list)) or len(bufs) != 3:
         raise RuntimeError(f"{who}: bufs must be the (q8, qs, kv8) triple of attn_fp8_buffers")
-    q8, qs, kv8 = bufs
-    lp, tiles = -(-L // 256) * 256, -(-L // 64)
-    want = ((q8, (B, H, lp, 128), torch.uint8), (qs, (B, H, lp), torch.int32), (kv8, (B, H, tiles, ATTN8_REC_BYTES), torch.uint8))
-    for t, shape, dt in want:
+    for t, (shape, dt) in zip(bufs, _fp8_operands(B, H, L)):
         if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous() or t.device != torch.device(device):
             raise RuntimeError(f"{who}: operand buffers are not attn_fp8_buffers(B={B}, H={H}, L={L}) on {device}: got {tuple(t.shape)} {t.dtype} "
                                f"on {t.device}, want {shape} {dt}")
@@ -554,9 +590,9 @@ def _check_fp8_bufs(bufs, B, H, L, device, who):
 def attn_fp8_pack(q, k, v, bufs=None):
     """q, k, v [B, L, H, 128] bf16 (q prescaled by softmax_scale * log2 e) -> the MXFP8 operand buffers of attn_fwd_fp8."""
     B, L, H, D = v.shape
-    for t in (q, k, v):
-        if t is not None and (t.stride(3) != 1 or t.stride(2) != D or t.shape != v.shape):
-            raise RuntimeError("attn_fp8_pack: q, k, v must be [B, L, H, 128] with packed heads")
+    if any(t is not None and t.shape != v.shape for t in (q, k)):
+        raise RuntimeError(f"attn_fp8_pack: q, k, v must be [B, L, H, {ATTN_HEAD_DIM}], all of one shape")
+    _packed_heads("attn_fp8_pack", v, q, k)
     if (q is None) != (k is None):
         raise RuntimeError("attn_fp8_pack: q and k go together (both None: V only, after rmsnorm_rope_mx)")
     if bufs is None:
@@ -573,41 +609,37 @@ def rmsnorm_rope_mx(q, wq, k, wk, bufs, rope_cos, rope_sin, tokens_per_batch, to
     """RMSNorm + RoPE of q and k ([M, 3072] bf16 views) written as the MXFP8 operands of attn_fwd_fp8 (Q rows, K image and scales);
     the V half of `bufs` comes from attn_fp8_pack(None, None, v, bufs)."""
     M, C, ldq = _rows(q)
-    if tokens_per_batch <= 0 or M % tokens_per_batch or C != heads * 128:
-        raise RuntimeError(f"rmsnorm_rope_mx: {M} rows of {C} columns do not tile batches of {tokens_per_batch} tokens x {heads} heads x 128")
+    if tokens_per_batch <= 0 or M % tokens_per_batch or C != heads * ATTN_HEAD_DIM:
+        raise RuntimeError(f"rmsnorm_rope_mx: {M} rows of {C} columns do not tile batches of {tokens_per_batch} tokens x {heads} heads x "
+                           f"{ATTN_HEAD_DIM}")
     _check_fp8_bufs(bufs, M // tokens_per_batch, heads, tokens_per_batch, q.device, "rmsnorm_rope_mx")
     q8, qs, kv8 = bufs
     _call("flexam_rmsnorm_rope_mx", _ptr(q, BF16), ldq, _ptr(wq, F32), _ptr(k, BF16), k.stride(0), _ptr(wk, F32), _raw(q8), _raw(qs),
-          _raw(kv8), M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, heads, 128)
+          _raw(kv8), M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, heads, ATTN_HEAD_DIM)
     return bufs
+
+
+def _fp8_split_words(device, kv_splits, split_from_unit, batch_heads, lq, lk):
+    """(kv_splits, split_from_unit, ws_o, ws_ml) as the MXFP8 entry points take them: 1, 0 and no workspace when nothing is split."""
+    S, from_unit = _split_request(kv_splits, split_from_unit, batch_heads, lq, lk)
+    if S <= 1:
+        return 1, 0, None, None
+    ws_o, ws_ml = _split_scratch(device, _stream(), S, attn_units(batch_heads, lq) - from_unit)
+    return S, from_unit, _ptr(ws_o, F32), _ptr(ws_ml, F32)
 
 
 def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None):
     """Self-attention from packed MXFP8 operands (attn_fp8_pack) -> out [B, L, H, 128] bf16."""
     q8, qs, kv8 = bufs
-    B, H, D = q8.shape[0], q8.shape[1], 128
+    B, H, D = q8.shape[0], q8.shape[1], ATTN_HEAD_DIM
     _check_fp8_bufs(bufs, B, H, L, q8.device, "attn_fwd_fp8")
     if out is None:
         out = torch.empty(B, L, H, D, device=q8.device, dtype=BF16)
-    if out.stride(3) != 1 or out.stride(2) != D or tuple(out.shape) != (B, L, H, D):
-        raise RuntimeError(f"attn_fwd_fp8: out must be [B={B}, L={L}, H={H}, 128] with heads packed along the row, got {tuple(out.shape)}")
-    units = B * H * ((L + 255) // 256)
-    if kv_splits is None:
-        S, from_unit = attn_split_plan(B * H, L, L, num_cus())
-    else:
-        S, from_unit = int(kv_splits), (0 if split_from_unit is None else int(split_from_unit))
-    ws_o = ws_ml = None
-    if S > 1:
-        n = units - from_unit
-        st = _stream()
-        slot, key = (q8.device.index if q8.device.index is not None else torch.cuda.current_device(), st), (S, n)
-        if _ATTN_WS.get(slot, (None,))[0] != key:
-            _ATTN_WS.pop(slot, None)
-            _ws_slot(_ATTN_WS, slot, lambda: (key, torch.empty(S, n, 256, D, device=q8.device, dtype=F32),
-                                              torch.empty(S, n, 256, 2, device=q8.device, dtype=F32)))
-        _, ws_o, ws_ml = _ws_slot(_ATTN_WS, slot, None)
-    _call("flexam_attn_fwd_fp8", _raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D, max(S, 1),
-          from_unit if S > 1 else 0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
+    _packed_heads("attn_fwd_fp8", out)
+    if tuple(out.shape) != (B, L, H, D):
+        raise RuntimeError(f"attn_fwd_fp8: out must be [B={B}, L={L}, H={H}, {D}] with heads packed along the row, got {tuple(out.shape)}")
+    _call("flexam_attn_fwd_fp8", _raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D,
+          *_fp8_split_words(q8.device, kv_splits, split_from_unit, B * H, L, L))
     return out
 
 
@@ -615,34 +647,23 @@ def attn_fwd_fp8_chunked(q8, qs, kv8_chunks, lq, lk, out=None):
     """Attention of `lq` local queries (q8 / qs of attn_fp8_buffers(B, H, lq)) over `lk` keys whose MXFP8 records come in CHUNKS:
     kv8_chunks uint8 [n_chunks, B, H, chunk_tiles, ATTN8_REC_BYTES], chunk c holding the keys [c, c + 1) * chunk_tiles * 64 -- the
     rank-major result of all-gathering every sequence-parallel rank's own records.  -> out [B, lq, H, 128] bf16."""
-    B, H, D = q8.shape[0], q8.shape[1], 128
-    lp = -(-lq // 256) * 256
-    if tuple(q8.shape) != (B, H, lp, D) or tuple(qs.shape) != (B, H, lp) or q8.dtype != U8 or qs.dtype != torch.int32 or not (q8.is_contiguous() and qs.is_contiguous()):
-        raise RuntimeError(f"attn_fwd_fp8_chunked: q8 / qs are not the query buffers of attn_fp8_buffers(B={B}, H={H}, L={lq})")
+    B, H, D = q8.shape[0], q8.shape[1], ATTN_HEAD_DIM
+    for t, (shape, dt) in zip((q8, qs), _fp8_operands(B, H, lq)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise RuntimeError(f"attn_fwd_fp8_chunked: q8 / qs are not the query buffers of attn_fp8_buffers(B={B}, H={H}, L={lq})")
     if (kv8_chunks.dim() != 5 or kv8_chunks.dtype != U8 or not kv8_chunks.is_contiguous() or tuple(kv8_chunks.shape[1:3]) != (B, H)
             or kv8_chunks.shape[4] != ATTN8_REC_BYTES or kv8_chunks.device != q8.device):
         raise RuntimeError(f"attn_fwd_fp8_chunked: records must be contiguous uint8 [chunks, B={B}, H={H}, chunk_tiles, {ATTN8_REC_BYTES}], got {tuple(kv8_chunks.shape)}")
     n_chunks, chunk_tiles = kv8_chunks.shape[0], kv8_chunks.shape[3]
-    if not 0 < lk <= n_chunks * chunk_tiles * 64:
+    if not 0 < lk <= n_chunks * chunk_tiles * ATTN_KV_TILE:
         raise RuntimeError(f"attn_fwd_fp8_chunked: {lk} keys do not fit {n_chunks} chunks of {chunk_tiles} tiles")
     if out is None:
         out = torch.empty(B, lq, H, D, device=q8.device, dtype=BF16)
-    if out.stride(3) != 1 or out.stride(2) != D or tuple(out.shape) != (B, lq, H, D):
-        raise RuntimeError(f"attn_fwd_fp8_chunked: out must be [B={B}, L={lq}, H={H}, 128] with heads packed along the row, got {tuple(out.shape)}")
-    units = B * H * ((lq + 255) // 256)
-    S, from_unit = attn_split_plan(B * H, lq, lk, num_cus())
-    ws_o = ws_ml = None
-    if S > 1:
-        n = units - from_unit
-        st = _stream()
-        slot, key = (q8.device.index if q8.device.index is not None else torch.cuda.current_device(), st), (S, n)
-        if _ATTN_WS.get(slot, (None,))[0] != key:
-            _ATTN_WS.pop(slot, None)
-            _ws_slot(_ATTN_WS, slot, lambda: (key, torch.empty(S, n, 256, D, device=q8.device, dtype=F32),
-                                              torch.empty(S, n, 256, 2, device=q8.device, dtype=F32)))
-        _, ws_o, ws_ml = _ws_slot(_ATTN_WS, slot, None)
+    _packed_heads("attn_fwd_fp8_chunked", out)
+    if tuple(out.shape) != (B, lq, H, D):
+        raise RuntimeError(f"attn_fwd_fp8_chunked: out must be [B={B}, L={lq}, H={H}, {D}] with heads packed along the row, got {tuple(out.shape)}")
     _call("flexam_attn_fwd_fp8_chunked", _raw(q8), _raw(qs), _raw(kv8_chunks), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, lq, lk,
-          chunk_tiles, D, max(S, 1), from_unit if S > 1 else 0, _ptr(ws_o, F32), _ptr(ws_ml, F32))
+          chunk_tiles, D, *_fp8_split_words(q8.device, None, None, B * H, lq, lk))
     return out
 
 

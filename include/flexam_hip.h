@@ -122,6 +122,12 @@ int flexam_gemm_fp8_gelu_q(const void* A, int64_t lda, const float* a_scale, con
  * by scale * log2(e) before its one rounding to bf16 (the DiT engine folds that factor into the RMSNorm weight of q), so the
  * scores are in exp2 units and the kernel saves one FMA per score: o = softmax2(q k^T) v with softmax2 built on 2^x. */
 #define FLEXAM_ATTN_PRESCALED (-1.0f)
+/* The kernels' geometry, for whoever sizes their buffers: a work unit is FLEXAM_ATTN_Q_BLOCK query rows of one (batch, head), keys
+ * are taken in tiles of FLEXAM_ATTN_KV_TILE, and one MXFP8 key / value record (below) holds one such tile of one head. */
+#define FLEXAM_ATTN_Q_BLOCK 256
+#define FLEXAM_ATTN_KV_TILE 64
+#define FLEXAM_ATTN_HEAD_DIM 128
+#define FLEXAM_ATTN8_REC_BYTES 18432
 int flexam_attn_fwd(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                     int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int Lk,
                     int head_dim, float softmax_scale, void* stream);
@@ -163,8 +169,8 @@ int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq,
  * VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION, FlexAM/models/attention_utils.py:195-203 (the reference calls the third-party
  * `sageattn`, which quantises Q, K and the P.V product; kept here: its contract, softmax attention within a stated tolerance).
  * flexam_attn_fp8_pack: q, k, v bf16 [B, L, H, 128] as flexam_attn_fwd takes them (q carrying softmax_scale * log2 e, i.e. the
- * FLEXAM_ATTN_PRESCALED form) -> q8 [B][H][Lp][128] e4m3, qs [B][H][Lp] four E8M0 bytes per row, kv8 [B][H][T] records of 18432
- * bytes (K tile image, V^T tile image with the key order the P.V operand needs, their scales), Lp = ceil(L / 256) * 256,
+ * FLEXAM_ATTN_PRESCALED form) -> q8 [B][H][Lp][128] e4m3, qs [B][H][Lp] four E8M0 bytes per row, kv8 [B][H][T] records of
+ * FLEXAM_ATTN8_REC_BYTES bytes (K tile image, V^T tile image with the key order the P.V operand needs, their scales), Lp = ceil(L / 256) * 256,
  * T = ceil(L / 64); rows past L are written as zeros; q = k = NULL: only the V half of the records is written.  flexam_attn_fwd_fp8: o [B, L, H, 128] bf16 from those buffers; kv_splits /
  * split_from_unit / ws_o / ws_ml as flexam_attn_fwd_splitkv (kv_splits = 1: no workspace). */
 int flexam_attn_fp8_pack(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,

@@ -207,6 +207,21 @@ def test_header_constants_are_read_not_evaluated():
     assert abi.CONSTANTS["FLEXAM_E_ARG"] == -1 and abi.CONSTANTS["FLEXAM_HIP_VERSION"] == 2
 
 
+def test_attention_geometry_constants_are_the_kernels():
+    """The header's attention geometry -- what hip.py and the engine size split-KV workspaces and MXFP8 buffers from -- against the
+    constexprs the kernels are compiled with, read from the sources by name: a renamed or re-valued constant fails here, it does not
+    mis-size a buffer."""
+    from flexam_amd import abi, hip
+    ties = (("FLEXAM_ATTN_Q_BLOCK", "attn.hip", "QBLK"), ("FLEXAM_ATTN_KV_TILE", "attn.hip", "KVBLK"),
+            ("FLEXAM_ATTN_HEAD_DIM", "attn.hip", "HD"), ("FLEXAM_ATTN8_REC_BYTES", "attn_fp8.inc", "REC_BYTES"))
+    for macro, source, name in ties:
+        text = open(os.path.join(ROOT, "flexam_amd", "csrc", source)).read()
+        found = re.findall(rf"^constexpr int\b[^;]*?\b{name} = (\d+)\s*[,;]", text, flags=re.M)
+        assert len(found) == 1, f"csrc/{source}: `constexpr int {name} = <integer>` found {len(found)} times"
+        assert int(found[0]) == abi.CONSTANTS[macro], f"{macro} = {abi.CONSTANTS[macro]}, csrc/{source} has {name} = {found[0]}"
+    assert (hip.ATTN_Q_BLOCK, hip.ATTN_KV_TILE, hip.ATTN_HEAD_DIM, hip.ATTN8_REC_BYTES) == tuple(abi.CONSTANTS[m] for m, _, _ in ties)
+
+
 def test_recorder_takes_recordable_from_the_header(libpath):
     """What a recorder records is what the generator makes replayable -- the header's stream-ordered prototypes -- except
     flexam_lincomb_f32, which reads host arrays during the call."""

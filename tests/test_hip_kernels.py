@@ -414,6 +414,37 @@ def test_attention_one_launch_tail_equals_two_launches(H, monkeypatch, b, h, lq,
     assert_bf16_close(one.cpu(), _attn_ref(q.cpu(), k.cpu(), v.cpu()), ulps=2.0, atol=6e-3, msg="one-launch tail vs oracle")
 
 
+def test_attention_split_scratch_follows_the_request_and_the_stream(H):
+    """The split-KV scratch (hip._ATTN_WS) is held per (device, stream) for the (S, n) of the last call there: a request of another
+    shape re-makes it instead of reusing slabs of the wrong size, the first request run again gives the same bits, and a second stream
+    gets an entry of its own."""
+    g = torch.Generator().manual_seed(300192)
+    b, h, lq, lk = 1, 2, 300, 192                        # 2 heads x 2 query blocks = 4 units, 3 key tiles
+    q = bf(torch.randn(b, lq, h, 128, generator=g))
+    k = bf(torch.randn(b, lk, h, 128, generator=g))
+    v = bf(torch.randn(b, lk, h, 128, generator=g))
+    ref = _attn_ref(q, k, v)
+    qd, kd, vd = q.to(dev()), k.to(dev()), v.to(dev())
+    main, side = torch.cuda.current_stream(dev()), torch.cuda.Stream(dev())
+
+    def held(stream):
+        return H._ATTN_WS[(dev().index, stream.cuda_stream)][0]
+    first = H.attn_fwd(qd, kd, vd, kv_splits=2, split_from_unit=1)
+    assert held(main) == (2, 3)
+    every = H.attn_fwd(qd, kd, vd, kv_splits=3)          # every unit split: scratch of another shape
+    assert held(main) == (3, 4)
+    again = H.attn_fwd(qd, kd, vd, kv_splits=2, split_from_unit=1)
+    side.wait_stream(main)
+    with torch.cuda.stream(side):
+        other = H.attn_fwd(qd, kd, vd, kv_splits=2, split_from_unit=1)
+    main.wait_stream(side)
+    for name, out in (("first", first), ("every unit split", every), ("first again", again), ("second stream", other)):
+        assert_bf16_close(out, ref, ulps=2.0, atol=6e-3, msg=f"split-KV scratch, {name}:")
+    assert torch.equal(first, again)
+    assert held(main) == (2, 3) and held(side) == (2, 3)
+    assert sum(1 for _, st in H._ATTN_WS if st in (main.cuda_stream, side.cuda_stream)) == 2
+
+
 def test_attention_split_plan():
     f = __import__("flexam_amd.hip", fromlist=["attn_split_plan"]).attn_split_plan
     assert f(48, 11648, 11648) == (3, 2048)    # one GPU: 2208 units = 8 full rounds + 160 units cut in 3
