@@ -27,52 +27,20 @@ from typing import List, Optional
 import torch
 
 from . import hip
+from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
 
 BF16, F32, I32, I64 = torch.bfloat16, torch.float32, torch.int32, torch.int64
 F8 = torch.float8_e4m3fn
 
 
-def _round_up(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
-
-
-class _ConvCL:
-    """A (1,kh,kw) convolution as an implicit GEMM over a padded channels-last image."""
-
-    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, cp_in: int, device):
-        co, ci = weight.shape[0], weight.shape[1]
-        kh, kw = weight.shape[-2], weight.shape[-1]
-        w = weight.detach().to(device, F32).reshape(co, ci, kh, kw).permute(0, 2, 3, 1)        # [co, kh, kw, ci]
-        wp = torch.zeros(co, kh, kw, cp_in, device=device, dtype=F32)
-        wp[..., :ci] = w
-        self.weight = wp.reshape(co, kh * kw * cp_in).to(BF16).contiguous()
-        self.bias = bias.detach().to(device, F32).contiguous()
-        self.kh, self.kw, self.cp_in, self.cout = kh, kw, cp_in, co
-        self._koff = {}
-
-    def koff(self, wp_img: int, device) -> torch.Tensor:
-        if wp_img not in self._koff:
-            offs = []
-            for dh in range(self.kh):
-                for dw in range(self.kw):
-                    base = ((dh - self.kh // 2) * wp_img + (dw - self.kw // 2)) * self.cp_in
-                    offs += [base + cb * 64 for cb in range(self.cp_in // 64)]
-            self._koff[wp_img] = torch.tensor(offs, dtype=I64, device=device)
-        return self._koff[wp_img]
-
-
-class _Image:
-    """Zero-padded channels-last bf16 image [F, H+2, W+2, Cp] with guard rows on both sides so that
-    every 3x3 tap offset of every padded position stays inside the allocation."""
-
-    def __init__(self, f, h, w, cp, device):
-        self.f, self.h, self.w, self.cp = f, h, w, cp
-        self.rows = f * (h + 2) * (w + 2)
-        guard = (w + 2) + 1
-        self.buf = torch.zeros((self.rows + 2 * guard) * cp, device=device, dtype=BF16)
-        self.img = self.buf[guard * cp:(guard + self.rows) * cp].view(f, h + 2, w + 2, cp)
-        self.mat = self.img.view(self.rows, cp)
+def _conv_cl(weight: torch.Tensor, bias: torch.Tensor, device) -> PackedConv:
+    """A (1,kh,kw) convolution of the cnn-block as an implicit GEMM over a padded channels-last image (GuardedImage).  K order
+    (dh, dw, channel block): tap-major, every tap a group of its own."""
+    co, ci = weight.shape[0], weight.shape[1]
+    kh, kw = weight.shape[-2], weight.shape[-1]
+    groups = [[Tap(0, dh - kh // 2, dw - kw // 2)] for dh in range(kh) for dw in range(kw)]
+    return PackedConv(weight.detach().to(device, F32).reshape(co, ci, kh * kw).permute(0, 2, 1), groups, bias, device)
 
 
 # What the block and head launches of one forward depend on apart from buffer contents and addresses, resolved once at the start of
@@ -129,18 +97,12 @@ class DiTEngine:
         # (qfloat8 storage, fp8_optimization.py: the e4m3 parameters outside the blocks -- embeddings, head, conv taps, biases and
         # norm rows -- are upcast here once, exactly; the block GEMM weights stay e4m3 in their packs, _Block.packed)
         small = lambda t: t.detach().to(dev).contiguous() if t.dtype in (BF16, F32) else (bf(t) if t.dtype == F8 else f32(t))
-
-        def pad_k(w2d):
-            n, k = w2d.shape
-            out = torch.zeros(n, _round_up(k, 64), device=dev, dtype=BF16)
-            out[:, :k] = w2d.detach().to(dev, BF16)
-            return out
-        self.pe_w, self.pe_b = pad_k(m.patch_embedding.weight.flatten(1)), f32(m.patch_embedding.bias)
+        self.pe_w, self.pe_b = pad_k(m.patch_embedding.weight.flatten(1), dev), f32(m.patch_embedding.bias)
         self.ref_w = self.ref_b = None
         if m.ref_conv is not None:
-            self.ref_w, self.ref_b = pad_k(m.ref_conv.weight.flatten(1)), f32(m.ref_conv.bias)
+            self.ref_w, self.ref_b = pad_k(m.ref_conv.weight.flatten(1), dev), f32(m.ref_conv.bias)
         self.head_w, self.head_b = bf(m.head.head.weight), f32(m.head.head.bias)
-        self.txt = [(pad_k(m.text_embedding[0].weight), f32(m.text_embedding[0].bias)),
+        self.txt = [(pad_k(m.text_embedding[0].weight, dev), f32(m.text_embedding[0].bias)),
                     (bf(m.text_embedding[2].weight), f32(m.text_embedding[2].bias))]
         self.time = [(small(l.weight), f32(l.bias)) for l in (m.time_embedding[0], m.time_embedding[2], m.time_projection[1])]
         self.dens = [(small(l.weight), f32(l.bias)) for l in (m.density_embedding[0], m.density_embedding[2], m.density_projection[1])]
@@ -160,11 +122,11 @@ class DiTEngine:
         self.hmod, self.hmdens = f32(m.head.modulation), f32(m.head.modulation_density)       # [1,2,d], [1,1,d]
         self.cnn = None
         if m.cnn_conv1 is not None:
-            cin = [_round_up(m.cnn_conv1[0].weight.shape[1], 64), 192, 192, 128]
+            cin = [round_up(m.cnn_conv1[0].weight.shape[1], 64), 192, 192, 128, 128]         # pixel widths of conv1..5's input images
             self.cnn = dict(
-                convs=[_ConvCL(getattr(m, f"cnn_conv{i}")[0].weight, getattr(m, f"cnn_conv{i}")[0].bias, cin[i - 1], dev) for i in range(1, 5)],
+                convs=[_conv_cl(getattr(m, f"cnn_conv{i}")[0].weight, getattr(m, f"cnn_conv{i}")[0].bias, dev) for i in range(1, 5)],
                 gn=[(f32(getattr(m, f"cnn_conv{i}")[1].weight), f32(getattr(m, f"cnn_conv{i}")[1].bias)) for i in range(1, 5)],
-                conv5=_ConvCL(m.cnn_conv5.weight, m.cnn_conv5.bias, 128, dev), groups=[24, 24, 12, 12], cp=cin)
+                conv5=_conv_cl(m.cnn_conv5.weight, m.cnn_conv5.bias, dev), groups=[24, 24, 12, 12], cp=cin)
 
     def set_parallel(self, sp_group, sp_rank: int, sp_size: int, world_group=None, world_size: int = None, cfg_size: int = 1,
                      cfg_row: int = 0):
@@ -272,21 +234,22 @@ class DiTEngine:
         _, f, h, w = control.shape
         cn = self.cnn
         rows = f * (h + 2) * (w + 2)
-        img = _Image(f, h, w, cn["cp"][0], dev)
+        image = lambda cp: GuardedImage(f, h, w, cp, dev, reach(w, cp), reach(w, cp))
+
+        def conv(c, img):
+            c.at(h + 2, w + 2, img.img.shape[-1])
+            return c.launch(img.mat, rows)
+        img = image(cn["cp"][0])
         hip.pack_cl(control.contiguous(), img.img, 0)
         hip.pack_cl(additional.contiguous(), img.img, control.shape[0])
-        prev = None
-        for i, conv in enumerate(cn["convs"]):
-            y = hip.gemm(img.mat, conv.weight, conv.bias, a_koff=conv.koff(w + 2, dev), m=rows, k=conv.weight.shape[1], out_dtype=F32)
-            cp_out = cn["cp"][i + 1] if i + 1 < 4 else 128
-            nxt = _Image(f, h, w, cp_out, dev)
+        for i, c in enumerate(cn["convs"]):
+            y = conv(c, img)
+            nxt = image(cn["cp"][i + 1])
             gamma, beta = cn["gn"][i]
             residual = img.img if i in (1, 3) else None                   # x2 = conv2(x1) + x1, x4 = conv4(x3) + x3
-            hip.groupnorm_silu_cl(y, conv.cout, f, h, w, cn["groups"][i], gamma, beta, nxt.img, residual=residual)
-            prev, img = img, nxt
-        c5 = cn["conv5"]
-        y = hip.gemm(img.mat, c5.weight, c5.bias, a_koff=c5.koff(w + 2, dev), m=rows, k=c5.weight.shape[1], out_dtype=F32)
-        return hip.unpack_cl(y, c5.cout, f, h, w)
+            hip.groupnorm_silu_cl(y, c.co, f, h, w, cn["groups"][i], gamma, beta, nxt.img, residual=residual)
+            img = nxt
+        return hip.unpack_cl(conv(cn["conv5"], img), cn["conv5"].co, f, h, w)
 
     def set_conditioning(self, context: List[torch.Tensor], y: Optional[torch.Tensor], full_ref: Optional[torch.Tensor],
                          additional_control: Optional[torch.Tensor], density: Optional[torch.Tensor], latent_shape,

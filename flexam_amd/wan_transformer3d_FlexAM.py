@@ -20,6 +20,7 @@ import torch.nn as nn
 from .cache_utils import TeaCache
 from .cfg_optimization import cfg_skip
 from .dit_engine import DiTEngine
+from .implicit_conv import pad_k
 from .rope import rope_angle_table
 
 F32 = torch.float32
@@ -86,12 +87,7 @@ class HipLinear(nn.Linear):
         sig = _param_sig(self)
         if self._pk is None or self._pk[0] != sig:
             w = self.weight.detach()
-            k = w.shape[1]
-            if k % 64:                                        # the GEMM wants K in 64-element blocks: zero-pad once
-                wp = torch.zeros(w.shape[0], (k + 63) // 64 * 64, device=dev, dtype=BF16)
-                wp[:, :k] = w.to(BF16)
-            else:
-                wp = _wmat(w, dev)
+            wp = pad_k(w, dev) if w.shape[1] % 64 else _wmat(w, dev)       # the GEMM wants K in 64-element blocks: zero-pad once
             self._pk = (sig, wp, _on(self.bias, dev, F32) if self.bias is not None else None)
         return self._pk[1], self._pk[2]
 

@@ -28,9 +28,10 @@ import torch
 import torch.nn as nn
 
 from . import hip
+from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .wan_transformer3d_FlexAM import ModelConfig
 
-BF16, F32, I64 = torch.bfloat16, torch.float32, torch.int64
+BF16, F32 = torch.bfloat16, torch.float32
 
 # latent normalisation statistics of the Wan2.2 VAE (published constants; VAE.py:906-1010)
 LATENT_MEAN = [-0.2289, -0.0052, -0.1323, -0.2339, -0.2799, 0.0174, 0.1838, 0.1557, -0.1382, 0.0542, 0.2813, 0.0891,
@@ -76,10 +77,6 @@ class AutoencoderKLOutput:
 
     def __getitem__(self, i):
         return (self.latent_dist,)[i]
-
-
-def _round_up(v, m):
-    return (v + m - 1) // m * m
 
 
 def decoder_param_shapes(z_dim=48, dec_dim=256, dim_mult=(1, 2, 4, 4), temporal_up=(True, True, False)) -> Dict[str, tuple]:
@@ -167,7 +164,7 @@ class _ParamTree(nn.Module):
         self._modules[head].add(rest, shape)
 
 
-class _Conv:
+class _Conv(PackedConv):
     """One (causal) convolution as an implicit GEMM: packed bf16 weight [Cout, taps*Cp], fp32 bias,
     a padded channels-last input image with `hist` leading history frames, tap-offset tables."""
 
@@ -176,7 +173,9 @@ class _Conv:
         if w.dim() == 4:
             w = w.unsqueeze(2)
         co, ci, kt, kh, kw = w.shape
-        self.co, self.ci, self.kt, self.kh, self.kw = co, ci, kt, kh, kw
+        self.ci, self.kt, self.kh, self.kw = ci, kt, kh, kw
+        pix = w.permute(0, 2, 3, 4, 1)                                           # [co, kt, kh, kw, ci]
+        rows = [(dt, dh - kh // 2) for dt in range(kt) for dh in range(kh)]      # the image rows under the window
         # Run packing (channel counts that are not multiples of 64: the encoder's 160-channel stage and its 12-channel input): the
         # image keeps `ci` channels per pixel (rounded to 8: 16-byte pixels) instead of padding each pixel to 64, and the kw taps of one
         # image row -- kw * cp CONTIGUOUS elements starting at pixel w - 1 -- are one K run, padded to 64 as a whole (3 * 160 = 480 ->
@@ -184,30 +183,20 @@ class _Conv:
         # finite activations against zero weights.
         self.run_pack = kw == 3 and ci % 64 != 0
         if self.run_pack:
-            self.cp = _round_up(ci, 8)
-            self.krun = _round_up(kw * self.cp, 64)
-            taps = torch.zeros(co, kt, kh, kw, self.cp, device=device, dtype=F32)
-            taps[..., :ci] = w.permute(0, 2, 3, 4, 1)
-            wp = torch.zeros(co, kt, kh, self.krun, device=device, dtype=F32)
-            wp[..., :kw * self.cp] = taps.reshape(co, kt, kh, kw * self.cp)
-            self.weight = wp.reshape(co, kt * kh * self.krun).to(BF16).contiguous()
+            self.cp = round_up(ci, 8)
+            runs = torch.zeros(co, kt * kh, kw, self.cp, device=device, dtype=F32)
+            runs[..., :ci] = pix.reshape(co, kt * kh, kw, ci)
+            tap_w, groups = runs.view(co, kt * kh, kw * self.cp), [[Tap(dt, dh, -(kw // 2))] for dt, dh in rows]
         else:
-            self.cp = _round_up(ci, 64)
-            wp = torch.zeros(co, kt, kh, kw, self.cp, device=device, dtype=F32)
-            wp[..., :ci] = w.permute(0, 2, 3, 4, 1)
             # K order (dt, dh, channel block, dw, 64 channels): the kw taps of one image row are consecutive K blocks, and they read
             # the same 64-channel slice of rows shifted by ONE position -- the second and third hit the L2 lines the first just
             # brought in.  (With the tap-major order (dt, dh, dw, channel block) a shifted re-read comes cp/64 K blocks later, after
             # the XCD's 32 workgroups have pulled 32 x cp/64 x 32 KiB through its 4 MiB L2: the 3x3x3 convs at 256 x 448 then fetch
             # every activation ~9 times over the fabric.)
-            wp = wp.view(co, kt, kh, kw, self.cp // 64, 64).permute(0, 1, 2, 4, 3, 5)
-            self.weight = wp.reshape(co, kt * kh * kw * self.cp).to(BF16).contiguous()
-        self.bias = bias.detach().to(device, F32).contiguous()
-        self.hist = kt - 1
-        self.t_cap = t_cap
-        self.device = device
-        self.shape = None
-        self._koff = None
+            self.cp = round_up(ci, 64)
+            tap_w, groups = pix.reshape(co, kt * kh * kw, ci), [[Tap(dt, dh, dw - kw // 2) for dw in range(kw)] for dt, dh in rows]
+        super().__init__(tap_w, groups, bias, device)
+        self.hist, self.t_cap, self.shape = kt - 1, t_cap, None
 
     # Causal convs keep their input frames in a ring of RING chunks: the window [history | current chunk] slides forward by the chunk
     # length after every run, so the last `hist` frames of a chunk ARE the history of the next one where they lie; only when the
@@ -217,22 +206,11 @@ class _Conv:
 
     def image(self, h, w):
         if self.shape != (h, w):
-            hp, wp = h + 2, w + 2
             ring = max(1, min(self.RING, 16 // max(self.t_cap, 1))) if self.hist else 1      # long chunks: fewer of them, and a short ring (memory)
-            frames = self.hist + self.t_cap * ring
-            guard = _round_up((wp + 1) * self.cp + 64, 8)       # + the overrun of a packed run's last K block
-            self.buf = torch.zeros(guard * 2 + frames * hp * wp * self.cp, device=self.device, dtype=BF16)
-            self.all = self.buf[guard:guard + frames * hp * wp * self.cp].view(frames, hp, wp, self.cp)
+            guard = reach(w, self.cp, 64)                        # + the overrun of a packed run's last K block
+            self.all = GuardedImage(self.hist + self.t_cap * ring, h, w, self.cp, self.device, guard, guard).img
             self.cur = 0                                         # first frame of the window
-            offs = []
-            tap = lambda dt, dh, dw: (dt * hp * wp + (dh - self.kh // 2) * wp + (dw - self.kw // 2)) * self.cp
-            for dt in range(self.kt):
-                for dh in range(self.kh):
-                    if self.run_pack:
-                        offs += [tap(dt, dh, 0) + 64 * blk for blk in range(self.krun // 64)]
-                    else:
-                        offs += [tap(dt, dh, dw) + cb * 64 for cb in range(self.cp // 64) for dw in range(self.kw)]
-            self._koff = torch.tensor(offs, dtype=I64, device=self.device)
+            self.at(h + 2, w + 2, self.cp)
             self.shape = (h, w)
             self.img = self.all[:self.hist + self.t_cap]
         return self.img
@@ -245,12 +223,7 @@ class _Conv:
 
     def run(self, t, h, w, out_dtype=F32, residual_into=None):
         """Convolve the `t` current frames (window frames hist..hist+t); then slide the window."""
-        rows = t * (h + 2) * (w + 2)
-        a = self.img.view(-1, self.cp)
-        if residual_into is not None:
-            out = hip.gemm_gate_residual(a, self.weight, self.bias, residual_into, a_koff=self._koff)
-        else:
-            out = hip.gemm(a, self.weight, self.bias, a_koff=self._koff, m=rows, k=self.weight.shape[1], out_dtype=out_dtype)
+        out = self.launch(self.img.view(-1, self.cp), t * (h + 2) * (w + 2), out_dtype, residual_into)
         self.roll(t)
         return out
 
@@ -273,8 +246,7 @@ class _Conv:
         rows = (h + 2) * (w + 2)
         out = torch.empty(t // 2 * rows, self.co, device=self.device, dtype=out_dtype)
         for j in range(t // 2):
-            hip.gemm(self.img[1 + 2 * j:].reshape(-1, self.cp), self.weight, self.bias, a_koff=self._koff, m=rows, k=self.weight.shape[1],
-                     out=out[j * rows:(j + 1) * rows])
+            self.launch(self.img[1 + 2 * j:].reshape(-1, self.cp), rows, out=out[j * rows:(j + 1) * rows])
         self.roll(t)
         return out
 
@@ -291,13 +263,13 @@ class _ConvFold(_Conv):
         co, ci, kt, kh, kw = w.shape
         assert (kh, kw) == (3, 3)
         self.co, self.ci, self.kt, self.kh, self.kw = co, ci, kt, kh, kw
-        self.run_pack = False
-        self.cp = _round_up(ci, 64)
-        wf = torch.zeros(kt * 9 * co, self.cp, device=device, dtype=F32)
-        wf[:, :ci] = w.permute(2, 3, 4, 0, 1).reshape(kt * 9 * co, ci)              # row (dt*9 + dh*3 + dw) * co + o
-        self.weight = wf.to(BF16).contiguous()
+        self.run_pack, self.cp = False, round_up(ci, 64)
+        # the taps lie along N, not K -- row (dt*9 + dh*3 + dw) * co + o, the order flexam_tapsum_cl gathers in -- and K is the channels
+        # of one pixel: a plain GEMM with no offset table, so there is no K order to state
+        self.weight = pad_k(w.permute(2, 3, 4, 0, 1).reshape(kt * 9 * co, ci), device)
         self.bias = bias.detach().to(device, F32).contiguous()
-        self.hist, self.t_cap, self.device, self.shape, self._koff, self._y = kt - 1, t_cap, device, None, None, None
+        self.blocks, self._tables = [], {}
+        self.hist, self.t_cap, self.device, self.shape, self._y = kt - 1, t_cap, device, None, None
 
     def run(self, t, h, w, out_dtype=F32, residual_into=None):
         assert out_dtype == F32 and residual_into is None
@@ -312,7 +284,7 @@ class _ConvFold(_Conv):
         return out
 
 
-class _ConvS2D:
+class _ConvS2D(PackedConv):
     """ZeroPad2d((0,1,0,1)) + Conv2d(3x3, stride 2) (Resample downsample2d/3d, VAE.py:104-113) as a unit-stride
     implicit GEMM over a space-to-depth image [t, H/2+2, W/2+2, 4*Cs]: tap (dh, dw) of the strided conv is
     (row dh>>1, col dw>>1, channel group (dh&1)*2 + (dw&1)) of that image."""
@@ -321,34 +293,24 @@ class _ConvS2D:
         w = weight.detach().to(device, F32)
         co, ci, kh, kw = w.shape
         assert (kh, kw) == (3, 3)
-        self.co, self.ci, self.cs = co, ci, _round_up(ci, 64)
-        wp = torch.zeros(co, 3, 3, self.cs, device=device, dtype=F32)
-        wp[..., :ci] = w.permute(0, 2, 3, 1)
-        wp = wp.view(co, 3, 3, self.cs // 64, 64).permute(0, 1, 3, 2, 4)      # K order as in _Conv: (dh, channel block, dw, 64)
-        self.weight = wp.reshape(co, 9 * self.cs).to(BF16).contiguous()
-        self.bias = bias.detach().to(device, F32).contiguous()
-        self.t_cap, self.device, self.shape = t_cap, device, None
+        self.ci, self.cs = ci, round_up(ci, 64)
+        # K order as in _Conv: (dh, channel block, dw, 64)
+        groups = [[Tap(0, dh >> 1, dw >> 1, ((dh & 1) * 2 + (dw & 1)) * self.cs) for dw in range(3)] for dh in range(3)]
+        super().__init__(w.permute(0, 2, 3, 1).reshape(co, 9, ci), groups, bias, device)
+        self.t_cap, self.shape = t_cap, None
 
     def image(self, h2, w2):
         """h2, w2: OUTPUT resolution."""
         if self.shape != (h2, w2):
-            hp, wp, c4 = h2 + 2, w2 + 2, 4 * self.cs
-            guard = (wp + 2) * c4
-            self.buf = torch.zeros(self.t_cap * hp * wp * c4 + guard, device=self.device, dtype=BF16)
-            self.img = self.buf[:self.t_cap * hp * wp * c4].view(self.t_cap, hp, wp, c4)
-            offs = []
-            tap = lambda dh, dw: (((dh >> 1) * wp + (dw >> 1)) * 4 + (dh & 1) * 2 + (dw & 1)) * self.cs
-            for dh in range(3):
-                offs += [tap(dh, dw) + cb * 64 for cb in range(self.cs // 64) for dw in range(3)]
-            self._koff = torch.tensor(offs, dtype=I64, device=self.device)
+            c4 = 4 * self.cs
+            self.img = GuardedImage(self.t_cap, h2, w2, c4, self.device, 0, (w2 + 4) * c4).img
+            self.at(h2 + 2, w2 + 2, c4)
             self.shape = (h2, w2)
         return self.img
 
     def run(self, t, h2, w2, out_dtype=F32, residual_into=None):
         rows = t * (h2 + 2) * (w2 + 2)
-        if residual_into is not None:                  # residual_into[rows, Cout] += conv (fp32, in the GEMM epilogue)
-            return hip.gemm_gate_residual(self.img.view(-1, 4 * self.cs), self.weight, self.bias, residual_into[:rows], a_koff=self._koff)
-        return hip.gemm(self.img.view(-1, 4 * self.cs), self.weight, self.bias, a_koff=self._koff, m=rows, k=self.weight.shape[1], out_dtype=out_dtype)
+        return self.launch(self.img.view(-1, 4 * self.cs), rows, out_dtype, None if residual_into is None else residual_into[:rows])
 
 
 class _ConvUp2x:
@@ -369,18 +331,16 @@ class _ConvUp2x:
         w = weight.detach().to(device, F32)
         co, ci, kh, kw = w.shape
         assert (kh, kw) == (3, 3)
-        self.co, self.ci, self.cp = co, ci, _round_up(ci, 64)
-        self.weights = []
+        self.co, self.ci, self.cp = co, ci, round_up(ci, 64)
+        self.bias = bias.detach().to(device, F32).contiguous()
+        self.phases = []
         for a in (0, 1):
             for b in (0, 1):
-                wp = torch.zeros(co, 2, 2, self.cp, device=device, dtype=F32)
-                for r in (0, 1):
-                    for c in (0, 1):
-                        wp[:, r, c, :ci] = sum(w[:, :, i, j] for i in self.SETS[(a, r)] for j in self.SETS[(b, c)])
+                sums = [sum(w[:, :, i, j] for i in self.SETS[(a, r)] for j in self.SETS[(b, c)]) for r in (0, 1) for c in (0, 1)]
                 # K order (r, channel block, c, 64): the two column taps of a row are consecutive K blocks on the same 64 channels (see _Conv)
-                wp = wp.view(co, 2, 2, self.cp // 64, 64).permute(0, 1, 3, 2, 4)
-                self.weights.append(wp.reshape(co, 4 * self.cp).to(BF16).contiguous())
-        self.bias = bias.detach().to(device, F32).contiguous()
+                groups = [[Tap(0, a + r - 1, b + c - 1) for c in (0, 1)] for r in (0, 1)]
+                self.phases.append(PackedConv(torch.stack(sums, 1), groups, self.bias, device))
+        self.weights = [p.weight for p in self.phases]
         self.t_cap, self.device, self.shape = t_cap, device, None
         self.hist = 0
 
@@ -388,15 +348,10 @@ class _ConvUp2x:
         """h, w: INPUT (low) resolution.  Zero-bordered [t_cap, h + 2, w + 2, cp] with guard rows on both sides (the taps of the first
         and last padded rows reach one row past the image)."""
         if self.shape != (h, w):
-            hp, wp, cp = h + 2, w + 2, self.cp
-            guard = _round_up((wp + 1) * cp + 64, 8)
-            self.buf = torch.zeros(2 * guard + self.t_cap * hp * wp * cp, device=self.device, dtype=BF16)
-            self.img = self.buf[guard:guard + self.t_cap * hp * wp * cp].view(self.t_cap, hp, wp, cp)
-            self._koff = []
-            for a in (0, 1):
-                for b in (0, 1):
-                    offs = [((a + r - 1) * wp + (b + c - 1)) * cp + cb * 64 for r in (0, 1) for cb in range(cp // 64) for c in (0, 1)]
-                    self._koff.append(torch.tensor(offs, dtype=I64, device=self.device))
+            guard = reach(w, self.cp, 64)
+            self.img = GuardedImage(self.t_cap, h, w, self.cp, self.device, guard, guard).img
+            for p in self.phases:
+                p.at(h + 2, w + 2, self.cp)
             self.shape = (h, w)
             self._ph = None
         return self.img
@@ -407,8 +362,8 @@ class _ConvUp2x:
         if self._ph is None or self._ph.shape[1] < rows:
             self._ph = torch.empty(4, self.t_cap * (h + 2) * (w + 2), self.co, device=self.device, dtype=F32)
         a = self.img.view(-1, self.cp)
-        for p in range(4):
-            hip.gemm(a, self.weights[p], self.bias, a_koff=self._koff[p], m=rows, k=4 * self.cp, out=self._ph[p, :rows])
+        for i, p in enumerate(self.phases):
+            p.launch(a, rows, out=self._ph[i, :rows])
         return self._ph[:, :rows]
 
     def reset(self):
@@ -453,7 +408,7 @@ class _EngineBase:
     def _plain_image(self, key, frames, h, w, cp):
         k = (key, frames, h, w, cp)
         if k not in self._scratch:
-            self._scratch[k] = torch.zeros(frames, h + 2, w + 2, cp, device=self.device, dtype=BF16)
+            self._scratch[k] = GuardedImage(frames, h, w, cp, self.device, 0, 0).img
         return self._scratch[k]
 
     def _res(self, r, x, t, h, w):
@@ -475,7 +430,7 @@ class _EngineBase:
         """AttentionBlock (VAE.py:243-282): per frame, one head with head_dim = C."""
         c, dev = a["c"], self.device
         n = h * w
-        n4, kp = _round_up(n, 4), _round_up(n, 64)                                         # GEMM N granularity / K granularity
+        n4, kp = round_up(n, 4), round_up(n, 64)                                         # GEMM N granularity / K granularity
         rows = (h + 2) * (w + 2)
         for f in range(t):
             xf = x[f * rows:(f + 1) * rows]
