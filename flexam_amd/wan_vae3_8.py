@@ -27,7 +27,7 @@ from typing import Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import hip
+from . import hip, vae_tiles
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .wan_transformer3d_FlexAM import ModelConfig
 
@@ -79,9 +79,8 @@ class AutoencoderKLOutput:
         return (self.latent_dist,)[i]
 
 
-def decoder_param_shapes(z_dim=48, dec_dim=256, dim_mult=(1, 2, 4, 4), temporal_up=(True, True, False)) -> Dict[str, tuple]:
-    """Parameter inventory of conv2 + Decoder3d under the reference's names (VAE.py:621-675)."""
-    dims = [dec_dim * m for m in [dim_mult[-1]] + list(dim_mult[::-1])]
+def _shape_inventory():
+    """-> (shapes, conv, res): an empty name -> shape dict and the two functions that enter a convolution / a ResidualBlock into it."""
     s: Dict[str, tuple] = {}
 
     def conv(name, co, ci, k):
@@ -94,6 +93,13 @@ def decoder_param_shapes(z_dim=48, dec_dim=256, dim_mult=(1, 2, 4, 4), temporal_
         conv(name + ".residual.6", co, co, (3, 3, 3))
         if ci != co:
             conv(name + ".shortcut", co, ci, (1, 1, 1))
+    return s, conv, res
+
+
+def decoder_param_shapes(z_dim=48, dec_dim=256, dim_mult=(1, 2, 4, 4), temporal_up=(True, True, False)) -> Dict[str, tuple]:
+    """Parameter inventory of conv2 + Decoder3d under the reference's names (VAE.py:621-675)."""
+    dims = [dec_dim * m for m in [dim_mult[-1]] + list(dim_mult[::-1])]
+    s, conv, res = _shape_inventory()
     conv("conv2", z_dim, z_dim, (1, 1, 1))
     conv("decoder.conv1", dims[0], z_dim, (3, 3, 3))
     res("decoder.middle.0", dims[0], dims[0])
@@ -118,18 +124,7 @@ def decoder_param_shapes(z_dim=48, dec_dim=256, dim_mult=(1, 2, 4, 4), temporal_
 def encoder_param_shapes(z_dim=48, dim=160, dim_mult=(1, 2, 4, 4), temporal_down=(False, True, True)) -> Dict[str, tuple]:
     """Parameter inventory of conv1 + Encoder3d under the reference's names (VAE.py:505-562, :757-758)."""
     dims = [dim * m for m in [1] + list(dim_mult)]
-    s: Dict[str, tuple] = {}
-
-    def conv(name, co, ci, k):
-        s[name + ".weight"], s[name + ".bias"] = (co, ci, *k), (co,)
-
-    def res(name, ci, co):
-        s[name + ".residual.0.gamma"] = (ci, 1, 1, 1)
-        conv(name + ".residual.2", co, ci, (3, 3, 3))
-        s[name + ".residual.3.gamma"] = (co, 1, 1, 1)
-        conv(name + ".residual.6", co, co, (3, 3, 3))
-        if ci != co:
-            conv(name + ".shortcut", co, ci, (1, 1, 1))
+    s, conv, res = _shape_inventory()
     conv("conv1", z_dim * 2, z_dim * 2, (1, 1, 1))
     conv("encoder.conv1", dims[0], 12, (3, 3, 3))
     n_stage = len(dims) - 1
@@ -164,9 +159,57 @@ class _ParamTree(nn.Module):
         self._modules[head].add(rest, shape)
 
 
-class _Conv(PackedConv):
-    """One (causal) convolution as an implicit GEMM: packed bf16 weight [Cout, taps*Cp], fp32 bias,
-    a padded channels-last input image with `hist` leading history frames, tap-offset tables."""
+def padded_rows(t, h, w):
+    """GEMM rows of t frames of an h x w image with its zero border."""
+    return t * (h + 2) * (w + 2)
+
+
+class _CausalImage:
+    """The input frames of a causal convolution: a zero-bordered channels-last bf16 image [hist + t_cap, h + 2, w + 2, cp] -- `hist`
+    frames of history in front of the current chunk -- as a window into a ring of RING chunks.  The window [history | current chunk]
+    slides forward by the chunk length after every run, so the last `hist` frames of a chunk ARE the history of the next one where they
+    lie; only when the window reaches the end of the buffer are those frames copied to its start (every RING-th chunk instead of after
+    every chunk: the copies were 3 % of a decode and 5 % of an encode).  Border positions are zero everywhere and never written."""
+    RING = max(1, int(os.environ.get("FLEXAM_VAE_RING", "4")))
+
+    def __init__(self, hist: int, t_cap: int, cp: int, device):
+        self.hist, self.t_cap, self.cp, self.device, self.shape = hist, t_cap, cp, device, None
+
+    def image(self, h, w):
+        if self.shape != (h, w):
+            ring = max(1, min(self.RING, 16 // max(self.t_cap, 1))) if self.hist else 1      # long chunks: fewer of them, and a short ring (memory)
+            guard = reach(w, self.cp, 64)                        # + the overrun of a packed run's last K block
+            self.all = GuardedImage(self.hist + self.t_cap * ring, h, w, self.cp, self.device, guard, guard).img
+            self.cur = 0                                         # first frame of the window
+            self.placed(h, w)
+            self.shape = (h, w)
+            self.img = self.all[:self.hist + self.t_cap]
+        return self.img
+
+    def placed(self, h, w):
+        """The image has a new geometry: what depends on it follows here."""
+
+    def reset(self):
+        if self.shape is not None and self.hist:
+            self.cur = 0
+            self.img = self.all[:self.hist + self.t_cap]
+            self.img[:self.hist].zero_()
+
+    def roll(self, t):
+        """The last `hist` frames of the chunk become the history of the next one: the window moves on by t frames."""
+        if self.hist:
+            win = self.hist + self.t_cap
+            self.cur += t
+            if self.cur + win > self.all.shape[0]:               # end of the ring: bring the history to the front
+                src = self.all[self.cur:self.cur + self.hist]
+                self.all[:self.hist].copy_(src.clone() if self.cur < self.hist else src)
+                self.cur = 0
+            self.img = self.all[self.cur:self.cur + win]
+
+
+class _Conv(PackedConv, _CausalImage):
+    """One (causal) convolution as an implicit GEMM: packed bf16 weight [Cout, taps*Cp], fp32 bias, tap-offset tables, over a
+    _CausalImage with kt - 1 history frames."""
 
     def __init__(self, weight, bias, device, t_cap: int):
         w = weight.detach().to(device, F32)
@@ -183,67 +226,40 @@ class _Conv(PackedConv):
         # finite activations against zero weights.
         self.run_pack = kw == 3 and ci % 64 != 0
         if self.run_pack:
-            self.cp = round_up(ci, 8)
-            runs = torch.zeros(co, kt * kh, kw, self.cp, device=device, dtype=F32)
+            cp = round_up(ci, 8)
+            runs = torch.zeros(co, kt * kh, kw, cp, device=device, dtype=F32)
             runs[..., :ci] = pix.reshape(co, kt * kh, kw, ci)
-            tap_w, groups = runs.view(co, kt * kh, kw * self.cp), [[Tap(dt, dh, -(kw // 2))] for dt, dh in rows]
+            tap_w, groups = runs.view(co, kt * kh, kw * cp), [[Tap(dt, dh, -(kw // 2))] for dt, dh in rows]
         else:
             # K order (dt, dh, channel block, dw, 64 channels): the kw taps of one image row are consecutive K blocks, and they read
             # the same 64-channel slice of rows shifted by ONE position -- the second and third hit the L2 lines the first just
             # brought in.  (With the tap-major order (dt, dh, dw, channel block) a shifted re-read comes cp/64 K blocks later, after
             # the XCD's 32 workgroups have pulled 32 x cp/64 x 32 KiB through its 4 MiB L2: the 3x3x3 convs at 256 x 448 then fetch
             # every activation ~9 times over the fabric.)
-            self.cp = round_up(ci, 64)
+            cp = round_up(ci, 64)
             tap_w, groups = pix.reshape(co, kt * kh * kw, ci), [[Tap(dt, dh, dw - kw // 2) for dw in range(kw)] for dt, dh in rows]
-        super().__init__(tap_w, groups, bias, device)
-        self.hist, self.t_cap, self.shape = kt - 1, t_cap, None
+        PackedConv.__init__(self, tap_w, groups, bias, device)
+        _CausalImage.__init__(self, kt - 1, t_cap, cp, device)
 
-    # Causal convs keep their input frames in a ring of RING chunks: the window [history | current chunk] slides forward by the chunk
-    # length after every run, so the last `hist` frames of a chunk ARE the history of the next one where they lie; only when the
-    # window reaches the end of the buffer are those frames copied to its start (every RING-th chunk instead of after every chunk:
-    # the copies were 3 % of a decode and 5 % of an encode).  Border positions are zero everywhere and never written.
-    RING = max(1, int(os.environ.get("FLEXAM_VAE_RING", "4")))
+    def placed(self, h, w):
+        self.at(h + 2, w + 2, self.cp)
 
-    def image(self, h, w):
-        if self.shape != (h, w):
-            ring = max(1, min(self.RING, 16 // max(self.t_cap, 1))) if self.hist else 1      # long chunks: fewer of them, and a short ring (memory)
-            guard = reach(w, self.cp, 64)                        # + the overrun of a packed run's last K block
-            self.all = GuardedImage(self.hist + self.t_cap * ring, h, w, self.cp, self.device, guard, guard).img
-            self.cur = 0                                         # first frame of the window
-            self.at(h + 2, w + 2, self.cp)
-            self.shape = (h, w)
-            self.img = self.all[:self.hist + self.t_cap]
-        return self.img
-
-    def reset(self):
-        if self.shape is not None and self.hist:
-            self.cur = 0
-            self.img = self.all[:self.hist + self.t_cap]
-            self.img[:self.hist].zero_()
+    def weight_elems(self):
+        """Weight elements the convolution multiplies per output position (_stage_cost)."""
+        return self.weight.numel()
 
     def run(self, t, h, w, out_dtype=F32, residual_into=None):
         """Convolve the `t` current frames (window frames hist..hist+t); then slide the window."""
-        out = self.launch(self.img.view(-1, self.cp), t * (h + 2) * (w + 2), out_dtype, residual_into)
+        out = self.launch(self.img.view(-1, self.cp), padded_rows(t, h, w), out_dtype, residual_into)
         self.roll(t)
         return out
-
-    def roll(self, t):
-        """The last `hist` frames of the chunk become the history of the next one: the window moves on by t frames."""
-        if self.hist:
-            win = self.hist + self.t_cap
-            self.cur += t
-            if self.cur + win > self.all.shape[0]:               # end of the ring: bring the history to the front
-                src = self.all[self.cur:self.cur + self.hist]
-                self.all[:self.hist].copy_(src.clone() if self.cur < self.hist else src)
-                self.cur = 0
-            self.img = self.all[self.cur:self.cur + win]
 
     def run_time_stride2(self, t, h, w, out_dtype=F32):
         """(3,1,1) conv with temporal stride 2 and one cached frame (Resample downsample3d, VAE.py:162-174):
         output frame j reads [prev | x][2j .. 2j+2] = image frames 1+2j .. 3+2j; one GEMM per output frame."""
         if t % 2 or (self.kt, self.kh, self.kw) != (3, 1, 1):
             raise RuntimeError("run_time_stride2: needs an even frame count and a (3,1,1) kernel")
-        rows = (h + 2) * (w + 2)
+        rows = padded_rows(1, h, w)
         out = torch.empty(t // 2 * rows, self.co, device=self.device, dtype=out_dtype)
         for j in range(t // 2):
             self.launch(self.img[1 + 2 * j:].reshape(-1, self.cp), rows, out=out[j * rows:(j + 1) * rows])
@@ -251,7 +267,7 @@ class _Conv(PackedConv):
         return out
 
 
-class _ConvFold(_Conv):
+class _ConvFold(_CausalImage):
     """A causal convolution with few output channels (the decoder head, 256 -> 12) as a per-tap product + gather: ONE plain GEMM over
     the input pixels, Y[pixel, tap * Cout + o] = W[o, :, tap] . x[pixel, :] (K = Cin: every activation is read once; N = 27 * 12 = 324),
     then flexam_tapsum_cl adds, for every output pixel, the 27 products of its neighbours.  As an implicit GEMM the same convolution has
@@ -262,23 +278,21 @@ class _ConvFold(_Conv):
         w = weight.detach().to(device, F32)
         co, ci, kt, kh, kw = w.shape
         assert (kh, kw) == (3, 3)
-        self.co, self.ci, self.kt, self.kh, self.kw = co, ci, kt, kh, kw
-        self.run_pack, self.cp = False, round_up(ci, 64)
+        _CausalImage.__init__(self, kt - 1, t_cap, round_up(ci, 64), device)
+        self.co, self.ci, self.kt = co, ci, kt
         # the taps lie along N, not K -- row (dt*9 + dh*3 + dw) * co + o, the order flexam_tapsum_cl gathers in -- and K is the channels
         # of one pixel: a plain GEMM with no offset table, so there is no K order to state
         self.weight = pad_k(w.permute(2, 3, 4, 0, 1).reshape(kt * 9 * co, ci), device)
         self.bias = bias.detach().to(device, F32).contiguous()
-        self.blocks, self._tables = [], {}
-        self.hist, self.t_cap, self.device, self.shape, self._y = kt - 1, t_cap, device, None, None
+        self._y = None
 
     def run(self, t, h, w, out_dtype=F32, residual_into=None):
         assert out_dtype == F32 and residual_into is None
-        hp, wp = h + 2, w + 2
-        rows_all = (self.hist + t) * hp * wp
+        rows_all = padded_rows(self.hist + t, h, w)
         if self._y is None or self._y.shape[0] < rows_all:
-            self._y = torch.empty((self.hist + self.t_cap) * hp * wp, self.weight.shape[0], device=self.device, dtype=F32)
+            self._y = torch.empty(padded_rows(self.hist + self.t_cap, h, w), self.weight.shape[0], device=self.device, dtype=F32)
         y = hip.gemm(self.img.view(-1, self.cp)[:rows_all], self.weight, None, out=self._y[:rows_all])
-        out = torch.empty(t * hp * wp, self.co, device=self.device, dtype=F32)      # border rows: never read
+        out = torch.empty(padded_rows(t, h, w), self.co, device=self.device, dtype=F32)      # border rows: never read
         hip.tapsum_cl(y, t, h, w, self.kt, self.co, self.bias, out)
         self.roll(t)
         return out
@@ -309,7 +323,7 @@ class _ConvS2D(PackedConv):
         return self.img
 
     def run(self, t, h2, w2, out_dtype=F32, residual_into=None):
-        rows = t * (h2 + 2) * (w2 + 2)
+        rows = padded_rows(t, h2, w2)
         return self.launch(self.img.view(-1, 4 * self.cs), rows, out_dtype, None if residual_into is None else residual_into[:rows])
 
 
@@ -342,7 +356,10 @@ class _ConvUp2x:
                 self.phases.append(PackedConv(torch.stack(sums, 1), groups, self.bias, device))
         self.weights = [p.weight for p in self.phases]
         self.t_cap, self.device, self.shape = t_cap, device, None
-        self.hist = 0
+
+    def weight_elems(self):
+        """Weight elements the four phases multiply per LOW-resolution position (_stage_cost)."""
+        return sum(wt.numel() for wt in self.weights)
 
     def image(self, h, w):
         """h, w: INPUT (low) resolution.  Zero-bordered [t_cap, h + 2, w + 2, cp] with guard rows on both sides (the taps of the first
@@ -358,20 +375,103 @@ class _ConvUp2x:
 
     def run(self, t, h, w):
         """-> phases [4, t*(h+2)*(w+2), Cout] fp32 (rows of the padded LOW-resolution image; border rows hold garbage, never read)."""
-        rows = t * (h + 2) * (w + 2)
+        rows = padded_rows(t, h, w)
         if self._ph is None or self._ph.shape[1] < rows:
-            self._ph = torch.empty(4, self.t_cap * (h + 2) * (w + 2), self.co, device=self.device, dtype=F32)
+            self._ph = torch.empty(4, padded_rows(self.t_cap, h, w), self.co, device=self.device, dtype=F32)
         a = self.img.view(-1, self.cp)
         for i, p in enumerate(self.phases):
             p.launch(a, rows, out=self._ph[i, :rows])
         return self._ph[:, :rows]
 
-    def reset(self):
-        pass
+
+def _f32(t, dev):
+    return t.detach().to(dev, F32).reshape(-1).contiguous()
+
+
+class _ResBlock:
+    """ResidualBlock (VAE.py:198-240): RMS_norm + SiLU + conv, twice, added to the input or to its 1x1x1 shortcut conv."""
+
+    def __init__(self, g0, c1, g3, c2, short, plain_image):
+        self.g0, self.c1, self.g3, self.c2, self.short = g0, c1, g3, c2, short
+        self._plain_image = plain_image                    # the engine's: one shortcut image per (Cin, t, h, w, cp), not one per block
+
+    def causal_convs(self):
+        return [self.c1, self.c2]
+
+    def weight_elems(self):
+        return self.c1.weight_elems() + self.c2.weight_elems() + (self.short.weight_elems() if self.short is not None else 0)
+
+    def run(self, x, t, h, w):
+        """Rows x [t*(h+2)*(w+2), Cin] fp32 -> [.., Cout] fp32 (in place when there is no shortcut conv)."""
+        c1, c2 = self.c1, self.c2
+        hip.vae_prep_cl(x, c1.ci, t, h, w, c1.image(h, w), mode=2, gamma=self.g0, t0=c1.hist)
+        t1 = c1.run(t, h, w, out_dtype=BF16)
+        hip.vae_prep_cl(t1, c2.ci, t, h, w, c2.image(h, w), mode=2, gamma=self.g3, t0=c2.hist)
+        if self.short is not None:
+            sc = self.short
+            xb = self._plain_image(("short", sc.ci), t, h, w, sc.cp)
+            hip.vae_prep_cl(x, sc.ci, t, h, w, xb, mode=0)
+            x = hip.gemm(xb.view(-1, sc.cp), sc.weight, sc.bias, out_dtype=F32)
+        c2.run(t, h, w, residual_into=x)
+        return x
+
+
+class _AttnBlock:
+    """AttentionBlock (VAE.py:243-282): per frame, one head with head_dim = C."""
+
+    def __init__(self, sd, name, c, dev):
+        wqkv = sd[name + ".to_qkv.weight"].detach().to(dev, F32).reshape(3 * c, c)
+        self.bqkv = _f32(sd[name + ".to_qkv.bias"], dev)
+        self.c, self.gamma, self.wqkv = c, _f32(sd[name + ".norm.gamma"], dev), wqkv.to(BF16).contiguous()
+        self.wv, self.bv = wqkv[2 * c:].to(BF16).contiguous(), self.bqkv[2 * c:].contiguous()
+        self.wproj = sd[name + ".proj.weight"].detach().to(dev, BF16).reshape(c, c).contiguous()
+        self.bproj = _f32(sd[name + ".proj.bias"], dev)
+
+    def causal_convs(self):
+        return []
+
+    def run(self, x, t, h, w):
+        c, dev = self.c, self.gamma.device
+        n = h * w
+        n4, kp = round_up(n, 4), round_up(n, 64)                                         # GEMM N granularity / K granularity
+        rows = padded_rows(1, h, w)
+        for f in range(t):
+            xf = x[f * rows:(f + 1) * rows]
+            xn = torch.zeros(n4, c, device=dev, dtype=BF16)
+            hip.vae_prep_cl(xf, c, 1, h, w, xn, mode=1, gamma=self.gamma, compact=True)
+            qk = hip.gemm(xn, self.wqkv[:2 * c], self.bqkv[:2 * c])                       # [n4, 2c]
+            s = hip.gemm(qk[:n, :c], qk[:, c:], out_dtype=F32)                             # q k^T  [n, n4]; softmax over the first n
+            p = torch.empty(n, kp, device=dev, dtype=BF16)
+            hip.softmax_rows(s, c ** -0.5, p, n)
+            vt = torch.zeros(c, kp, device=dev, dtype=BF16)
+            hip.gemm(self.wv, xn, out=vt[:, :n4])                                          # V^T (bias folded below: rows of P sum to 1)
+            o = hip.gemm(p, vt, self.bv)                                                   # [n, c]
+            y = hip.gemm(o, self.wproj, self.bproj)
+            hip.scatter_add_cl(xf, y, c, 1, h, w)
+        return x
+
+
+class _Stage:
+    """The residual blocks of one resolution; all stages but the last end in a resample (2x in space; with `time_conv` also in time)."""
+
+    def __init__(self, res, cout, resample=None, time_conv=None):
+        self.res, self.cout, self.resample, self.time_conv = res, cout, resample, time_conv
+        self.temporal = time_conv is not None
+
+
+class _UpStage(_Stage):
+    up = property(lambda self: self.resample is not None)
+
+    def __getitem__(self, key):                            # benchlib/vae_clip.py reads stages[i]["up"]
+        return getattr(self, key)
+
+
+class _DownStage(_Stage):
+    down = property(lambda self: self.resample is not None)
 
 
 class _EngineBase:
-    """Blocks shared by the decoder and the encoder: ResidualBlock and the middle AttentionBlock."""
+    """What the decoder and the encoder share: conv1, the stages, the middle [ResidualBlock, AttentionBlock, ResidualBlock], the head."""
 
     def _setup(self, vae):
         self.sd = sd = {k: v for k, v in vae.model.state_dict().items()}
@@ -382,28 +482,18 @@ class _EngineBase:
         self._scratch = {}
         return sd, dev
 
-    @staticmethod
-    def _f32(t, dev):
-        return t.detach().to(dev, F32).reshape(-1).contiguous()
-
     def _mk_conv(self, name, t_cap=1):
         return _Conv(self.sd[name + ".weight"], self.sd[name + ".bias"], self.device, t_cap)
 
     def _mk_res(self, name, t_cap):
         sd, dev = self.sd, self.device
-        d = dict(g0=self._f32(sd[name + ".residual.0.gamma"], dev), c1=self._mk_conv(name + ".residual.2", t_cap),
-                 g3=self._f32(sd[name + ".residual.3.gamma"], dev), c2=self._mk_conv(name + ".residual.6", t_cap))
-        d["short"] = self._mk_conv(name + ".shortcut", t_cap) if (name + ".shortcut.weight") in sd else None
-        return d
+        return _ResBlock(_f32(sd[name + ".residual.0.gamma"], dev), self._mk_conv(name + ".residual.2", t_cap),
+                         _f32(sd[name + ".residual.3.gamma"], dev), self._mk_conv(name + ".residual.6", t_cap),
+                         self._mk_conv(name + ".shortcut", t_cap) if (name + ".shortcut.weight") in sd else None, self._plain_image)
 
-    def _mk_attn(self, name, c):
-        sd, dev = self.sd, self.device
-        wqkv = sd[name + ".to_qkv.weight"].detach().to(dev, F32).reshape(3 * c, c)
-        bqkv = self._f32(sd[name + ".to_qkv.bias"], dev)
-        return dict(c=c, gamma=self._f32(sd[name + ".norm.gamma"], dev), wqkv=wqkv.to(BF16).contiguous(), bqkv=bqkv,
-                    wv=wqkv[2 * c:].to(BF16).contiguous(), bv=bqkv[2 * c:].contiguous(),
-                    wproj=sd[name + ".proj.weight"].detach().to(dev, BF16).reshape(c, c).contiguous(),
-                    bproj=self._f32(sd[name + ".proj.bias"], dev))
+    def _mk_mid(self, name, c, t_cap):
+        r0, r2 = self._mk_res(name + ".0", t_cap), self._mk_res(name + ".2", t_cap)
+        return [r0, _AttnBlock(self.sd, name + ".1", c, self.device), r2]
 
     def _plain_image(self, key, frames, h, w, cp):
         k = (key, frames, h, w, cp)
@@ -411,40 +501,15 @@ class _EngineBase:
             self._scratch[k] = GuardedImage(frames, h, w, cp, self.device, 0, 0).img
         return self._scratch[k]
 
-    def _res(self, r, x, t, h, w):
-        """ResidualBlock (VAE.py:198-240) on rows x [t*(h+2)*(w+2), Cin] fp32 -> [.., Cout] fp32
-        (in place when there is no shortcut conv)."""
-        c1, c2 = r["c1"], r["c2"]
-        hip.vae_prep_cl(x, c1.ci, t, h, w, c1.image(h, w), mode=2, gamma=r["g0"], t0=c1.hist)
-        t1 = c1.run(t, h, w, out_dtype=BF16)
-        hip.vae_prep_cl(t1, c2.ci, t, h, w, c2.image(h, w), mode=2, gamma=r["g3"], t0=c2.hist)
-        if r["short"] is not None:
-            sc = r["short"]
-            xb = self._plain_image(("short", sc.ci), t, h, w, sc.cp)
-            hip.vae_prep_cl(x, sc.ci, t, h, w, xb, mode=0)
-            x = hip.gemm(xb.view(-1, sc.cp), sc.weight, sc.bias, out_dtype=F32)
-        c2.run(t, h, w, residual_into=x)
-        return x
+    def _all_convs(self):
+        """Every convolution that carries frames from one chunk to the next."""
+        blocks = self.mid + [r for st in self.stages for r in st.res]
+        return ([self.conv1, self.head_conv] + [c for r in blocks for c in r.causal_convs()]
+                + [st.time_conv for st in self.stages if st.time_conv is not None])
 
-    def _attention(self, a, x, t, h, w):
-        """AttentionBlock (VAE.py:243-282): per frame, one head with head_dim = C."""
-        c, dev = a["c"], self.device
-        n = h * w
-        n4, kp = round_up(n, 4), round_up(n, 64)                                         # GEMM N granularity / K granularity
-        rows = (h + 2) * (w + 2)
-        for f in range(t):
-            xf = x[f * rows:(f + 1) * rows]
-            xn = torch.zeros(n4, c, device=dev, dtype=BF16)
-            hip.vae_prep_cl(xf, c, 1, h, w, xn, mode=1, gamma=a["gamma"], compact=True)
-            qk = hip.gemm(xn, a["wqkv"][:2 * c], a["bqkv"][:2 * c])                       # [n4, 2c]
-            s = hip.gemm(qk[:n, :c], qk[:, c:], out_dtype=F32)                             # q k^T  [n, n4]; softmax over the first n
-            p = torch.empty(n, kp, device=dev, dtype=BF16)
-            hip.softmax_rows(s, c ** -0.5, p, n)
-            vt = torch.zeros(c, kp, device=dev, dtype=BF16)
-            hip.gemm(a["wv"], xn, out=vt[:, :n4])                                          # V^T (bias folded below: rows of P sum to 1)
-            o = hip.gemm(p, vt, a["bv"])                                                   # [n, c]
-            y = hip.gemm(o, a["wproj"], a["bproj"])
-            hip.scatter_add_cl(xf, y, c, 1, h, w)
+    def _run_mid(self, x, t, h, w):
+        for blk in self.mid:
+            x = blk.run(x, t, h, w)
         return x
 
 
@@ -467,22 +532,20 @@ class _DecoderEngine(_EngineBase):
         self.phase_up = os.environ.get("FLEXAM_VAE_UPCONV", "phase") != "image"
         self.conv2 = conv("conv2")
         self.conv1 = conv("decoder.conv1", n)
-        self.mid = [res("decoder.middle.0", n), None, res("decoder.middle.2", n)]
-        self.attn = self._mk_attn("decoder.middle.1", dims[0])
+        self.mid = self._mk_mid("decoder.middle", dims[0], n)
         self.stages = []
         n_stage = len(dims) - 1
         for i in range(n_stage):
             p = f"decoder.upsamples.{i}.upsamples"
-            st = dict(res=[res(f"{p}.{j}", tmul[i]) for j in range(3)], up=i != n_stage - 1, cout=dims[i + 1])
-            if st["up"]:
-                st["temporal"] = bool(self.temporal_up[i])
-                t_rs = tmul[i] * (2 if st["temporal"] else 1)
+            blocks, resample, time_conv = [res(f"{p}.{j}", tmul[i]) for j in range(3)], None, None
+            if i != n_stage - 1:
+                t_rs = tmul[i] * (2 if self.temporal_up[i] else 1)
                 # FLEXAM_VAE_UPCONV=image: the earlier form (upsampled image + one 3x3 convolution over it), A/B and cross-check only
-                st["resample"] = (_ConvUp2x(sd[f"{p}.3.resample.1.weight"], sd[f"{p}.3.resample.1.bias"], dev, t_rs) if self.phase_up
-                                  else conv(f"{p}.3.resample.1", t_rs))
-                st["time_conv"] = conv(f"{p}.3.time_conv", tmul[i]) if st["temporal"] else None
-            self.stages.append(st)
-        self.head_gamma = self._f32(sd["decoder.head.0.gamma"], dev)
+                resample = (_ConvUp2x(sd[f"{p}.3.resample.1.weight"], sd[f"{p}.3.resample.1.bias"], dev, t_rs) if self.phase_up
+                            else conv(f"{p}.3.resample.1", t_rs))
+                time_conv = conv(f"{p}.3.time_conv", tmul[i]) if self.temporal_up[i] else None
+            self.stages.append(_UpStage(blocks, dims[i + 1], resample, time_conv))
+        self.head_gamma = _f32(sd["decoder.head.0.gamma"], dev)
         # FLEXAM_VAE_HEADCONV=implicit: the head as an implicit GEMM like every other convolution (A/B and cross-check)
         if os.environ.get("FLEXAM_VAE_HEADCONV", "fold") != "implicit" and sd["decoder.head.2.weight"].shape[0] % 4 == 0:
             self.head_conv = _ConvFold(sd["decoder.head.2.weight"], sd["decoder.head.2.bias"], dev, tmul[-1])
@@ -493,16 +556,6 @@ class _DecoderEngine(_EngineBase):
         self._grid_cache = {}
         del self.sd
 
-    def _all_convs(self):
-        out = [self.conv1, self.head_conv]
-        blocks = [self.mid[0], self.mid[2]] + [r for st in self.stages for r in st["res"]]
-        for r in blocks:
-            out += [r["c1"], r["c2"]]
-        for st in self.stages:
-            if st["up"] and st["time_conv"] is not None:
-                out.append(st["time_conv"])
-        return out
-
     def _chunk(self, src_rows, h, w, first, video, f0, stripe=None, t=1):
         """Decoder3d.forward on `t` latent frames (VAE.py:677-728; the first chunk is always the single first frame); writes 1 or 4 t
         frames into `video`.  stripe = {stage: (a, b, ca, cb)}: rows [a, b) x columns [ca, cb) (relative to what it holds at that point) of
@@ -511,9 +564,7 @@ class _DecoderEngine(_EngineBase):
         c1 = self.conv1
         hip.vae_prep_cl(src_rows, c1.ci, t, h, w, c1.image(h, w), mode=0, t0=c1.hist)
         x = c1.run(t, h, w, out_dtype=F32)
-        x = self._res(self.mid[0], x, t, h, w)
-        x = self._attention(self.attn, x, t, h, w)
-        x = self._res(self.mid[2], x, t, h, w)
+        x = self._run_mid(x, t, h, w)
         for si, st in enumerate(self.stages):
             if stripe is not None and si in stripe:
                 a, b, ca, cb = stripe[si]
@@ -523,18 +574,17 @@ class _DecoderEngine(_EngineBase):
             x_in, cin = x, x.shape[1]
             # the residual blocks update their input in place unless the first one has a shortcut convolution (a new tensor): only then
             # does x_in survive without a copy for the DupUp3D shortcut below
-            main = x.clone() if (st["up"] and st["res"][0]["short"] is None) else x
-            for r in st["res"]:
-                main = self._res(r, main, t, h, w)
-            if not st["up"]:
+            main = x.clone() if (st.up and st.res[0].short is None) else x
+            for r in st.res:
+                main = r.run(main, t, h, w)
+            if not st.up:
                 x = main
                 continue
-            co = st["cout"]
-            rs = st["resample"]
-            ft = 2 if st["temporal"] else 1
+            co, rs = st.cout, st.resample
+            ft = 2 if st.temporal else 1
             y = None
-            if st["temporal"] and not first:
-                tc = st["time_conv"]
+            if st.temporal and not first:
+                tc = st.time_conv
                 hip.vae_prep_cl(main, co, t, h, w, tc.image(h, w), mode=0, t0=tc.hist)
                 y = tc.run(t, h, w, out_dtype=BF16)                                        # [rows, 2*co]: frames 2i | 2i + 1 side by side
             t2 = 2 * t if y is not None else t
@@ -544,7 +594,7 @@ class _DecoderEngine(_EngineBase):
                 else:
                     hip.vae_prep_cl(main, co, t, h, w, rs.image(h, w), mode=0, t0=0)
                 ph = rs.run(t2, h, w)
-                out = torch.empty(t2 * (2 * h + 2) * (2 * w + 2), co, device=self.device, dtype=F32)      # border rows: never read
+                out = torch.empty(padded_rows(t2, 2 * h, 2 * w), co, device=self.device, dtype=F32)      # border rows: never read
                 hip.phase_dupup_cl(ph, out, co, t2, 2 * h, 2 * w, x_in, cin, ft, (ft - 1) if first else 0)
             else:
                 if y is not None:
@@ -560,106 +610,41 @@ class _DecoderEngine(_EngineBase):
         hip.vae_unpatchify_clamp(y, t, h, w, video, f0)
         return t
 
-    def _axis_need(self, n: int, part: int, parts: int):
-        """One axis of stripe_plan: [lo, hi) of the activation ENTERING each stage that part `part` of `parts` needs for its share of the
-        2 n 2^ups output rows (or columns) to come out exact, and that share [r0, r1) itself."""
-        n_st = len(self.stages)
-        N = [n]
-        for st in self.stages:
-            N.append(N[-1] * (2 if st["up"] else 1))
-        n_out = 2 * N[-1]                                      # unpatchify doubles once more
-        if n_out % parts:
-            raise ValueError(f"{n_out} output rows / columns do not divide over {parts} parts")
-        r0, r1 = part * n_out // parts, (part + 1) * n_out // parts
-        lo, hi = r0 // 2 - 1, -(-r1 // 2) + 1                  # what the head conv's 3x3 window touches
-        need = [None] * n_st
-        for si in range(n_st - 1, -1, -1):
-            st = self.stages[si]
-            lo, hi = max(0, lo), min(N[si + 1], hi)
-            if st["up"]:                                       # resample conv: 3x3 at the upsampled resolution = (y - 1) // 2 .. (y + 1) // 2 of the low one
-                lo, hi = (lo - 1) // 2, -(-(hi + 1) // 2)
-            lo, hi = lo - 2 * len(st["res"]), hi + 2 * len(st["res"])
-            need[si] = (max(0, lo), min(N[si], hi))
-        return need, N, r0, r1
-
     def _stage_cost(self):
         """Relative matrix work of a stage per pixel of ITS resolution and latent frame (weights of its convolutions x the frames the
         temporal upsamples before it have made): what band_grid weighs the stages with."""
         out, frames = [], 1
         for st in self.stages:
-            n = sum(r[c].weight.numel() for r in st["res"] for c in ("c1", "c2")) + sum(r["short"].weight.numel() for r in st["res"] if r["short"] is not None)
-            if st["up"]:
-                rs = st["resample"]
-                n += sum(wt.numel() for wt in rs.weights) if hasattr(rs, "weights") else 4 * rs.weight.numel()
-                if st.get("time_conv") is not None:
-                    n += st["time_conv"].weight.numel()
+            n = sum(r.weight_elems() for r in st.res)
+            if st.up:
+                n += st.resample.weight_elems() * (1 if self.phase_up else 4)        # the image form runs at the upsampled resolution
+                if st.temporal:
+                    n += st.time_conv.weight_elems()
             out.append(n * frames)
-            if st["up"] and st["temporal"]:
+            if st.temporal:
                 frames *= 2
         return out
 
+    # The tile plan of the parallel decode is vae_tiles': these hand it the stages' shape and work
+    def _tile_stages(self):
+        return [(st.up, len(st.res)) for st in self.stages]
+
     def band_grid(self, h: int, w: int, world: int):
-        """(rows, columns) of the tile grid the parallel decode cuts the output into: the factorisation of `world` whose SLOWEST tile does
-        the least matrix work (area of what it holds in every stage x that stage's work per pixel).  A 97 x 512 x 896 clip on 8 ranks:
-        2 x 4 (0.72 of the work of 8 row bands: a tile's halo is a fixed number of rows / columns, so squarer tiles carry less of it)."""
+        """(rows, columns) of the tile grid the parallel decode cuts the output into (vae_tiles.band_grid), cached per (h, w, world)."""
         key = (h, w, world)
-        if key in self._grid_cache:
-            return self._grid_cache[key]
-        cost = self._stage_cost()
-        best, best_c = None, None
-        for gr in range(world, 0, -1):                         # row bands first: another grid must beat them by 2 %
-            if world % gr:
-                continue
-            gc = world // gr
-            try:
-                worst = 0.0
-                for ri in range(gr):
-                    nr, _, _, _ = self._axis_need(h, ri, gr)
-                    for ci in range(gc):
-                        nc, _, _, _ = self._axis_need(w, ci, gc)
-                        c = 0.0
-                        for si, st in enumerate(self.stages):
-                            c += cost[si] * (nr[si][1] - nr[si][0]) * (nc[si][1] - nc[si][0])
-                        worst = max(worst, c)
-            except ValueError:
-                continue
-            if best is None or worst < best_c * 0.98:
-                best, best_c = (gr, gc), worst
-        if best is None:
-            raise ValueError(f"a [{16 * h}, {16 * w}] frame does not divide into {world} equal tiles")
-        self._grid_cache[key] = best
-        return best
+        if key not in self._grid_cache:
+            self._grid_cache[key] = vae_tiles.band_grid(self._tile_stages(), self._stage_cost(), h, w, world)
+        return self._grid_cache[key]
 
     def stripe_plan(self, h: int, w: int, rank: int, world: int):
         """Tiles of the parallel decode for `rank` of `world`: which rows x columns of the activation ENTERING each stage this
-        rank keeps so that its tile of the output comes out EXACT with no exchange.  Walking back from the output, what a stage must
-        deliver grows by the receptive field of what follows: 1 for the head conv, 1 (at the upsampled resolution) for a resample conv,
-        2 per residual block (two 3x3(x3) convs); a 2x upsample halves the range (_axis_need, the same walk for both axes).  conv1 and
-        the middle block (global attention) always run on full frames.  r6: the tile is re-cropped at EVERY stage where that removes
-        >= 1/8 of what is held (r1-r5 cropped once, entering stage 2, row bands only: 0.47 of a whole decode per rank at 8 ranks; per-stage
-        row bands 0.35; the 2 x 4 grid band_grid picks for the 512 x 896 clip ~0.26).
+        rank keeps so that its tile of the output comes out EXACT with no exchange (vae_tiles.stripe_plan on band_grid's grid).
         Returns (crops, (lo, hi, clo, chi), (gr, gc)): crops = {stage: (a, b, ca, cb)} relative to what is held when entering that stage;
         the tile's video has its own pixels at [lo, hi) x [clo, chi); rank = row * gc + column of the grid."""
-        gr, gc = self.band_grid(h, w, world)
-        ri, ci = divmod(rank, gc)
-        nr, _, r0, r1 = self._axis_need(h, ri, gr)
-        nc, _, c0, c1 = self._axis_need(w, ci, gc)
-        crops, cur, ccur = {}, (0, h), (0, w)
-        for si, st in enumerate(self.stages):
-            (a, b), (ca, cb) = nr[si], nc[si]
-            held, kept = (cur[1] - cur[0]) * (ccur[1] - ccur[0]), (b - a) * (cb - ca)
-            if held - kept >= max(1, held // 8):
-                crops[si] = (a - cur[0], b - cur[0], ca - ccur[0], cb - ccur[0])
-                cur, ccur = (a, b), (ca, cb)
-            if st["up"]:
-                cur, ccur = (2 * cur[0], 2 * cur[1]), (2 * ccur[0], 2 * ccur[1])
-        return crops, (r0 - 2 * cur[0], r1 - 2 * cur[0], c0 - 2 * ccur[0], c1 - 2 * ccur[0]), (gr, gc)
+        grid = self.band_grid(h, w, world)
+        return vae_tiles.stripe_plan(self._tile_stages(), grid, h, w, rank)[:2] + (grid,)
 
-    @staticmethod
-    def assemble_tiles(tiles, grid):
-        """Tiles [3, F, rows, cols] of all ranks (rank = row * gc + column) -> the frame."""
-        gr, gc = grid
-        return torch.cat([torch.cat(list(tiles[r * gc:(r + 1) * gc]), dim=3) for r in range(gr)], dim=2)
+    assemble_tiles = staticmethod(vae_tiles.assemble_tiles)
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, stripe=None) -> torch.Tensor:
@@ -671,7 +656,7 @@ class _DecoderEngine(_EngineBase):
         zi = self._plain_image("z", tz, h, w, self.conv2.cp)
         hip.pack_affine_cl(z.to(self.device, F32), self.std, self.mean, zi)                # z / (1/std) + mean
         x0 = hip.gemm(zi.view(-1, self.conv2.cp), self.conv2.weight, self.conv2.bias, out_dtype=F32)
-        rows = (h + 2) * (w + 2)
+        rows = padded_rows(1, h, w)
         scale = 2 ** (len(self.stages) - 1)
         tfac = 2 ** sum(self.temporal_up)
         frames = 1 + tfac * (tz - 1)
@@ -679,13 +664,9 @@ class _DecoderEngine(_EngineBase):
             video = torch.empty(3, frames, h * scale * 2, w * scale * 2, device=self.device, dtype=F32)
             self._walk(x0, rows, tz, h, w, video, None)
             return video
-        crops, (lo, hi, clo, chi), _ = self.stripe_plan(h, w, *stripe)
-        held, cheld = h, w                                     # rows / columns the tile holds at the output resolution
-        for si, st in enumerate(self.stages):
-            if si in crops:
-                held, cheld = crops[si][1] - crops[si][0], crops[si][3] - crops[si][2]
-            held, cheld = held * (2 if st["up"] else 1), cheld * (2 if st["up"] else 1)
-        band = torch.empty(3, frames, 2 * held, 2 * cheld, device=self.device, dtype=F32)
+        rank, world = stripe
+        crops, (lo, hi, clo, chi), held = vae_tiles.stripe_plan(self._tile_stages(), self.band_grid(h, w, world), h, w, rank)
+        band = torch.empty(3, frames, *held, device=self.device, dtype=F32)
         self._walk(x0, rows, tz, h, w, band, crops)
         return band[:, :, lo:hi, clo:chi].contiguous()
 
@@ -725,16 +706,14 @@ class _EncoderEngine(_EngineBase):
         n_stage = len(dims) - 1
         for i in range(n_stage):
             p = f"encoder.downsamples.{i}.downsamples"
-            st = dict(res=[res(f"{p}.{j}", tcap[i]) for j in range(2)], down=i != n_stage - 1, cout=dims[i + 1], temporal=False)
-            if st["down"]:
-                st["temporal"] = bool(self.temporal_down[i]) if i < len(self.temporal_down) else False
-                st["resample"] = _ConvS2D(sd[f"{p}.2.resample.1.weight"], sd[f"{p}.2.resample.1.bias"], dev, tcap[i])
-                st["time_conv"] = conv(f"{p}.2.time_conv", tcap[i]) if st["temporal"] else None
-            self.stages.append(st)
+            blocks, resample, time_conv = [res(f"{p}.{j}", tcap[i]) for j in range(2)], None, None
+            if i != n_stage - 1:
+                resample = _ConvS2D(sd[f"{p}.2.resample.1.weight"], sd[f"{p}.2.resample.1.bias"], dev, tcap[i])
+                time_conv = conv(f"{p}.2.time_conv", tcap[i]) if i < len(self.temporal_down) and self.temporal_down[i] else None
+            self.stages.append(_DownStage(blocks, dims[i + 1], resample, time_conv))
         t_last = tcap[n_stage - 1] if n_stage - 1 < len(tcap) else 1
-        self.mid = [res("encoder.middle.0", t_last), None, res("encoder.middle.2", t_last)]
-        self.attn = self._mk_attn("encoder.middle.1", dims[-1])
-        self.head_gamma = self._f32(sd["encoder.head.0.gamma"], dev)
+        self.mid = self._mk_mid("encoder.middle", dims[-1], t_last)
+        self.head_gamma = _f32(sd["encoder.head.0.gamma"], dev)
         # head conv (C -> 2z) followed by conv1 (1x1x1, 2z -> 2z) and (mu - mean) / std: one linear map, folded in fp32
         w1 = sd["conv1.weight"].detach().to(dev, F32).reshape(z2, z2)
         b1 = sd["conv1.bias"].detach().to(dev, F32)
@@ -749,14 +728,6 @@ class _EncoderEngine(_EngineBase):
         self.head_conv = _Conv(wf, bf, dev, t_last)
         del self.sd
 
-    def _all_convs(self):
-        out = [self.conv1, self.head_conv]
-        blocks = [self.mid[0], self.mid[2]] + [r for st in self.stages for r in st["res"]]
-        for r in blocks:
-            out += [r["c1"], r["c2"]]
-        out += [st["time_conv"] for st in self.stages if st.get("time_conv") is not None]
-        return out
-
     def _chunk(self, video, f0, t, h, w, first):
         """Encoder3d.forward (VAE.py:564-618) on frames f0..f0+t of `video`; returns rows [t'*(h'+2)*(w'+2), 2z] fp32."""
         c1 = self.conv1
@@ -764,40 +735,38 @@ class _EncoderEngine(_EngineBase):
         x = c1.run(t, h, w, out_dtype=F32)
         for st in self.stages:
             x_in, cin, t_in = x, x.shape[1], t
-            co = st["cout"]
+            co = st.cout
             # Stage 0 (same width in and out, spatial downsample only): the AvgDown3D shortcut is taken FIRST, into the buffer the
             # stride-2 convolution then adds its result to (fp32 residual epilogue) -- the residual blocks can overwrite x in place, and
             # neither a copy of x (0.3 GB per 4 frames at 256 x 448) nor a second pass over the downsampled rows is needed
-            fold = st["down"] and not st["temporal"] and st["res"][0]["short"] is None and cin == co
+            fold = st.down and not st.temporal and st.res[0].short is None and cin == co
             if fold:
-                short = torch.zeros(t * (h // 2 + 2) * (w // 2 + 2), co, device=self.device, dtype=F32)
+                short = torch.zeros(padded_rows(t, h // 2, w // 2), co, device=self.device, dtype=F32)
                 hip.avgdown_add_cl(short, co, t, h // 2, w // 2, x_in, cin, t_in, 1, 2)
                 main = x
             else:
-                main = x.clone() if st["res"][0]["short"] is None else x
-            for r in st["res"]:
-                main = self._res(r, main, t, h, w)
-            if st["down"]:
-                ds = st["resample"]
+                main = x.clone() if st.res[0].short is None else x
+            for r in st.res:
+                main = r.run(main, t, h, w)
+            if st.down:
+                ds = st.resample
                 h, w = h // 2, w // 2
                 hip.space_to_depth_cl(main, co, t, 2 * h, 2 * w, ds.image(h, w), ds.cs)
                 if fold:
                     x = ds.run(t, h, w, residual_into=short)
                     continue
                 main = ds.run(t, h, w, out_dtype=F32)
-                if st["temporal"]:
-                    tc = st["time_conv"]
+                if st.temporal:
+                    tc = st.time_conv
                     hip.vae_prep_cl(main, co, t, h, w, tc.image(h, w), mode=0, t0=tc.hist)
                     if first:
                         tc.roll(t)                                          # first chunk: the frame is only cached (VAE.py:165-166)
                     else:
                         main = tc.run_time_stride2(t, h, w, out_dtype=F32)
                         t //= 2
-            hip.avgdown_add_cl(main, co, t, h, w, x_in, cin, t_in, 2 if st["temporal"] else 1, 2 if st["down"] else 1)
+            hip.avgdown_add_cl(main, co, t, h, w, x_in, cin, t_in, 2 if st.temporal else 1, 2 if st.down else 1)
             x = main
-        x = self._res(self.mid[0], x, t, h, w)
-        x = self._attention(self.attn, x, t, h, w)
-        x = self._res(self.mid[2], x, t, h, w)
+        x = self._run_mid(x, t, h, w)
         hc = self.head_conv
         hip.vae_prep_cl(x, hc.ci, t, h, w, hc.image(h, w), mode=2, gamma=self.head_gamma, t0=hc.hist)
         return hc.run(t, h, w, out_dtype=F32), t, h, w
@@ -806,7 +775,7 @@ class _EncoderEngine(_EngineBase):
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         """x [3, 1 + 4k, H, W] in [-1, 1] -> [2z, 1 + k, H/16, W/16] fp32: normalised mu | log_var."""
         c, frames, hh, ww = x.shape
-        n_down = sum(1 for st in self.stages if st["down"])
+        n_down = sum(1 for st in self.stages if st.down)
         if c != 3 or hh % (2 << n_down) or ww % (2 << n_down):
             raise ValueError(f"encode: expected [3, F, H, W] with H, W multiples of {2 << n_down}, got {tuple(x.shape)}")
         for cv in self._all_convs():
@@ -874,7 +843,7 @@ class AutoencoderKLWan3_8(nn.Module):
     def enable_parallel_decode(self, group=None):
         """Tiled decode over the ranks of `group` (replaces the reference's missing `parallel_magvit_vae`,
         FlexAM/models/__init__.py:36-38): every rank decodes 1/N of the output pixels -- a tile of a rows x columns grid -- exactly
-        (see _DecoderEngine.stripe_plan) and one all-gather assembles the clip."""
+        (see vae_tiles) and one all-gather assembles the clip."""
         self._parallel_group, self._parallel = group, True
 
     def disable_parallel_decode(self):
@@ -888,8 +857,7 @@ class AutoencoderKLWan3_8(nn.Module):
         band = eng.decode(u, stripe=(dist.get_rank(self._parallel_group), world))
         bands = [torch.empty_like(band) for _ in range(world)]
         dist.all_gather(bands, band, group=self._parallel_group)
-        grid = eng.band_grid(u.shape[-2], u.shape[-1], world) if hasattr(eng, "band_grid") else (world, 1)
-        return _DecoderEngine.assemble_tiles(bands, grid)
+        return vae_tiles.assemble_tiles(bands, eng.band_grid(u.shape[-2], u.shape[-1], world))
 
     @torch.no_grad()
     def decode(self, z: torch.Tensor, return_dict: bool = True):

@@ -169,12 +169,14 @@ def _parallel_decode_gather(rank, world):
     full = torch.arange(3 * 5 * 8 * 6, dtype=torch.float32).view(3, 5, 8, 6)
 
     class FakeEngine:                                     # stands in for the HIP decoder: returns this rank's row band
+        def band_grid(self, h, w, n):
+            return (n, 1)
         def decode(self, u, stripe=None):
             r, n = stripe
             return full[:, :, r * 8 // n:(r + 1) * 8 // n].contiguous()
     vae = AutoencoderKLWan3_8(c_dim=16, dec_dim=16)
     vae.enable_parallel_decode()
-    out = vae._decode_one(FakeEngine(), None)
+    out = vae._decode_one(FakeEngine(), torch.zeros(1, 1, 4, 3))
     return bool(torch.equal(out, full))
 
 

@@ -52,7 +52,7 @@ def _tapsum(y, t, h, w, kt, co, bias, out):
 def restated(monkeypatch):
     monkeypatch.setattr(hip, "gemm", _gemm)
     monkeypatch.setattr(hip, "tapsum_cl", _tapsum)
-    monkeypatch.setattr(V._Conv, "RING", 1)
+    monkeypatch.setattr(V._CausalImage, "RING", 1)
 
 
 def _ints(g, *shape):

@@ -202,7 +202,7 @@ def test_vae_conv_layout_is_exact(layer, monkeypatch):
     """One layer of the engines at its true width; causal convs across three chunks with the history ring wrapping after every one
     (RING = 1), compared with one convolution over all frames joined."""
     from flexam_amd import wan_vae3_8 as V
-    monkeypatch.setattr(V._Conv, "RING", 1)
+    monkeypatch.setattr(V._CausalImage, "RING", 1)
     kind, ci, co, k = layer
     h, w = _size(ci, co)
     _run_layer(kind, ci, co, k, h, w, torch.Generator().manual_seed(ci * 7919 + co * 31 + len(k)))
@@ -217,5 +217,5 @@ def test_vae_conv_layout_wide_row_is_exact(kind, ci, co, k, h, w, monkeypatch):
     """One long-row case per class (112-position rows, as in the 64 x 112 stage of a 512 x 896 clip): thousands of GEMM rows, so the
     persistent grid runs many tiles and a tail, with the run-packed 160-channel taps reaching across tile edges."""
     from flexam_amd import wan_vae3_8 as V
-    monkeypatch.setattr(V._Conv, "RING", 1)
+    monkeypatch.setattr(V._CausalImage, "RING", 1)
     _run_layer(kind, ci, co, k, h, w, torch.Generator().manual_seed(ci + co + h * w), chunks=(1, 2))

@@ -129,6 +129,8 @@ def test_vae_tiled_decode_is_exact(world, h, w):
     z = C.vae_case(seed=56, frames=3, h=h, w=w)
     full = vae.decode(z.cuda()).sample[0]
     eng = vae.engine()
+    from test_vae_tiles_cpu import SMALL_COST
+    assert eng._stage_cost() == SMALL_COST                           # the CPU test of the plan uses these
     gr, gc = eng.band_grid(h, w, world)
     assert gr * gc == world
     tiles = [eng.decode(z[0].cuda(), stripe=(r, world)) for r in range(world)]
@@ -155,6 +157,8 @@ def test_vae_tile_grid_of_the_clip():
     with torch.device("cuda"):
         vae = AutoencoderKLWan3_8(spatial_compression_ratio=16).to(torch.bfloat16)
     eng = vae.engine()
+    from test_vae_tiles_cpu import REAL_COST
+    assert eng._stage_cost() == REAL_COST                            # the CPU test of the plan uses these
     assert eng.band_grid(32, 56, 8) == (2, 4) and eng.band_grid(32, 56, 4) == (2, 2) and eng.band_grid(32, 56, 2)[0] * eng.band_grid(32, 56, 2)[1] == 2
     crops, (lo, hi, clo, chi), grid = eng.stripe_plan(32, 56, 5, 8)            # second row of tiles, second column
     assert (hi - lo, chi - clo) == (256, 224) and max(crops) == 3
@@ -170,13 +174,13 @@ def test_vae_decode_ring_wraps_are_consumed(frames, monkeypatch):
     vae, sd = build(seed=83)
     z = C.vae_case(seed=84, frames=frames, h=2, w=4)
     want = OV.vae_decode(sd, z, C.VAE_SMALL["temporal_up"], OV.LATENT_MEAN, OV.LATENT_STD)
-    assert V._Conv.RING == 4
+    assert V._CausalImage.RING == 4
     out = vae.decode(z.cuda()).sample
     assert out.shape == (1, 3, 4 * (frames - 1) + 1, 32, 64)
     check(out, want, f"vae decode {frames} chunks (ring of 4)")
     again = vae.decode(z.cuda()).sample                       # second call starts from a reset ring
     torch.testing.assert_close(out, again, rtol=0, atol=0)
-    monkeypatch.setattr(V._Conv, "RING", 1)
+    monkeypatch.setattr(V._CausalImage, "RING", 1)
     vae1, _ = build(seed=83)
     out1 = vae1.decode(z.cuda()).sample
     torch.testing.assert_close(out, out1, rtol=0, atol=0)
