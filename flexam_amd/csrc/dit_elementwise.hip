@@ -4,6 +4,7 @@
 // Row kernels use one 128-thread workgroup (2 waves) per token row: a 3072-wide row is exactly
 // 3 x 128 vectors of 8 elements, kept in registers between the reduction and the write.
 #include "common.h"
+#include "dit_rows.h"
 #include "flexam_hip.h"
 
 namespace {
@@ -11,6 +12,15 @@ namespace {
 constexpr int RT = 128;   // threads per row
 
 __device__ __forceinline__ float row_sum(float v, float* red) { return block_sum<RT>(v, red); }
+
+// LayerNorm's apply step at columns c .. c + 3: normalise, then the optional affine (ln_w, ln_b) and the optional modulation row (sc, sh)
+__device__ __forceinline__ f32x4 ln_apply(f32x4 v, int c, float mean, float rstd, const float* __restrict__ ln_w,
+                                          const float* __restrict__ ln_b, const float* __restrict__ sc, const float* __restrict__ sh) {
+  f32x4 y = (v - mean) * rstd;
+  if (ln_w) y = y * *(const f32x4*)(ln_w + c) + *(const f32x4*)(ln_b + c);
+  if (sh) y = y * *(const f32x4*)(sc + c) + *(const f32x4*)(sh + c);
+  return y;
+}
 
 // ------------------------------------------------------------------------------------------
 // Same LayerNorm + modulation, ONE WAVE PER ROW (C = 512*NV8, NV8 <= 8): every lane keeps 8*NV8 values in registers, both
@@ -55,7 +65,7 @@ __global__ __launch_bounds__(64) void ln_modulate_wave_kernel(const float* __res
   const float* sh = nullptr;
   const float* sc = nullptr;
   if (shift) {
-    const int64_t r = row_index ? (int64_t)row_index[m] : m / rows_per_batch;
+    const int64_t r = mod_row(row_index, rows_per_batch, m);
     sh = shift + r * tab_ld;
     sc = scale + r * tab_ld;
   }
@@ -63,9 +73,7 @@ __global__ __launch_bounds__(64) void ln_modulate_wave_kernel(const float* __res
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c = (i * 64 + lane) * 4;
-    f32x4 y = (v[i] - mean) * rstd;
-    if (ln_w) y = y * *(const f32x4*)(ln_w + c) + *(const f32x4*)(ln_b + c);
-    if (sh) y = y * *(const f32x4*)(sc + c) + *(const f32x4*)(sh + c);
+    const f32x4 y = ln_apply(v[i], c, mean, rstd, ln_w, ln_b, sc, sh);
     if constexpr (FP8) {
       v[i] = y;
 #pragma unroll
@@ -81,11 +89,8 @@ __global__ __launch_bounds__(64) void ln_modulate_wave_kernel(const float* __res
     }
   }
   if constexpr (FP8) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const float qs = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
-    const float inv = 1.0f / qs;
-    if (lane == 0) row_scale[m] = qs;
+    const RowScale8 qs = e4m3_row_scale(wave_max(amax));
+    if (lane == 0) row_scale[m] = qs.scale;
     if (next_scale) {
       // A scale for the e4m3 OUTPUT of the GEMM this row feeds, known before that GEMM runs: |gelu(a . w_j + b_j)| <= |a|_2 |w_j|_2 + |b_j|
       // (Cauchy-Schwarz; |a|_2 of the quantised row <= 1.07 |y|_2: 2^-4 relative rounding + subnormal steps), so the consumer of
@@ -96,12 +101,7 @@ __global__ __launch_bounds__(64) void ln_modulate_wave_kernel(const float* __res
     }
     uint8_t* qrow = (uint8_t*)out + m * ldo;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      int w = 0;
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][0] * inv, v[i][1] * inv, w, false);
-      w = __builtin_amdgcn_cvt_pk_fp8_f32(v[i][2] * inv, v[i][3] * inv, w, true);
-      *(unsigned*)(qrow + (i * 64 + lane) * 4) = (unsigned)w;
-    }
+    for (int i = 0; i < NV; ++i) *(unsigned*)(qrow + (i * 64 + lane) * 4) = e4m3_pack4(v[i], qs.inv);
   }
 }
 
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(RT) void ln_modulate_kernel(const float* __restrict
   const float* sh = nullptr;
   const float* sc = nullptr;
   if (shift) {
-    const int64_t r = row_index ? (int64_t)row_index[m] : m / rows_per_batch;
+    const int64_t r = mod_row(row_index, rows_per_batch, m);
     sh = shift + r * tab_ld;
     sc = scale + r * tab_ld;
   }
@@ -164,9 +164,7 @@ __global__ __launch_bounds__(RT) void ln_modulate_kernel(const float* __restrict
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int c = vec * 8 + h * 4;
-      f32x4 y = (v[i][h] - mean) * rstd;
-      if (ln_w) y = y * *(const f32x4*)(ln_w + c) + *(const f32x4*)(ln_b + c);
-      if (sh) y = y * *(const f32x4*)(sc + c) + *(const f32x4*)(sh + c);
+      const f32x4 y = ln_apply(v[i][h], c, mean, rstd, ln_w, ln_b, sc, sh);
 #pragma unroll
       for (int j = 0; j < 4; ++j) o[h * 4 + j] = f2bf(y[j]);
     }
@@ -191,7 +189,7 @@ __global__ __launch_bounds__(256) void gate_residual_kernel(float* __restrict__ 
     f32x4 a = *(const f32x4*)xp, b = *(const f32x4*)(xp + 4);
     f32x4 g0 = {1.f, 1.f, 1.f, 1.f}, g1 = g0;
     if (gate) {
-      const int64_t r = row_index ? (int64_t)row_index[m] : m / rows_per_batch;
+      const int64_t r = mod_row(row_index, rows_per_batch, m);
       g0 = *(const f32x4*)(gate + r * gate_ld + c);
       g1 = *(const f32x4*)(gate + r * gate_ld + c + 4);
     }
@@ -414,21 +412,29 @@ __global__ __launch_bounds__(256) void patchify_kernel(const T* __restrict__ src
 // ------------------------------------------------------------------------------------------
 // unpatchify (FX.py:1126-1149): tokens [L, 4*C] (col = (ph*2+pw)*C + c) -> [C, F, H, W]
 // ------------------------------------------------------------------------------------------
+struct TokenCol {
+  int64_t token;
+  int col;
+};
+// where element i of the flat [C, F, H, W] latent lives in the token rows
+__device__ __forceinline__ TokenCol unpatchify_src(int64_t i, int64_t tok0, int C, int F, int H, int W) {
+  const int hw2 = (H / 2) * (W / 2);
+  const int w = (int)(i % W);
+  int64_t t = i / W;
+  const int h = (int)(t % H);
+  t /= H;
+  const int f = (int)(t % F);
+  const int c = (int)(t / F);
+  return {tok0 + (int64_t)f * hw2 + (h >> 1) * (W / 2) + (w >> 1), (((h & 1) << 1) | (w & 1)) * C + c};
+}
+
 template <typename TO>
 __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict__ tok, int64_t ldt, int64_t tok0, int C,
                                                          int F, int H, int W, TO* __restrict__ dst) {
   const int64_t total = (int64_t)C * F * H * W;
-  const int hw2 = (H / 2) * (W / 2);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int w = (int)(i % W);
-    int64_t t = i / W;
-    const int h = (int)(t % H);
-    t /= H;
-    const int f = (int)(t % F);
-    const int c = (int)(t / F);
-    const int64_t token = tok0 + (int64_t)f * hw2 + (h >> 1) * (W / 2) + (w >> 1);
-    const int col = (((h & 1) << 1) | (w & 1)) * C + c;
-    dst[i] = (TO)tok[token * ldt + col];
+    const TokenCol s = unpatchify_src(i, tok0, C, F, H, W);
+    dst[i] = (TO)tok[s.token * ldt + s.col];
   }
 }
 
@@ -436,35 +442,32 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict
 // Fused sampler step (PIPE.py:926-934): unpatchify both CFG rows, v = u + g (c - u),
 // x += (sigma_next - sigma) v, x = (1 - mask) x_known + mask x.   Latents fp32 [C, F, H, W].
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ float mask_blend(float mk, float known, float x) { return (1.0f - mk) * known + mk * x; }
+
+// the tail of the step for element i with guided velocity v: hand v to a multistep sampler's scheduler.step (v_out), or update and blend
+__device__ __forceinline__ void euler_blend_store(int64_t i, float v, float dt, float* __restrict__ latents, const float* __restrict__ known,
+                                                  const float* __restrict__ mask, int64_t fhw, float* __restrict__ v_out) {
+  if (v_out) {
+    v_out[i] = v;
+    return;
+  }
+  float x = latents[i] + dt * v;
+  if (mask) x = mask_blend(mask[i % fhw], known[i], x);
+  latents[i] = x;
+}
+
 __global__ __launch_bounds__(256) void cfg_euler_blend_kernel(const float* __restrict__ tok_u, const float* __restrict__ tok_c,
                                                               int64_t ldt, int64_t tok0, float guidance, float dt,
                                                               float* __restrict__ latents, const float* __restrict__ known,
                                                               const float* __restrict__ mask, int C, int F, int H, int W,
                                                               float* __restrict__ v_out) {
   const int64_t total = (int64_t)C * F * H * W;
-  const int hw2 = (H / 2) * (W / 2);
   const int64_t fhw = (int64_t)F * H * W;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const int w = (int)(i % W);
-    int64_t t = i / W;
-    const int h = (int)(t % H);
-    t /= H;
-    const int f = (int)(t % F);
-    const int c = (int)(t / F);
-    const int64_t token = tok0 + (int64_t)f * hw2 + (h >> 1) * (W / 2) + (w >> 1);
-    const int col = (((h & 1) << 1) | (w & 1)) * C + c;
-    float v = tok_u[token * ldt + col];
-    if (tok_c) v = v + guidance * (tok_c[token * ldt + col] - v);
-    if (v_out) {                       // multistep samplers: hand the guided velocity to scheduler.step
-      v_out[i] = v;
-      continue;
-    }
-    float x = latents[i] + dt * v;
-    if (mask) {
-      const float mk = mask[i % fhw];
-      x = (1.0f - mk) * known[i] + mk * x;
-    }
-    latents[i] = x;
+    const TokenCol s = unpatchify_src(i, tok0, C, F, H, W);
+    float v = tok_u[s.token * ldt + s.col];
+    if (tok_c) v = v + guidance * (tok_c[s.token * ldt + s.col] - v);
+    euler_blend_store(i, v, dt, latents, known, mask, fhw, v_out);
   }
 }
 
@@ -501,17 +504,7 @@ __global__ __launch_bounds__(256) void cfg_euler_blend_tiled_kernel(const float*
     const int t = idx / W;
     const int ph = t & 1, c = t >> 1;
     const float v = sm_v[(w >> 1) * NCP + ((ph << 1) | (w & 1)) * C + c];
-    const int64_t i = (((int64_t)c * F + f) * H + 2 * h2 + ph) * W + w;
-    if (v_out) {
-      v_out[i] = v;
-      continue;
-    }
-    float x = latents[i] + dt * v;
-    if (mask) {
-      const float mk = mask[i % fhw];
-      x = (1.0f - mk) * known[i] + mk * x;
-    }
-    latents[i] = x;
+    euler_blend_store((((int64_t)c * F + f) * H + 2 * h2 + ph) * W + w, v, dt, latents, known, mask, fhw, v_out);
   }
 }
 
@@ -544,14 +537,15 @@ __global__ __launch_bounds__(256) void lincomb_kernel(float* out, LincombArgs a,
 __global__ __launch_bounds__(256) void mask_blend_kernel(float* __restrict__ x, const float* __restrict__ known,
                                                          const float* __restrict__ mask, int64_t total, int64_t fhw) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-    const float mk = mask[i % fhw];
-    x[i] = (1.0f - mk) * known[i] + mk * x[i];
+    x[i] = mask_blend(mask[i % fhw], known[i], x[i]);
   }
 }
 
-inline int grid_for(int64_t total, int block) {
-  int64_t g = (total + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+// the launch of a grid-stride kernel over `total` items: 256 threads per workgroup, at most 4096 workgroups
+template <typename... P, typename... A>
+void launch_flat(void (*kernel)(P...), int64_t total, void* stream, A... args) {
+  const int64_t g = (total + 255) / 256;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g))), dim3(256), 0, (hipStream_t)stream, args...);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -610,27 +604,37 @@ __global__ __launch_bounds__(256) void checksum_kernel(const uint32_t* __restric
     }                                                                                 \
   } while (0)
 
+// what flexam_ln_modulate and flexam_ln_modulate_fp8 ask of the arguments they share; rows_per_batch leaves as a divisor
+static int ln_check_args(const char* who, int C, int64_t ldx, int64_t ldo, const char* ldo_name, const float* shift, const float* scale, const int32_t* row_index,
+                         int64_t& rows_per_batch, const float* ln_w, const float* ln_b) {
+  FX_REQUIRE(C % 8 == 0 && ldx % 4 == 0 && ldo % 8 == 0, FLEXAM_E_SHAPE, "%s: C%%8, ldx%%4, %s%%8 required (C=%d)", who, ldo_name, C);
+  FX_REQUIRE((shift == nullptr) == (scale == nullptr), FLEXAM_E_ARG, "%s: shift and scale go together", who);
+  FX_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), FLEXAM_E_ARG, "%s: ln_w and ln_b go together", who);
+  FX_REQUIRE(!shift || row_index || rows_per_batch > 0, FLEXAM_E_ARG, "%s: need row_index or rows_per_batch", who);
+  if (rows_per_batch <= 0) rows_per_batch = 1;
+  return FLEXAM_OK;
+}
+
+// does the wave-per-row form take this width?  (ln_modulate_wave_kernel<NV8>: C = 512 * NV8, NV8 <= 8)
+static bool ln_wave_takes(int C) { return C % 512 == 0 && C <= 4096; }
+
+template <bool FP8, typename... A>
+static void launch_ln_wave(int C, int64_t M, void* stream, A... args) {
+  const dim3 grid((unsigned)M), block(64);     // one wave per row, one row per workgroup
+#define LN_WAVE(N_) case N_: hipLaunchKernelGGL((ln_modulate_wave_kernel<N_, FP8>), grid, block, 0, (hipStream_t)stream, args...); break;
+  switch (C / 512) { LN_WAVE(1) LN_WAVE(2) LN_WAVE(3) LN_WAVE(4) LN_WAVE(5) LN_WAVE(6) LN_WAVE(7) LN_WAVE(8) }
+#undef LN_WAVE
+}
+
 extern "C" int flexam_ln_modulate(const float* x, int64_t ldx, int64_t M, int C, float eps, const float* shift,
                                   const float* scale, int64_t tab_ld, const int32_t* row_index, int64_t rows_per_batch,
                                   const float* ln_w, const float* ln_b, void* out, int64_t ldo, void* stream) {
   FX_REQUIRE(x && out && M > 0, FLEXAM_E_ARG, "ln_modulate: null pointer or empty");
-  FX_REQUIRE(C % 8 == 0 && ldx % 4 == 0 && ldo % 8 == 0, FLEXAM_E_SHAPE, "ln_modulate: C%%8, ldx%%4, ldo%%8 required (C=%d)", C);
-  FX_REQUIRE((shift == nullptr) == (scale == nullptr), FLEXAM_E_ARG, "ln_modulate: shift and scale go together");
-  FX_REQUIRE((ln_w == nullptr) == (ln_b == nullptr), FLEXAM_E_ARG, "ln_modulate: ln_w and ln_b go together");
-  FX_REQUIRE(!shift || row_index || rows_per_batch > 0, FLEXAM_E_ARG, "ln_modulate: need row_index or rows_per_batch");
-  if (rows_per_batch <= 0) rows_per_batch = 1;
-  if (C % 512 == 0 && C <= 4096) {             // wave-per-row form (the DiT width 3072 = 512 * 6)
-    const dim3 grid((unsigned)M), block(64);   // one wave per row, one row per workgroup
-#define LN_WAVE(NV8_)                                                                                                              \
-  case NV8_:                                                                                                                       \
-    hipLaunchKernelGGL(ln_modulate_wave_kernel<NV8_>, grid, block, 0, (hipStream_t)stream, x, ldx, M, eps, shift, scale, tab_ld, \
-                       row_index, rows_per_batch, ln_w, ln_b, (bf16*)out, ldo);                                                    \
-    break;
-    switch (C / 512) { LN_WAVE(1) LN_WAVE(2) LN_WAVE(3) LN_WAVE(4) LN_WAVE(5) LN_WAVE(6) LN_WAVE(7) LN_WAVE(8) }
-#undef LN_WAVE
-    return flexam_check_launch("flexam_ln_modulate");
-  }
-  DISPATCH_VPT(C, hipLaunchKernelGGL(ln_modulate_kernel<VPT>, dim3((unsigned)M), dim3(RT), 0, (hipStream_t)stream, x, ldx, C, eps,
+  if (const int rc = ln_check_args("ln_modulate", C, ldx, ldo, "ldo", shift, scale, row_index, rows_per_batch, ln_w, ln_b)) return rc;
+  if (ln_wave_takes(C))                        // (the DiT width 3072 = 512 * 6)
+    launch_ln_wave<false>(C, M, stream, x, ldx, M, eps, shift, scale, tab_ld, row_index, rows_per_batch, ln_w, ln_b, (bf16*)out, ldo);
+  else
+    DISPATCH_VPT(C, hipLaunchKernelGGL(ln_modulate_kernel<VPT>, dim3((unsigned)M), dim3(RT), 0, (hipStream_t)stream, x, ldx, C, eps,
                                      shift, scale, tab_ld, row_index, rows_per_batch, ln_w, ln_b, (bf16*)out, ldo));
   return flexam_check_launch("flexam_ln_modulate");
 }
@@ -641,20 +645,10 @@ extern "C" int flexam_ln_modulate_fp8(const float* x, int64_t ldx, int64_t M, in
                                       float next_bias, void* stream) {
   FX_REQUIRE(x && q_out && row_scale && M > 0, FLEXAM_E_ARG, "ln_modulate_fp8: null pointer or empty");
   FX_REQUIRE(!next_scale || (next_wnorm >= 0.f && next_bias >= 0.f), FLEXAM_E_ARG, "ln_modulate_fp8: negative norm bound");
-  FX_REQUIRE(C % 512 == 0 && C <= 4096, FLEXAM_E_SHAPE, "ln_modulate_fp8: row width %d must be a multiple of 512, at most 4096", C);
-  FX_REQUIRE(ldx % 4 == 0 && ldq % 8 == 0, FLEXAM_E_SHAPE, "ln_modulate_fp8: ldx%%4, ldq%%8 required");
-  FX_REQUIRE((shift == nullptr) == (scale == nullptr) && (ln_w == nullptr) == (ln_b == nullptr), FLEXAM_E_ARG,
-             "ln_modulate_fp8: shift / scale and ln_w / ln_b go together");
-  FX_REQUIRE(!shift || row_index || rows_per_batch > 0, FLEXAM_E_ARG, "ln_modulate_fp8: need row_index or rows_per_batch");
-  if (rows_per_batch <= 0) rows_per_batch = 1;
-  const dim3 grid((unsigned)M), block(64);
-#define LN_WAVE8(NV8_)                                                                                                                   \
-  case NV8_:                                                                                                                            \
-    hipLaunchKernelGGL((ln_modulate_wave_kernel<NV8_, true>), grid, block, 0, (hipStream_t)stream, x, ldx, M, eps, shift, scale, tab_ld, \
-                       row_index, rows_per_batch, ln_w, ln_b, (bf16*)q_out, ldq, row_scale, next_scale, next_wnorm, next_bias);         \
-    break;
-  switch (C / 512) { LN_WAVE8(1) LN_WAVE8(2) LN_WAVE8(3) LN_WAVE8(4) LN_WAVE8(5) LN_WAVE8(6) LN_WAVE8(7) LN_WAVE8(8) }
-#undef LN_WAVE8
+  FX_REQUIRE(ln_wave_takes(C), FLEXAM_E_SHAPE, "ln_modulate_fp8: row width %d must be a multiple of 512, at most 4096", C);
+  if (const int rc = ln_check_args("ln_modulate_fp8", C, ldx, ldq, "ldq", shift, scale, row_index, rows_per_batch, ln_w, ln_b)) return rc;
+  launch_ln_wave<true>(C, M, stream, x, ldx, M, eps, shift, scale, tab_ld, row_index, rows_per_batch, ln_w, ln_b, (bf16*)q_out, ldq, row_scale,
+                       next_scale, next_wnorm, next_bias);
   return flexam_check_launch("flexam_ln_modulate_fp8");
 }
 
@@ -664,8 +658,7 @@ extern "C" int flexam_gate_residual(float* x, int64_t ldx, const void* y, int64_
   FX_REQUIRE(C % 8 == 0 && ldx % 4 == 0 && ldy % 8 == 0, FLEXAM_E_SHAPE, "gate_residual: C%%8, ldx%%4, ldy%%8 required");
   FX_REQUIRE(!gate || row_index || rows_per_batch > 0, FLEXAM_E_ARG, "gate_residual: need row_index or rows_per_batch");
   if (rows_per_batch <= 0) rows_per_batch = 1;
-  hipLaunchKernelGGL(gate_residual_kernel, dim3(grid_for(M * (C / 8), 256)), dim3(256), 0, (hipStream_t)stream, x, ldx,
-                     (const bf16*)y, ldy, gate, gate_ld, row_index, rows_per_batch, M, C);
+  launch_flat(gate_residual_kernel, M * (C / 8), stream, x, ldx, (const bf16*)y, ldy, gate, gate_ld, row_index, rows_per_batch, M, C);
   return flexam_check_launch("flexam_gate_residual");
 }
 
@@ -724,9 +717,15 @@ extern "C" int flexam_mod_table(const float* mod, const float* e, const float* m
   FX_REQUIRE(mod && e && out, FLEXAM_E_ARG, "mod_table: null pointer");
   FX_REQUIRE(nblk > 0 && R > 0 && nj > 0 && nj <= 8 && C > 0 && rows_per_batch > 0, FLEXAM_E_SHAPE, "mod_table: bad sizes");
   FX_REQUIRE(dens_slots == -1 || (mdens && dens && nslot > 0), FLEXAM_E_ARG, "mod_table: density terms need mdens/dens");
-  hipLaunchKernelGGL(mod_table_kernel, dim3(grid_for((int64_t)nblk * R * nj * C, 256)), dim3(256), 0, (hipStream_t)stream, mod, e,
-                     mdens, dens, out, nblk, R, nj, nslot, C, rows_per_batch, scale_mask, dens_slots);
+  launch_flat(mod_table_kernel, (int64_t)nblk * R * nj * C, stream, mod, e, mdens, dens, out, nblk, R, nj, nslot, C, rows_per_batch, scale_mask, dens_slots);
   return flexam_check_launch("flexam_mod_table");
+}
+
+template <int MAXM, int NPW, typename... A>
+static void launch_small_linear(int w_is_bf16, int N, void* stream, const float* x, int64_t ldx, const void* W, A... rest) {
+  const dim3 grid((N + 4 * NPW - 1) / (4 * NPW)), block(256);       // 4 waves per workgroup, NPW outputs per wave
+  if (w_is_bf16) hipLaunchKernelGGL((small_linear_kernel<bf16, MAXM, NPW>), grid, block, 0, (hipStream_t)stream, x, ldx, (const bf16*)W, rest...);
+  else hipLaunchKernelGGL((small_linear_kernel<float, MAXM, NPW>), grid, block, 0, (hipStream_t)stream, x, ldx, (const float*)W, rest...);
 }
 
 extern "C" int flexam_small_linear_f32(const float* x, int64_t ldx, const void* W, int w_is_bf16, int64_t ldw, const float* b,
@@ -734,20 +733,10 @@ extern "C" int flexam_small_linear_f32(const float* x, int64_t ldx, const void* 
   FX_REQUIRE(x && W && y, FLEXAM_E_ARG, "small_linear: null pointer");
   FX_REQUIRE(M >= 1 && M <= 32, FLEXAM_E_SHAPE, "small_linear: M=%d must be in 1..32", M);
   FX_REQUIRE(K % 4 == 0 && ldx % 4 == 0 && ldw % 4 == 0, FLEXAM_E_SHAPE, "small_linear: K, ldx, ldw must be multiples of 4");
-  dim3 block(256);
-  if (M <= 8) {                       // one output per wave (two distinct timesteps per sample in every demo mode)
-    dim3 grid((N + 3) / 4);
-    if (w_is_bf16)
-      hipLaunchKernelGGL((small_linear_kernel<bf16, 8, 1>), grid, block, 0, (hipStream_t)stream, x, ldx, (const bf16*)W, ldw, b, y, ldy, M, N, K, silu_in);
-    else
-      hipLaunchKernelGGL((small_linear_kernel<float, 8, 1>), grid, block, 0, (hipStream_t)stream, x, ldx, (const float*)W, ldw, b, y, ldy, M, N, K, silu_in);
-  } else {                            // soft foreground masks: hundreds of distinct timesteps, 32 rows per pass over the weights
-    dim3 grid((N + 15) / 16);
-    if (w_is_bf16)
-      hipLaunchKernelGGL((small_linear_kernel<bf16, 32, 4>), grid, block, 0, (hipStream_t)stream, x, ldx, (const bf16*)W, ldw, b, y, ldy, M, N, K, silu_in);
-    else
-      hipLaunchKernelGGL((small_linear_kernel<float, 32, 4>), grid, block, 0, (hipStream_t)stream, x, ldx, (const float*)W, ldw, b, y, ldy, M, N, K, silu_in);
-  }
+  // one output per wave (two distinct timesteps per sample in every demo mode), or (soft foreground masks: hundreds of distinct
+  // timesteps) 32 rows per pass over the weights
+  if (M <= 8) launch_small_linear<8, 1>(w_is_bf16, N, stream, x, ldx, W, ldw, b, y, ldy, M, N, K, silu_in);
+  else launch_small_linear<32, 4>(w_is_bf16, N, stream, x, ldx, W, ldw, b, y, ldy, M, N, K, silu_in);
   return flexam_check_launch("flexam_small_linear_f32");
 }
 
@@ -764,10 +753,8 @@ extern "C" int flexam_patchify(const void* src, int src_is_bf16, int C, int F, i
   // odd H / W: the stride-2 patch convolution drops the last row / column (FX.py:885: Conv3d without padding), as the kernel's H / 2, W / 2 do
   FX_REQUIRE(C > 0 && F > 0 && H >= 2 && W >= 2, FLEXAM_E_SHAPE, "patchify: needs at least one 2 x 2 patch (H = %d, W = %d)", H, W);
   const int64_t total = (int64_t)F * (H / 2) * (W / 2) * C * 4;
-  if (src_is_bf16)
-    hipLaunchKernelGGL(patchify_kernel<bf16>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)src, C, F, H, W, (bf16*)dst, ldd, col0, row0);
-  else
-    hipLaunchKernelGGL(patchify_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)src, C, F, H, W, (bf16*)dst, ldd, col0, row0);
+  if (src_is_bf16) launch_flat(patchify_kernel<bf16>, total, stream, (const bf16*)src, C, F, H, W, (bf16*)dst, ldd, col0, row0);
+  else launch_flat(patchify_kernel<float>, total, stream, (const float*)src, C, F, H, W, (bf16*)dst, ldd, col0, row0);
   return flexam_check_launch("flexam_patchify");
 }
 
@@ -776,14 +763,12 @@ extern "C" int flexam_unpatchify(const float* tok, int64_t ldt, int64_t tok0, in
   FX_REQUIRE(tok && dst, FLEXAM_E_ARG, "unpatchify: null pointer");
   FX_REQUIRE(H % 2 == 0 && W % 2 == 0, FLEXAM_E_SHAPE, "unpatchify: H, W must be even");
   const int64_t total = (int64_t)C * F * H * W;
-  if (dst_is_bf16)
-    hipLaunchKernelGGL(unpatchify_kernel<bf16>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, tok, ldt, tok0, C, F, H, W, (bf16*)dst);
-  else
-    hipLaunchKernelGGL(unpatchify_kernel<float>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, tok, ldt, tok0, C, F, H, W, (float*)dst);
+  if (dst_is_bf16) launch_flat(unpatchify_kernel<bf16>, total, stream, tok, ldt, tok0, C, F, H, W, (bf16*)dst);
+  else launch_flat(unpatchify_kernel<float>, total, stream, tok, ldt, tok0, C, F, H, W, (float*)dst);
   return flexam_check_launch("flexam_unpatchify");
 }
 
-static int launch_cfg_euler_blend(const float* tok_u, const float* tok_c, int64_t ldt, int64_t tok0, float guidance, float dt, float* latents,
+static void launch_cfg_euler_blend(const float* tok_u, const float* tok_c, int64_t ldt, int64_t tok0, float guidance, float dt, float* latents,
                                   const float* known, const float* mask, int C, int F, int H, int W, float* v_out, hipStream_t st) {
   const size_t lds = (size_t)(W / 2) * (4 * C + 1) * sizeof(float);
   const bool vec = ldt % 4 == 0 && (uintptr_t)tok_u % 16 == 0 && (!tok_c || (uintptr_t)tok_c % 16 == 0) && lds <= 64 * 1024;
@@ -791,9 +776,7 @@ static int launch_cfg_euler_blend(const float* tok_u, const float* tok_c, int64_
     hipLaunchKernelGGL(cfg_euler_blend_tiled_kernel, dim3(F * (H / 2)), dim3(256), lds, st, tok_u, tok_c, ldt, tok0, guidance, dt, latents,
                        known, mask, C, F, H, W, v_out);
   else
-    hipLaunchKernelGGL(cfg_euler_blend_kernel, dim3(grid_for((int64_t)C * F * H * W, 256)), dim3(256), 0, st, tok_u, tok_c, ldt, tok0,
-                       guidance, dt, latents, known, mask, C, F, H, W, v_out);
-  return 0;
+    launch_flat(cfg_euler_blend_kernel, (int64_t)C * F * H * W, st, tok_u, tok_c, ldt, tok0, guidance, dt, latents, known, mask, C, F, H, W, v_out);
 }
 
 extern "C" int flexam_cfg_euler_blend(const float* tok_uncond, const float* tok_cond, int64_t ldt, int64_t tok0, float guidance,
@@ -823,20 +806,19 @@ extern "C" int flexam_lincomb_f32(float* out, int64_t n, int n_terms, const floa
     a.x[i] = terms[i];
     a.c[i] = coefs[i];
   }
-  hipLaunchKernelGGL(lincomb_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, out, a, n_terms, n / 4);
+  launch_flat(lincomb_kernel, n / 4, stream, out, a, n_terms, n / 4);
   return flexam_check_launch("flexam_lincomb_f32");
 }
 
 extern "C" int flexam_mask_blend_f32(float* x, const float* known, const float* mask, int C, int64_t fhw, void* stream) {
   FX_REQUIRE(x && known && mask && C > 0 && fhw > 0, FLEXAM_E_ARG, "mask_blend_f32: bad arguments");
-  hipLaunchKernelGGL(mask_blend_kernel, dim3(grid_for((int64_t)C * fhw, 256)), dim3(256), 0, (hipStream_t)stream, x, known, mask,
-                     (int64_t)C * fhw, fhw);
+  launch_flat(mask_blend_kernel, (int64_t)C * fhw, stream, x, known, mask, (int64_t)C * fhw, fhw);
   return flexam_check_launch("flexam_mask_blend_f32");
 }
 
 extern "C" int flexam_axpby_f32(float* y, float a, const float* x, float b, int64_t n, void* stream) {
   FX_REQUIRE(y && x && n > 0 && n % 4 == 0, FLEXAM_E_ARG, "axpby_f32: null pointer or n %% 4 != 0");
-  hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, y, a, x, b, n / 4);
+  launch_flat(axpby_kernel, n / 4, stream, y, a, x, b, n / 4);
   return flexam_check_launch("flexam_axpby_f32");
 }
 
@@ -844,7 +826,6 @@ extern "C" int flexam_checksum(const void* data, int64_t nbytes, uint64_t* out2,
   FX_REQUIRE(data && out2 && nbytes > 0, FLEXAM_E_ARG, "checksum: null pointer or empty buffer");
   FX_REQUIRE((uintptr_t)data % 4 == 0 && (uintptr_t)out2 % 8 == 0, FLEXAM_E_ARG, "checksum: data must be 4-byte, out 8-byte aligned");
   const int64_t words = nbytes / 4;
-  hipLaunchKernelGGL(checksum_kernel, dim3(grid_for(words > 0 ? words : 1, 256)), dim3(256), 0, (hipStream_t)stream, (const uint32_t*)data,
-                     words, (const uint8_t*)data + words * 4, (int)(nbytes - words * 4), (unsigned long long*)out2);
+  launch_flat(checksum_kernel, words, stream, (const uint32_t*)data, words, (const uint8_t*)data + words * 4, (int)(nbytes - words * 4), (unsigned long long*)out2);
   return flexam_check_launch("flexam_checksum");
 }

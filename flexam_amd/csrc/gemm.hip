@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dit_rows.h"
 #include "flexam_hip.h"
 #include "gemm_tile.h"
 
@@ -554,7 +555,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
               const int row = t0 * RT + 4 * i;           // + rr
               int gr;
               if constexpr (GATE == 1) gr = growl[row];
-              else gr = (mw + row + rr) / p.rows_per_batch;
+              else gr = batch_row(p.rows_per_batch, mw + row + rr);
               gv[i] = *(const f32x4*)(p.gate + (int64_t)gr * p.gate_ld + nw);
             }
           }
@@ -661,7 +662,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
 #pragma unroll
         for (int t = 0; t < NRT; ++t) {
           const int m = min(mrow + t * RT, p.M - 1);
-          grr[t] = p.gate_row ? p.gate_row[m] : (int)(m / p.rows_per_batch);
+          grr[t] = (int)mod_row(p.gate_row, p.rows_per_batch, m);
         }
       }
       // loads are unconditional (rows / columns past the edge re-read the last valid ones), only the stores are predicated
@@ -711,8 +712,7 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_kernel(GemmParams p, const i
     const float* grow = nullptr;
     if constexpr (EPI == EPI_GATE_RESIDUAL) {
       if (p.gate) {
-        const int64_t r = p.gate_row ? (int64_t)p.gate_row[m] : (int64_t)m / p.rows_per_batch;
-        grow = p.gate + r * p.gate_ld;
+        grow = p.gate + mod_row(p.gate_row, p.rows_per_batch, m) * p.gate_ld;
         asm volatile("" ::"v"(grow));                   // the gate_row load is "used" even if every column below is out of range
       }
     }
@@ -770,7 +770,7 @@ __global__ __launch_bounds__(512) void gemm_splitk_finish_kernel(GemmParams p) {
   const float* base = p.ws + (int64_t)tr * p.split_s * SLAB;
   const float* grow = nullptr;
   if constexpr (EPI == EPI_GATE_RESIDUAL) {
-    if (p.gate) grow = p.gate + (p.gate_row ? (int64_t)p.gate_row[m] : (int64_t)m / p.rows_per_batch) * p.gate_ld;
+    if (p.gate) grow = p.gate + mod_row(p.gate_row, p.rows_per_batch, m) * p.gate_ld;
   }
 #pragma unroll
   for (int v = 0; v < NV; ++v) {

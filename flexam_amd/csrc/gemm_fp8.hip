@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dit_rows.h"
 #include "flexam_hip.h"
 #include "gemm_tile.h"
 
@@ -305,7 +306,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
             // non-temporal, like the bf16 GEMM's epilogues (gemm.hip): X and the e4m3 GELU output are touched once per launch
             xv[i] = __builtin_nontemporal_load((const f32x4*)(xtile + (int64_t)(t0 * 16 + 4 * i) * p.ldx * 4 + xlane));
             if constexpr (GATE == 1) gr[i] = p.gate_row[m];
-            if constexpr (GATE == 2) gr[i] = m / p.rows_per_batch;
+            if constexpr (GATE == 2) gr[i] = batch_row(p.rows_per_batch, m);
           }
           if constexpr (GATE != 0) {
 #pragma unroll
@@ -352,11 +353,10 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
         const float inv = __builtin_amdgcn_rcpf(so_l[16 * t + (le & 15)]);
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-          const f32x4 y4 = yv(t, v);
-          int w = 0;
-          w = __builtin_amdgcn_cvt_pk_fp8_f32(gelu_tanh(y4[0]) * inv, gelu_tanh(y4[1]) * inv, w, false);
-          w = __builtin_amdgcn_cvt_pk_fp8_f32(gelu_tanh(y4[2]) * inv, gelu_tanh(y4[3]) * inv, w, true);
-          *(int*)(stg + wr_row * 64 + ((v ^ ((wr_row >> 1) & 3)) << 4) + wr_g * 4) = w;
+          f32x4 y4 = yv(t, v);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) y4[j] = gelu_tanh(y4[j]);
+          *(unsigned*)(stg + wr_row * 64 + ((v ^ ((wr_row >> 1) & 3)) << 4) + wr_g * 4) = e4m3_pack4(y4, inv);
         }
         const u32x4 o = *(const u32x4*)(stg + rd_row * 64 + ((rd_c ^ ((rd_row >> 1) & 3)) << 4));
         __builtin_nontemporal_store(o, (u32x4*)(crow + (int64_t)(t * 16) * p.ldc));
@@ -374,11 +374,10 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
       for (int v = 0; v < NV; ++v) {
         const int n = ncol + v * 16;
         if (n >= p.N) continue;
-        const f32x4 y4 = yv(t, v);
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(gelu_tanh(y4[0]) * inv, gelu_tanh(y4[1]) * inv, w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(gelu_tanh(y4[2]) * inv, gelu_tanh(y4[3]) * inv, w, true);
-        *(int*)((uint8_t*)p.C + (int64_t)m * p.ldc + n) = w;
+        f32x4 y4 = yv(t, v);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) y4[j] = gelu_tanh(y4[j]);
+        *(unsigned*)((uint8_t*)p.C + (int64_t)m * p.ldc + n) = e4m3_pack4(y4, inv);
       }
     }
     wait_vm<0>();
@@ -421,8 +420,7 @@ __global__ __launch_bounds__(512, 2) void gemm_fp8_kernel(Gemm8Params p) {
     const float* grow = nullptr;
     if constexpr (EPI == EPI_GATE_RESIDUAL) {
       if (p.gate) {
-        const int64_t r = p.gate_row ? (int64_t)p.gate_row[m] : (int64_t)m / p.rows_per_batch;
-        grow = p.gate + r * p.gate_ld;
+        grow = p.gate + mod_row(p.gate_row, p.rows_per_batch, m) * p.gate_ld;
         asm volatile("" ::"v"(grow));
       }
     }
@@ -466,22 +464,15 @@ __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const bf16* __re
 #pragma unroll
       for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(bf2f(v[j])));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const float s = amax > 0.f ? amax * (1.0f / 448.0f) : 1.0f;
-    const float inv = 1.0f / s;
-    if (lane == 0) scale[m] = s;
+    const RowScale8 s = e4m3_row_scale(wave_max(amax));
+    if (lane == 0) scale[m] = s.scale;
     uint8_t* qr = q + m * ldq;
     for (int c = lane * 8; c < K; c += 512) {
       const bf16x8 v = *(const bf16x8*)(xr + c);
       u32x2 o;
 #pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4 * h]) * inv, bf2f(v[4 * h + 1]) * inv, w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(bf2f(v[4 * h + 2]) * inv, bf2f(v[4 * h + 3]) * inv, w, true);
-        o[h] = (unsigned)w;
-      }
+      for (int h = 0; h < 2; ++h)
+        o[h] = e4m3_pack4((f32x4){bf2f(v[4 * h]), bf2f(v[4 * h + 1]), bf2f(v[4 * h + 2]), bf2f(v[4 * h + 3])}, s.inv);
       *(u32x2*)(qr + c) = o;
     }
   }
