@@ -20,13 +20,14 @@ All arithmetic runs in libflexam_hip.so (flexam_amd/hip.py); torch only allocate
 """
 import math
 import os
-from collections import namedtuple
 from contextlib import nullcontext
 from typing import List, Optional
 
 import torch
 
 from . import hip
+from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked
+from .dit_sp import HeadAllToAll, KVGather, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
 
@@ -43,11 +44,27 @@ def _conv_cl(weight: torch.Tensor, bias: torch.Tensor, device) -> PackedConv:
     return PackedConv(weight.detach().to(device, F32).reshape(co, ci, kh * kw).permute(0, 2, 1), groups, bias, device)
 
 
-# What the block and head launches of one forward depend on apart from buffer contents and addresses, resolved once at the start of
-# DiTEngine.run (DiTEngine._mode): the stages read it, and a recorded launch plan is keyed on it
-_Mode = namedtuple("_Mode", "B Lp lc tok0 R rows_per_batch only_row "                                 # sizes (Lp: padded sequence)
-                   "per_layer share0 sage sage_gather sage_fused fp8 fp8_oproj ffn_apriori "        # switches
-                   "sp rank sp_mode sp_pieces sp_overlap_level sp_fused_qkv use_plan")              # layout
+def _fp8_weight(pk: dict, name: str):
+    """(e4m3 bytes, per-output-channel scales) of pack entry `name`, quantised once per pack (the pack is rebuilt when a parameter
+    changes): the one store behind DiTEngine.enable_fp8 and the blocks called as modules."""
+    key = "_f8_" + name
+    if key not in pk:
+        w = pk[name]
+        pk[key] = hip.quantize_rows_fp8(w.to(BF16) if w.dtype == F8 else w)     # (qfloat8 storage: one matrix upcast at a time)
+    return pk[key]
+
+
+# the pack that owns each fp8 weight: the self- / cross-attention module's (a block pack's "sa" / "ca", which those modules ask when the
+# block is called as a module) or the block's own (None)
+_FP8_OWNER = dict(wqkv="sa", wo="sa", cwq="ca", cwo="ca", w1=None, w2=None)
+
+
+def _proj_fp8(h: torch.Tensor, pk: dict, wname: str, bias, epilogue: int = 0) -> torch.Tensor:
+    """h [M, K] bf16 -> bf16 [M, N] on the fp8 (OCP e4m3) MFMA path: rows of h quantised per call (absmax / 448), weights per output channel,
+    fp32 accumulation, scales / bias / activation in the epilogue (csrc/gemm_fp8.hip) -- the module-seam form of DiTEngine.enable_fp8."""
+    a8, sa = hip.quantize_rows_fp8(h)
+    w8, sw = _fp8_weight(pk, wname)
+    return hip.gemm_fp8(a8, sa, w8, sw, bias, epilogue=epilogue)
 
 
 class DiTEngine:
@@ -73,9 +90,12 @@ class DiTEngine:
         hip.device_check()
         self.sp_group = None
         self.sp_rank, self.sp_size = 0, 1
+        self.sp_mode, self.sp_overlap_level, self.sp_pieces, self.sp_fused_qkv = SINGLE_RANK
+        self.sp_overlap = False
         self.world_group, self.world_size = None, 1
         self.cfg_size, self.cfg_row = 1, 0          # cfg_size 2: this rank computes only CFG row `cfg_row`
         self._ws = {}
+        self._attn8 = {}                            # MXFP8 operand buffers of the quantised self-attention (_attn8_buffers)
         self._ws_gen = 0                            # bumped whenever the activation buffers are dropped: recorded launch plans name their addresses
         self._angles = None
         self.cond = None
@@ -133,33 +153,8 @@ class DiTEngine:
         """Parallel layout of this rank: token chunk `sp_rank` of `sp_size` inside `sp_group`; with cfg_size = 2 the
         world is two such groups, one per CFG row (world rank = cfg_row * sp_size + sp_rank)."""
         self.sp_group, self.sp_rank, self.sp_size = sp_group, sp_rank, sp_size
-        mode = os.environ.get("FLEXAM_SP_MODE", "allgather")
-        if mode not in ("ulysses", "allgather"):
-            raise ValueError(f"FLEXAM_SP_MODE={mode!r}: expected 'ulysses' or 'allgather'")
-        self.sp_mode = mode if (mode == "allgather" or self.nh % max(sp_size, 1) == 0) else "allgather"
-        # FLEXAM_SP_OVERLAP.  K|V all-gather: 0 (default since r6) = ONE gather per block and CFG row, waited for, then ONE ordinary
-        # attention call; 1 = head-group pieces with local-chunk-first partial attention + merge underneath them.  r5 measured the
-        # overlap machinery at 6.7 ms of a 48 ms rank step at 8 GPUs (three partial calls parking 17 fp32 slots for a merge: 605 us of
-        # attention per block against 342 for the one call; profiles/r5o_*): it pays only on links slow enough that hiding ~0.3 ms of
-        # a block's gather is worth 0.22 ms of compute, which bench.py's layout probe measures per node -- the default is the form
-        # that is fastest on compute.  All-to-all over heads: 1 (default) = a sample's blocks leave under the other sample's projection,
-        # 2 = attention per sample as well, 0 = one exchange for the pair.
-        ov = os.environ.get("FLEXAM_SP_OVERLAP")
-        ov = ("1" if self.sp_mode == "ulysses" else "0") if ov is None else ov.strip().lower()
-        self.sp_overlap_level = 0 if ov in ("0", "off", "false", "no", "") else (2 if ov == "2" else 1)      # anything else: on (1)
+        self.sp_mode, self.sp_overlap_level, self.sp_pieces, self.sp_fused_qkv = resolve_parallel(os.environ, self.nh, sp_size)
         self.sp_overlap = self.sp_overlap_level != 0
-        # with the overlap on, the K|V gather is cut into `sp_pieces` groups of heads, one collective each: the attention of a group starts
-        # when ITS piece has landed, the later pieces travel underneath it.  Default: 2 pieces from 4 chunks on (3+ peers: the gather
-        # outlasts the local-chunk attention it hides under), 1 below and whenever the gather is waited for (two attention calls on half
-        # the heads each fill 256 CUs worse than one: 44.2 against 41.4 ms per rank step, profiles/r5o_*)
-        env = os.environ.get("FLEXAM_SP_PIECES")
-        pieces = int(env) if env is not None else (2 if (sp_size >= 4 and self.nh % 2 == 0 and self.sp_overlap and self.sp_mode == "allgather") else 1)
-        if self.sp_mode != "allgather":
-            pieces = 1                              # (head-group pieces belong to the gather)
-        if pieces < 1 or self.nh % pieces:
-            raise ValueError(f"FLEXAM_SP_PIECES={pieces}: must divide the {self.nh} heads")
-        self.sp_pieces = pieces if sp_size > 1 else 1
-        self.sp_fused_qkv = os.environ.get("FLEXAM_SP_FUSED_QKV", "1") != "0"
         # FLEXAM_CU_BUDGET=<n>: plan the persistent grids for n CUs (a multiple of 8) while this layout runs collectives beside compute --
         # a kernel that owns every CU leaves a collective's own kernels nowhere to run until it ends.  Not set by default: on one GPU
         # the emulation's stand-in (a single delay wave) finds room beside the GEMMs, and 8 CUs cost 3 % of a rank's step
@@ -195,8 +190,7 @@ class DiTEngine:
             for p in self.blocks:
                 q = {}
                 for name in ("wqkv", "cwq", "w1", "w2", "wo", "cwo"):
-                    w = p[name]                                        # (qfloat8 storage: one e4m3 matrix upcast at a time)
-                    q[name], q["s_" + name] = hip.quantize_rows_fp8(w.to(BF16) if w.dtype == F8 else w)
+                    q[name], q["s_" + name] = _fp8_weight(p[_FP8_OWNER[name]] if _FP8_OWNER[name] else p, name)
                 # bounds for the a-priori scale of FFN1's e4m3 output (flexam_ln_modulate_fp8, next_scale): the largest L2 norm of a
                 # DEQUANTISED w1 row (what the MFMA multiplies) and the largest |bias|; two floats per layer, read back once
                 deq = q["w1"].view(torch.float8_e4m3fn).float() * q["s_w1"][:, None]
@@ -345,7 +339,7 @@ class DiTEngine:
 
     def _attn8_buffers(self, nb, lc, heads=None):
         """MXFP8 operand buffers of the quantised self-attention (one set per (samples, tokens, heads) shape, reused by every block)."""
-        cache = self.__dict__.setdefault("_attn8", {})
+        cache = self._attn8
         heads = self.nh if heads is None else heads
         if (nb, lc, heads) not in cache:
             if any(k[1:] != (lc, heads) for k in cache):          # another token / head count: drop the old sets (as _workspace does)
@@ -371,46 +365,19 @@ class DiTEngine:
     def _mode(self, bx, R, rows_per_batch, only_row, rows_shared, teacache):
         """The mode of one forward (see _Mode).  Every environment switch a forward reads is read here, once per forward: tests and
         benchlib flip them between forwards."""
-        env, cd, sp, L = os.environ, self.cond, self.sp_size, self.cond["L"]
-        B = cd["B"] if only_row is None else 1
-        sp_mode, pieces, overlap = getattr(self, "sp_mode", None), getattr(self, "sp_pieces", 1), getattr(self, "sp_overlap_level", 0)
-        # A sequence that does not divide over the ranks is padded to the next multiple with zero tokens at its end, as the reference
-        # does (FX.py:919-925); they are rows like any other in every token-local op, never keys of self-attention (the key ranges
-        # end at L), and the head gather drops them
-        # VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION under the K|V gather (one gather, waited for): the ranks exchange their MXFP8 key / value
-        # RECORDS (one per 64 keys) instead of bf16 rows, so every chunk is a whole number of 64-key tiles: the padding unit is 64 x ranks
-        sage_asked = env.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION"
-        sage_gather = sage_asked and self.fused and sp > 1 and sp_mode == "allgather" and overlap == 0 and pieces == 1
-        unit = sp * hip.ATTN_KV_TILE if sage_gather else sp
-        Lp = -(-L // unit) * unit
-        # the reference reads the switch at every attention call (attention_utils.py:195); quantised self-attention on one rank: MXFP8
-        # operands of the rank's tokens.  Sequence parallel with the all-to-all over heads: every rank ends up with ALL tokens of its
-        # heads in bf16, packs them and runs the MXFP8 kernel on them.  K|V all-gather in its default form (one gather, waited for):
-        # each rank quantises ITS keys / values and the MXFP8 records are what is gathered (sage_gather, above).  The overlapped gather
-        # forms (head-group pieces, partial softmaxes) keep the bf16 kernel -- said once per process
-        sage = sage_asked and self.fused and (sp == 1 or (sp_mode == "ulysses" and Lp == L) or sage_gather)
-        if sage_asked and not sage and not DiTEngine._sage_warned:
+        cd, env = self.cond, os.environ
+        m = resolve_mode(env, fused=self.fused, nl=self.nl, nh=self.nh, hd=self.hd, dim=self.dim, table_limit=self.table_limit, fp8=self.fp8,
+                         sp=self.sp_size, rank=self.sp_rank,
+                         parallel=(self.sp_mode, self.sp_overlap_level, self.sp_pieces, self.sp_fused_qkv),
+                         B=cd["B"], L=cd["L"], dens_same=cd.get("dens_same", False), bx=bx, R=R, rows_per_batch=rows_per_batch,
+                         only_row=only_row, rows_shared=rows_shared, teacache=teacache is not None)
+        if sage_asked(env) and not m.sage and not DiTEngine._sage_warned:          # said once per process
             DiTEngine._sage_warned = True
             import warnings
             warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored " +
                           "under sequence parallelism with the OVERLAPPED K|V all-gather (FLEXAM_SP_OVERLAP=1 / head-group pieces) or an all-to-all "
                           "over a padded sequence: self-attention runs the bf16 kernel", RuntimeWarning, stacklevel=3)
-        # CFG pair on one latent (PIPE.py:846-848 feeds `torch.cat([latents] * 2)`): until the first cross-attention the two samples
-        # are the same tensor -- same tokens, same timestep rows, same density -- so block 0 runs LayerNorm, q|k|v, RoPE, self-
-        # attention and the output projection ONCE and the second sample's residual stream is a copy (half of 1/30 of the
-        # attention and projection work of a step; every later operation sees the text and runs per sample)
-        share0 = (self.fused and B == 2 and bx == 1 and sp == 1 and rows_shared and cd.get("dens_same", False) and teacache is None
-                  and env.get("FLEXAM_SHARE_BLOCK0", "1") != "0")
-        per_layer = (not self.fused) or self.nl * R * 6 * self.dim * 4 > self.table_limit
-        lc = Lp // sp
-        return _Mode(B=B, Lp=Lp, lc=lc, tok0=self.sp_rank * lc, R=R, rows_per_batch=rows_per_batch, only_row=only_row,
-                     per_layer=per_layer, share0=bool(share0), sage=bool(sage), sage_gather=bool(sage_gather),
-                     sage_fused=bool(sage) and self.nh == 24 and self.hd == hip.ATTN_HEAD_DIM,
-                     fp8=self.fp8, fp8_oproj=self.fp8 and env.get("FLEXAM_FP8_OPROJ", "0") == "1",
-                     ffn_apriori=env.get("FLEXAM_FP8_FFN_APRIORI", "1") != "0",
-                     sp=sp, rank=self.sp_rank, sp_mode=sp_mode, sp_pieces=pieces, sp_overlap_level=overlap,
-                     sp_fused_qkv=getattr(self, "sp_fused_qkv", True),
-                     use_plan=self.fused and teacache is None and not per_layer and env.get("FLEXAM_REPLAY", "1") != "0")
+        return m
 
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
             only_row: Optional[int] = None, teacache=None, cond_flag: bool = True, rows_shared: bool = False) -> torch.Tensor:
@@ -468,11 +435,12 @@ class DiTEngine:
             tabs["blk"] = torch.empty(1 if m.per_layer else self.nl, R, 6, d, device=dev, dtype=F32)
             tabs["head"] = torch.empty(1, R, 2, d, device=dev, dtype=F32)
         if not m.per_layer:
-            hip.mod_table(self.mod, e0, tabs["blk"], rows_per_batch, 0b010010, self.mdens, dens0c, 0xFF1FF0 if dens0 is not None else -1)
+            hip.mod_table(self.mod, e0, tabs["blk"], rows_per_batch, hip.MOD_BLOCK_SLOTS.scale_mask, self.mdens, dens0c,
+                          hip.MOD_BLOCK_SLOTS.dens_slots if dens0 is not None else -1)
         e2 = e.unsqueeze(1).expand(R, 2, d).contiguous()
         hd_dens = dens_emb.reshape(B, 1, d).contiguous() if dens_emb is not None else None
-        hip.mod_table(self.hmod, e2, tabs["head"], rows_per_batch, 0b10, self.hmdens if hd_dens is not None else None, hd_dens,
-                      0xF0 if hd_dens is not None else -1)
+        hip.mod_table(self.hmod, e2, tabs["head"], rows_per_batch, hip.MOD_HEAD_SLOTS.scale_mask, self.hmdens if hd_dens is not None else None, hd_dens,
+                      hip.MOD_HEAD_SLOTS.dens_slots if hd_dens is not None else -1)
         calc = self._teacache_decide(teacache, e0, row_index, B, L, cond_flag) if teacache is not None else True
         if row_index is not None:
             # the per-token row index of THIS rank's rows, copied (47 KB) into a buffer of the workspace: the blocks' launches then see ONE
@@ -540,12 +508,13 @@ class DiTEngine:
     # ------------------------------------------------------------------ stages of a forward (fused blocks)
     def _blocks(self, m, ws, e0, dens0):
         tab = ws["tabs", m.R, m.per_layer]["blk"]
+        ex = self._exchange(m, ws) if m.sp > 1 else None
         for i, p in enumerate(self.blocks):
             if m.per_layer:                                # one table, rebuilt per layer (bounded memory, see table_limit)
-                hip.mod_table(self.mod[i:i + 1], e0, tab, m.rows_per_batch, 0b010010, self.mdens[i:i + 1], dens0,
-                              0xFF1FF0 if dens0 is not None else -1)
+                hip.mod_table(self.mod[i:i + 1], e0, tab, m.rows_per_batch, hip.MOD_BLOCK_SLOTS.scale_mask, self.mdens[i:i + 1], dens0,
+                              hip.MOD_BLOCK_SLOTS.dens_slots if dens0 is not None else -1)
             T = tab[0 if m.per_layer else i]
-            self._self_attention(i, p, T, m, ws)
+            self._self_attention(i, p, T, m, ws, ex)
             self._cross_attention(i, p, m, ws)
             self._ffn(i, p, T, m, ws)
 
@@ -590,7 +559,7 @@ class DiTEngine:
         if bufs is not None:
             hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs)
 
-    def _self_attention(self, i, p, T, m, ws):
+    def _self_attention(self, i, p, T, m, ws, ex=None):
         """LN + modulate -> q|k|v -> self-attention in this forward's layout (one rank, all-to-all over heads or K|V all-gather) ->
         output projection + gated residual."""
         d = self.dim
@@ -602,7 +571,7 @@ class DiTEngine:
         if m.sp > 1 and m.sp_mode == "ulysses":
             # all tokens of H/sp heads per rank: q|k|v all-to-all -> attention -> all-to-all back; the o-projection reads the
             # returned blocks in place (flexam_amd/dist.py)
-            a_o, koff_o = self._ulysses_attention(a8sa, i, p, m, ws)
+            a_o, koff_o = ex.run(self, ws, a8sa, i, p, m)
             self._out_proj(i, p, "wo", "bo", a_o, ws, mb, False, a_koff=koff_o, **gate)
             return
         qkv, h = ws["qkv"], ws["h"]
@@ -614,10 +583,7 @@ class DiTEngine:
             #  gather starts ~15 us later, not ~80; sage_gather: the MXFP8 records travel, always one q|k|v launch)
             whole = m.sp_fused_qkv or m.sage
             self._proj(h, a8sa, i, p, "wqkv", "bqkv", slice(None) if whole else slice(d, None), qkv if whole else qkv[:, d:])
-            if m.sage:
-                self._allgather_attention_mx(p, m, ws)
-            else:
-                self._allgather_attention(a8sa, i, p, m, ws)
+            ex.run(self, ws, a8sa, i, p, m)
             self._out_proj(i, p, "wo", "bo", ws["ao"], ws, mb, False, **gate)
             return
         self._proj(h[:mb], a8sa, i, p, "wqkv", "bqkv", slice(None), qkv[:mb])
@@ -741,96 +707,14 @@ class DiTEngine:
         return calc
 
     # ------------------------------------------------------------------ sequence parallel
-    def _ulysses_attention(self, a8sa, layer, p, m, ws):
-        """h [B*lc, C] (LayerNorm output of this rank's tokens) -> q|k|v projection -> exchange -> attention -> exchange back ->
-        (A base view, per-K-block A offsets) of the attention output for the o-projection.  Head group j = heads j*H/sp .. goes
-        to rank j.
-        Send layout [B, sp, lc, 3*G] (G = H/sp * head_dim): written by the RMSNorm+RoPE launch itself (q, k normed + rotated, v
-        copied), block (b, j) goes to rank j.  Receive layout [B, sp, lc, 3*G] = [B, L, 3*G]: rank-major blocks ARE the token
-        order, so attention addresses it with plain strides.  Its output [B, L, G] is cut into the sp token chunks that go back;
-        rank j's block returns to [j, B, lc, G], which the o-projection reads as A[m, j*G + c] through its K-block offsets.
-        With several samples per rank (the CFG pair batched: pure N-way chunks) the samples are stages of the outbound exchange
-        (FLEXAM_SP_OVERLAP=1, default): sample b's q|k|v leave as soon as ITS projection and norm are done and travel under the
-        projection of sample b + 1; ONE attention call for the pair follows the last arrival (two calls of half the work units fill
-        256 CUs a quarter worse than one), then the outputs return.  FLEXAM_SP_OVERLAP=2 pipelines the attention too: sample b's
-        call runs while sample b + 1's blocks arrive and sample b - 1's output returns -- only the last return is not under compute;
-        it pays when a link is slower than the ~0.1 ms the two smaller attention calls cost (about 35 GB/s at 8 GPUs)."""
-        from .dist import all_to_all_blocks
-        sp, nh, hd, d, dev = m.sp, self.nh, self.hd, self.dim, self.device
-        B, lc, tok0, qkv, hbuf = m.B, m.lc, m.tok0, ws["qkv"], ws["h"]
-        hg = nh // sp
-        G = hg * hd
-        W = 3 * G
-        if "a2a_send" not in ws:
-            ws["a2a_send"] = torch.empty(B, sp, lc, W, device=dev, dtype=BF16)
-            ws["a2a_recv"] = torch.empty(B, sp, lc, W, device=dev, dtype=BF16)
-            ws["a2a_out"] = torch.empty(B, sp * lc, hg, hd, device=dev, dtype=BF16)
-            ws["a2a_recv2"] = torch.empty(sp, B, lc, G, device=dev, dtype=BF16)
-            ws["a2a_koff"] = torch.tensor([(kb * 64 // G) * (B * lc * G) + (kb * 64) % G for kb in range(d // 64)], dtype=I64, device=dev)
-        cd = self.cond
-        send, recv, out, recv2 = ws["a2a_send"], ws["a2a_recv"], ws["a2a_out"], ws["a2a_recv2"]
-        full = recv.view(B, sp * lc, 3, hg, hd)
-        chunks = out.view(B, sp, lc, G)
-        nk = cd["L"]                                   # keys: the real tokens (rows nk .. sp*lc - 1 are the reference's zero pads, FX.py:919-925)
-
-        def attend(b0, nb):
-            """Attention of samples b0 .. b0 + nb - 1 on this rank's heads over all tokens; SAGE_ATTENTION: the received bf16 q|k|v are
-            packed into MXFP8 operands first (flexam_attn_fp8_pack) and the quantised kernel runs (_mode only asks for it when nk = sp * lc)."""
-            q_, k_, v_ = full[b0:b0 + nb, :, 0], full[b0:b0 + nb, :nk, 1], full[b0:b0 + nb, :nk, 2]
-            if m.sage:
-                bufs = self._attn8_buffers(nb, sp * lc, hg)
-                hip.attn_fp8_pack(q_, k_, v_, bufs)
-                hip.attn_fwd_fp8(bufs, sp * lc, out=out[b0:b0 + nb])
-            else:
-                hip.attn_fwd(q_, k_, v_, out=out[b0:b0 + nb], prescaled=True)
-
-        def project_and_pack(rows, b0, nb):          # samples b0 .. b0 + nb - 1: rows of h -> q|k|v -> normed / rotated send blocks
-            a8 = a8sa and (a8sa[0][rows], a8sa[1][rows])
-            self._proj(hbuf[rows], a8, layer, p, "wqkv", "bqkv", slice(None), qkv[rows])
-            flat = send[b0:b0 + nb].view(-1)
-            hip.rmsnorm_rope_scatter(qkv[rows, 0:d], p["nq"], qkv[rows, d:2 * d], p["nk"], qkv[rows, 2 * d:], flat, flat[G:], flat[2 * G:],
-                                     ld_out=W, out_bs=sp * lc * W, col_block=G, block_stride=lc * W, eps=self.eps, rope_cos=cd["cos"],
-                                     rope_sin=cd["sin"], tokens_per_batch=lc, token_offset=tok0, head_dim=hd)
-
-        # the exchanges and their waits are host steps (hip.host_op): run here, and again at this place by every replay of a recorded
-        # launch plan; `st` carries the Work handles from the step that issues to the step that waits
-        st = {"there": [None] * B, "back": [None] * B}
-
-        if "a2a_lists" not in ws:                      # the per-peer block views, made once (a replayed step must not rebuild 32 views per block)
-            ws["a2a_lists"] = [([recv[b, i] for i in range(sp)], [send[b, j] for j in range(sp)],
-                                [recv2[j, b] for j in range(sp)], [chunks[b, i] for i in range(sp)]) for b in range(B)]
-        lists = ws["a2a_lists"]
-
-        def go_there(b, async_op):                     # packed = the same blocks as ONE tensor pair (a backend that copies can do it in one go)
-            st["there"][b] = all_to_all_blocks(lists[b][0], lists[b][1], self.sp_group, async_op=async_op, packed=(recv[b], send[b]))
-
-        def go_back(b, async_op):
-            st["back"][b] = all_to_all_blocks(lists[b][2], lists[b][3], self.sp_group, async_op=async_op, packed=(recv2[:, b], chunks[b]))
-
-        def wait(which, bs):
-            for b in bs:
-                if st[which][b] is not None:
-                    st[which][b].wait()
-        if B == 1 or m.sp_overlap_level == 0:
-            project_and_pack(slice(None), 0, B)
-            hip.host_op(lambda: [go_there(b, False) for b in range(B)])
-            attend(0, B)
-            hip.host_op(lambda: [go_back(b, False) for b in range(B)])
-            return recv2.view(sp * B * lc, G), ws["a2a_koff"]
-        for b in range(B):
-            project_and_pack(slice(b * lc, (b + 1) * lc), b, 1)
-            hip.host_op(lambda b=b: go_there(b, True))
-        if m.sp_overlap_level < 2:
-            hip.host_op(lambda: wait("there", range(B)))
-            attend(0, B)
-            hip.host_op(lambda: ([go_back(b, True) for b in range(B)], wait("back", range(B))))
-            return recv2.view(sp * B * lc, G), ws["a2a_koff"]
-        for b in range(B):
-            hip.host_op(lambda b=b: wait("there", [b]))
-            attend(b, 1)
-            hip.host_op(lambda b=b: go_back(b, True))
-        hip.host_op(lambda: wait("back", range(B)))
-        return recv2.view(sp * B * lc, G), ws["a2a_koff"]
+    def _exchange(self, m, ws):
+        """The exchange object of sequence-parallel self-attention in this forward's layout (flexam_amd/dit_sp.py): one per workspace and
+        layout, made by the first forward that needs it."""
+        cls = HeadAllToAll if m.sp_mode == "ulysses" else (RecordGather if m.sage else KVGather)      # (the all-to-all serves bf16 and SAGE)
+        ex = ws.get(("exchange", cls.__name__))
+        if ex is None:
+            ex = ws["exchange", cls.__name__] = cls(self, m, ws)
+        return ex
 
     def _proj(self, hbuf, a8sa, layer, p, wname, bname, rows, out):
         """out = h @ W[rows]^T + b[rows]: bf16 MFMA, or fp8 MFMA on the row-quantised h (`a8sa` = (bytes, row scales)) with the
@@ -839,95 +723,6 @@ class DiTEngine:
             w8 = self._fp8_w[layer]
             return hip.gemm_fp8(a8sa[0], a8sa[1], w8[wname][rows], w8["s_" + wname][rows], p[bname][rows], out=out)
         return hip.gemm(hbuf, p[wname][rows], p[bname][rows], out=out)
-
-    def _allgather_attention(self, a8sa, layer, p, m, ws):
-        """K|V of this rank's tokens are in qkv[:, C:] (projected, not yet normed).  The RMSNorm+RoPE launch writes K (normed,
-        rotated) and V into the send buffer, cut into `sp_pieces` groups of heads: [G, B, lc, 2*C/G].  One all-gather per group
-        and CFG row assembles [G, B, L, 2*C/G] in token order (the rank-major concatenation IS the token order: no re-layout
-        pass), all of them issued at once.  DEFAULT (r6: FLEXAM_SP_OVERLAP=0, one piece): the gather is waited for and ONE ordinary
-        attention call of the local queries over all L real keys follows -- the fastest form on compute.  FLEXAM_SP_OVERLAP=1
-        (r2-r5's default, a layout-probe candidate): underneath the gather: Q projection, Q norm/RoPE, then the heads of group 0 attend to the LOCAL
-        chunk (partial softmax, straight from the send buffer), to the chunks before / after it once piece 0 has landed, one
-        merge; the heads of group g > 0 run one ordinary attention call on their gathered piece, which travelled while group
-        g - 1 computed.  A peer chunk cannot arrive faster than its one xGMI link delivers it, and the chunks of one gather all
-        land together; cutting along the heads gives pieces that are complete work for part of the kernel, so all links stay
-        busy in every phase (reference call sites of the missing exchange: wan_transformer3d_FlexAM.py:801-815, 970-975)."""
-        from .dist import all_gather_into_tensor, group_backend
-        sp, nh, hd, d, dev = m.sp, self.nh, self.hd, self.dim, self.device
-        B, lc, tok0, qkv = m.B, m.lc, m.tok0, ws["qkv"]
-        q4, _, _, ao4 = self._heads(m, ws)
-        L = sp * lc                                    # rows of the gathered buffer (the padded sequence)
-        Lr = self.cond["L"]                            # keys: the real tokens; rows Lr .. L - 1 are zero pads (FX.py:919-925) and end every key range
-        n_loc = max(0, min(lc, Lr - tok0))             # real tokens of the local chunk
-        G = m.sp_pieces
-        cb, hg = d // G, nh // G
-        if "kv_send" not in ws:
-            ws["kv_send"] = torch.empty(G, B, lc, 2 * cb, device=dev, dtype=BF16)
-            ws["kv_cat"] = torch.empty(G, B, L, 2 * cb, device=dev, dtype=BF16)
-            units = hip.attn_units(B * hg, lc)
-            ranges = [n_loc, min(tok0, Lr), max(0, Lr - tok0 - lc)]                      # local, before, after
-            # no CU count passed: these ranges are planned for the planner's default of 256 CUs, whatever FLEXAM_CU_BUDGET says
-            ws["kv_splits"] = [hip.attn_partial_splits(units, hip.attn_kv_tiles(n)) if n else 0 for n in ranges]
-            ws["kv_part"] = hip.attn_partial_workspace(B, hg, lc, sum(hip.attn_effective_splits(n, s) for n, s in zip(ranges, ws["kv_splits"]) if n), dev)
-        cd = self.cond
-        send, cat = ws["kv_send"], ws["kv_cat"]
-        flat = send.view(-1)
-        hip.rmsnorm_rope_scatter(None, None, qkv[:, d:2 * d], p["nk"], qkv[:, 2 * d:], None, flat, flat[cb:], ld_out=2 * cb, out_bs=lc * 2 * cb,
-                                 col_block=cb, block_stride=B * lc * 2 * cb, eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"],
-                                 tokens_per_batch=lc, token_offset=tok0, head_dim=hd)
-        # RCCL runs the pieces one after the other on its own stream, in the order they are issued here.  The host-staged backends of the
-        # test runs (gloo) execute several in-flight collectives of one group on concurrent worker threads, which is not what is being
-        # modelled (and delivered wrong chunks intermittently with 8 ranks on one device): there each gather completes before the next.
-        overlapped = group_backend(self.sp_group) in ("nccl", "loopback")
-        # collectives and waits are host steps (hip.host_op): run here, and again at this place by every replay of a recorded launch plan
-        st = {}
-
-        def issue():
-            st["works"] = [[all_gather_into_tensor(cat[g, b], send[g, b], group=self.sp_group, async_op=overlapped) for b in range(B)] for g in range(G)]
-
-        def wait(g):
-            for w in st["works"][g]:
-                if w is not None:
-                    w.wait()
-        hip.host_op(issue)
-        if not m.sp_fused_qkv:
-            self._proj(ws["h"], a8sa, layer, p, "wqkv", "bqkv", slice(0, d), qkv[:, 0:d])
-        hip.rmsnorm_rope(qkv[:, 0:d], p["nq"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=lc, token_offset=tok0,
-                         head_dim=hd)
-        heads = lambda t: t.unflatten(2, (hg, hd))
-        for g in range(G):
-            qg, og = q4[:, :, g * hg:(g + 1) * hg], ao4[:, :, g * hg:(g + 1) * hg]
-            kc, vc = cat[g, :, :, 0:cb], cat[g, :, :, cb:]
-            if g > 0 or m.sp_overlap_level == 0:
-                hip.host_op(lambda g=g: wait(g))
-                hip.attn_fwd(qg, heads(kc[:, :Lr]), heads(vc[:, :Lr]), out=og, prescaled=True)
-                continue
-            s_loc, s_before, s_after = ws["kv_splits"]
-            n = 0
-            if n_loc > 0:
-                n = hip.attn_fwd_partial(qg, heads(send[0, :, :n_loc, 0:cb]), heads(send[0, :, :n_loc, cb:]), ws["kv_part"], 0, s_loc, prescaled=True)
-            hip.host_op(lambda: wait(0))
-            if tok0 > 0:
-                n += hip.attn_fwd_partial(qg, heads(kc[:, :min(tok0, Lr)]), heads(vc[:, :min(tok0, Lr)]), ws["kv_part"], n, s_before, prescaled=True)
-            if tok0 + lc < Lr:
-                n += hip.attn_fwd_partial(qg, heads(kc[:, tok0 + lc:Lr]), heads(vc[:, tok0 + lc:Lr]), ws["kv_part"], n, s_after, prescaled=True)
-            hip.attn_merge(og, ws["kv_part"], n, prescaled=True)
-
-    def _allgather_attention_mx(self, p, m, ws):
-        """SAGE_ATTENTION under the K|V all-gather (r6; the reference's `sageattn` switch, attention_utils.py:195-203, with the exchange of
-        the missing FlexAM/dist, wan_transformer3d_FlexAM.py:801-815): this rank's q, k (RMSNorm + RoPE at the chunk's global offset) and
-        v become MXFP8 operands (_norm_rope_qk), ONE all-gather moves the key / value RECORDS ([B, H, lc / 64] x 18 KiB per rank:
-        288 bytes per key and head instead of 512 in bf16; the rank-major result is the chunk layout flexam_attn_fwd_fp8_chunked reads),
-        and one attention call of the local queries over all L real keys follows.  lc is a multiple of 64 (_mode pads to 64 x ranks)."""
-        from .dist import all_gather_into_tensor
-        sp, B, lc = m.sp, m.B, m.lc
-        bufs = self._attn8_buffers(B, lc)
-        if "kv8_all" not in ws:
-            ws["kv8_all"] = torch.empty(sp, *bufs[2].shape, device=self.device, dtype=torch.uint8)
-        kv8_all = ws["kv8_all"]
-        self._norm_rope_qk(p, m, ws, B, bufs)
-        hip.host_op(lambda: all_gather_into_tensor(kv8_all.view(sp * B, *bufs[2].shape[1:]), bufs[2], group=self.sp_group))
-        hip.attn_fwd_fp8_chunked(bufs[0], bufs[1], kv8_all, lc, self.cond["L"], out=self._heads(m, ws)[3])
 
     def gather_tokens(self, head_local: torch.Tensor) -> torch.Tensor:
         """All-gather of the head output [B, Lc, 192] -> [B, L, 192] (the reference's one collective,

@@ -7,6 +7,7 @@ GPU, the call fails loudly (a silent CPU/eager path would void every parity clai
 """
 import ctypes
 import os
+from collections import namedtuple
 from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 import torch
@@ -723,6 +724,14 @@ def rmsnorm_rope_scatter(q, wq, k, wk, v, q_out, k_out, v_out, ld_out, out_bs, c
           _ptr(wk, F32), _ptr(v, BF16), v.stride(0) if v is not None else 0, _ptr(q_out, BF16), _ptr(k_out, BF16), _ptr(v_out, BF16),
           ld_out, out_bs, col_block, block_stride, M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset,
           head_dim)
+
+
+# (scale_mask, dens_slots) of the model's two AdaLN tables: a block's six slots (shift, scale, gate of the attention and the FFN half:
+# bit j of scale_mask set = slot j is a scale and gets + 1; nibble j of dens_slots = the density slot added to slot j, 0xF = none) and the
+# head's two (shift, scale)
+ModSlots = namedtuple("ModSlots", "scale_mask dens_slots")
+MOD_BLOCK_SLOTS = ModSlots(0b010010, 0xFF1FF0)
+MOD_HEAD_SLOTS = ModSlots(0b10, 0xF0)
 
 
 def mod_table(mod, e, out, rows_per_batch, scale_mask, mdens=None, dens=None, dens_slots=-1):

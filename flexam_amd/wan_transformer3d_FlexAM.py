@@ -19,7 +19,7 @@ import torch.nn as nn
 
 from .cache_utils import TeaCache
 from .cfg_optimization import cfg_skip
-from .dit_engine import DiTEngine
+from .dit_engine import DiTEngine, _fp8_weight, _proj_fp8
 from .implicit_conv import pad_k
 from .rope import rope_angle_table
 
@@ -105,25 +105,6 @@ class HipLinear(nn.Linear):
 
 def _holder(n_out: int, n_in: int) -> nn.Linear:
     return HipLinear(n_in, n_out)
-
-
-def _fp8_weight(pk: dict, name: str):
-    """(e4m3 bytes, per-output-channel scales) of pack entry `name`, quantised once per pack (the pack is rebuilt when a parameter changes)."""
-    from . import hip
-    key = "_f8_" + name
-    if key not in pk:
-        w = pk[name]
-        pk[key] = hip.quantize_rows_fp8(w.to(BF16) if w.dtype == F8 else w)     # (qfloat8 storage: one matrix upcast at a time)
-    return pk[key]
-
-
-def _proj_fp8(h: torch.Tensor, pk: dict, wname: str, bias, epilogue: int = 0) -> torch.Tensor:
-    """h [M, K] bf16 -> bf16 [M, N] on the fp8 (OCP e4m3) MFMA path: rows of h quantised per call (absmax / 448), weights per output channel,
-    fp32 accumulation, scales / bias / activation in the epilogue (csrc/gemm_fp8.hip) -- the module-seam form of DiTEngine.enable_fp8."""
-    from . import hip
-    a8, sa = hip.quantize_rows_fp8(h)
-    w8, sw = _fp8_weight(pk, wname)
-    return hip.gemm_fp8(a8, sa, w8, sw, bias, epilogue=epilogue)
 
 
 class _Norm(nn.Module):
@@ -246,7 +227,7 @@ class _SelfAttn(_Attn):
         wan_transformer3d_FlexAM.py:807-815): x is this rank's token chunk [B, L/N, C]; q|k|v of the chunk, RMSNorm + RoPE at the
         chunk's GLOBAL token offset, ONE all-gather of the normed / rotated K|V over the sequence-parallel group (RCCL over xGMI; the
         rank-major concatenation is the token order), attention of the local queries to all keys, output projection.  The engine's
-        fused path does the same exchange in head-group pieces overlapped with compute (DiTEngine._allgather_attention); this seam
+        fused path does the same exchange in head-group pieces overlapped with compute (flexam_amd.dit_sp.KVGather); this seam
         form favours being one plain forward a wrapper can trace."""
         from . import hip
         from .dist import all_gather_seq
@@ -383,8 +364,8 @@ class _Block(nn.Module):
         xres = x.reshape(b * l, c).to(F32).clone()
         rows, idx, rpb = adaln_rows(e, b, l)
         tab = torch.empty(1, rows.shape[0], 6, c, device=x.device, dtype=F32)
-        hip.mod_table(pk["mod"].unsqueeze(0), rows, tab, rpb, 0b010010, pk["mdens"].unsqueeze(0),
-                      density_emb.to(F32).contiguous(), 0xFF1FF0)
+        hip.mod_table(pk["mod"].unsqueeze(0), rows, tab, rpb, hip.MOD_BLOCK_SLOTS.scale_mask, pk["mdens"].unsqueeze(0),
+                      density_emb.to(F32).contiguous(), hip.MOD_BLOCK_SLOTS.dens_slots)
         T = tab[0]
         hbuf = hip.ln_modulate(xres, eps=self.eps, shift=T[:, 0], scale=T[:, 1], row_index=idx, rows_per_batch=l)
         y = self.self_attn(hbuf.view(b, l, c), seq_lens, grid_sizes, freqs, dtype, t=t)
@@ -427,8 +408,8 @@ class _Head(nn.Module):
         else:                                                  # e feeds both slots (shift, scale) of the head's modulation
             rows, idx, rpb = adaln_rows(e.unsqueeze(-2).expand(*e.shape[:-1], 2, c), b, l)
         tab = torch.empty(1, rows.shape[0], 2, c, device=dev, dtype=F32)
-        hip.mod_table(_on(self.modulation, dev, F32), rows, tab, rpb, 0b10, _on(self.modulation_density, dev, F32),
-                      density_emb.to(F32).reshape(b, 1, c).contiguous(), 0xF0)
+        hip.mod_table(_on(self.modulation, dev, F32), rows, tab, rpb, hip.MOD_HEAD_SLOTS.scale_mask, _on(self.modulation_density, dev, F32),
+                      density_emb.to(F32).reshape(b, 1, c).contiguous(), hip.MOD_HEAD_SLOTS.dens_slots)
         H = tab[0]
         hbuf = hip.ln_modulate(x.reshape(b * l, c).to(F32).contiguous(), eps=self.eps, shift=H[:, 0], scale=H[:, 1], row_index=idx,
                                rows_per_batch=l)

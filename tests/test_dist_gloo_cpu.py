@@ -292,7 +292,7 @@ def test_default_layout_follows_the_exchange_mode():
 
 
 def _head_group_pieces(rank, world):
-    """The K|V gather cut into G head-group pieces (DiTEngine._allgather_attention): send layout [G, B, lc, 2*C/G] (K of the
+    """The K|V gather cut into G head-group pieces (flexam_amd.dit_sp.KVGather): send layout [G, B, lc, 2*C/G] (K of the
     group's heads | V of the group's heads), one all-gather per (piece, CFG row) whose rank-major concatenation is the token
     order.  Group g's attention needs ONLY piece g -- whatever the other pieces' buffers hold (here: NaN until their own gather
     is consumed, in reverse order of issue) -- and the groups together equal attention over all heads; within a piece the

@@ -1,7 +1,7 @@
 """GPU (one device is enough): RCCL's stream semantics against kernels this library launches through RAW stream handles.
 
 The multi-rank engine enqueues its kernels with ctypes on `torch.cuda.current_stream().cuda_stream` and lets `torch.distributed`
-run the K|V all-gathers asynchronously on RCCL's own stream (DiTEngine._allgather_attention).  What keeps that correct is c10d's
+run the K|V all-gathers asynchronously on RCCL's own stream (flexam_amd.dit_sp.KVGather).  What keeps that correct is c10d's
 contract: the collective's stream waits for the work already enqueued on the current stream when it is issued, `Work.wait()`
 makes the current stream wait for the collective, and nothing else orders the two.  Two ranks cannot share a device under RCCL,
 so this runs the REAL backend with a ONE-rank group (`device_id=` initialisation, `all_gather_into_tensor(async_op=True)`,
