@@ -21,14 +21,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mxfp8_restatement as R  # noqa: E402
+from gemm_checks import _bf16_ulp, _gelu64, _margins_untouched, _strided, dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
 GA, GB = -2.302208198, -0.1029432396          # gelu_tanh's exp2 exponent t = y (GA + GB y^2)
-
-
-def dev():
-    return torch.device("cuda:0")
 
 
 @pytest.fixture(scope="module")
@@ -40,27 +37,6 @@ def H():
 
 def _e4m3_bytes(x_int):
     return x_int.float().to(torch.float8_e4m3fn).view(torch.uint8)
-
-
-def _strided(rows, cols, ld, dtype, sentinel, r0=1, c0=16):
-    """(buffer, view [rows, cols] at (r0, c0)) with the rest of the buffer holding `sentinel`."""
-    buf = torch.full((rows + 2 * r0, ld), sentinel, dtype=dtype, device=dev())
-    return buf, buf[r0:r0 + rows, c0:c0 + cols]
-
-
-def _margins_untouched(buf, view_rows, view_cols, sentinel, r0=1, c0=16):
-    keep = torch.ones(buf.shape, dtype=torch.bool, device=buf.device)
-    keep[r0:r0 + view_rows, c0:c0 + view_cols] = False
-    return bool((buf[keep] == sentinel).all())
-
-
-def _gelu64(y):
-    """0.5 y (1 + tanh(u)) written as y / (1 + exp(-2u)): no cancellation for negative y (1 + tanh(u) is 0 in float64 below y = -7)."""
-    return y / (1.0 + torch.exp(-1.5957691216057308 * (y + 0.044715 * y ** 3)))
-
-
-def _bf16_ulp(x):
-    return torch.pow(2.0, torch.floor(torch.log2(x.abs().clamp_min(2.0 ** -126))) - 7)
 
 
 def _case(m, n, k, seed):
