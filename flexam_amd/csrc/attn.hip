@@ -159,15 +159,6 @@ __device__ __forceinline__ float pair_sum(float x) {
 // (A 4-wave x 64-row variant -- each K/V fragment feeding two MFMAs -- was tried in r1: hipcc cannot keep
 //  Q in the accumulator file and spills 150+ VGPRs; see DESIGN.md.)
 // ------------------------------------------------------------------------------------------------
-#ifndef A32_DEFER
-#define A32_DEFER 0      // scores of a half tile whose exp2 / sum / pack wait for part A of the next step (see stepA); 0 = none
-#endif
-// (ATTN_STAMP_*, A32_DEFER and body16 in attn_run are inert; they are part of the text the counter record in
-// profiles/head_attn_traffic.json was hashed from and go with the next change to this kernel)
-#define ATTN_STAMP_DECL()
-#define ATTN_STAMP_BEGIN()
-#define ATTN_STAMP_BARRIER(stmt) stmt
-#define ATTN_STAMP_END()
 constexpr int NT = 512;
 constexpr int NSLOT = 4;
 constexpr int V_RING = NSLOT * KV_TILE_BYTES;   // LDS: [4 K slots][4 V slots]
@@ -179,6 +170,75 @@ using IC = std::integral_constant<int, V>;
 // +1.2 % of a denoise step at 2^4 and -0.5 / -0.9 / -1.3 ... -2.1 % at 2^12 / 2^16 / 2^24 on such rows (nothing on N(0, 1) logits).
 // 8 stays: parity before speed.
 constexpr float RESCALE_THR_LOG2 = 8.0f;
+
+// workgroups bid = 8 * local + xcd go to XCD `xcd` in the order of `local`: an XCD walks a contiguous eighth of the work list
+__device__ __forceinline__ int eighth(int n, int xcd, int local) {      // index into a list of n items, -1 past this XCD's share
+  const int q = n >> 3, rr = n & 7;
+  if (local >= q + (xcd < rr ? 1 : 0)) return -1;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + local;
+}
+// The work unit of this workgroup (not SHORT: a walk of its own): a whole unit -- all keys, writes O -- or key range `split` of unit `ul` of the
+// launch's split part.  The caller presets split = 0, tps = p.tiles_per_split and partial = p.partial; false = this workgroup has no work.
+__device__ __forceinline__ bool unit_of_workgroup(const AttnParams& p, int& split, int& ul, int& unit, int& tps, int& partial) {
+  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
+  const int wmax = (p.whole_units + 7) >> 3;
+  if (local < wmax) {                              // (whole_units = 0: wmax = 0)
+    unit = eighth(p.whole_units, xcd, local);
+    if (unit < 0) return false;
+    ul = unit;
+    tps = (p.Lk + KVBLK - 1) / KVBLK;
+    partial = 0;
+  } else {
+    // consecutive workgroups: the units of one split, i.e. q blocks of one head first -> same K/V range in L2
+    const int j = eighth(p.n_units * p.kv_splits, xcd, local - wmax);
+    if (j < 0) return false;
+    split = j / p.n_units;
+    ul = j - split * p.n_units;                    // unit index inside the launch's split (or only) part
+    unit = p.unit0 + ul;
+  }
+  return true;
+}
+// ---- epilogue of both kernels: O[q][32dt + 8i + 4h + (0..3)] = o_acc[dt][4i + (0..3)] / l, lane (r, h) of `wave` holding row qi.  Partial result
+// of one key range: un-normalised O (SCALE: times osc) and (reference, row sum) to the workspace; attn_merge_kernel finishes the softmax.
+template <bool SCALE>
+__device__ __forceinline__ void store_partial(const AttnParams& p, const f32x16 (&o_acc)[4], float osc, float ref, float l_tot, int split,
+                                              int ul, int wave, int r, int h, int qi) {
+  if (qi >= p.Lq) return;
+  const int64_t row = ((int64_t)(p.slot0 + split) * p.n_units + ul) * QBLK + wave * 32 + r;
+  float* orow = p.ws_o + row * HD;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      f32x4 ov;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) ov[e] = SCALE ? o_acc[dt][4 * i + e] * osc : o_acc[dt][4 * i + e];
+      *(f32x4*)(orow + 32 * dt + 8 * i + 4 * h) = ov;
+    }
+  if (h == 0) *(f32x2*)(p.ws_ml + row * 2) = (f32x2){ref, l_tot};
+}
+// A lane holds 4 of the 8 columns of each 8-column group of its row, its partner (lane ^ 32) the other 4.  One half exchange
+// per dword between the groups of a pair (lower lanes give their part of the odd group, upper lanes their part of the even
+// one) leaves 16 contiguous bytes in every lane: 8 stores of 16 B instead of 16 of 8 B (the tail is store-issue bound).
+__device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (&o_acc)[4], float inv_l, int b, int head, int qi, int h) {
+  bf16* orow = p.o + (int64_t)b * p.o_bs + (int64_t)min(qi, p.Lq - 1) * p.o_rs + head * HD + 8 * h;
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+    for (int i = 0; i < 4; i += 2) {
+      bf16x4 even, odd;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        even[e] = f2bf(o_acc[dt][4 * i + e] * inv_l);
+        odd[e] = f2bf(o_acc[dt][4 * i + 4 + e] * inv_l);
+      }
+      const u32x2 ev = __builtin_bit_cast(u32x2, even), od = __builtin_bit_cast(u32x2, odd);
+      unsigned a0 = ev[0], a1 = ev[1], c0 = od[0], c1 = od[1];
+      half_swap_u32(a0, c0);
+      half_swap_u32(a1, c1);
+      if (qi < p.Lq) *(u32x4*)(orow + 32 * dt + 8 * i) = (u32x4){a0, a1, c0, c1};
+    }
+}
 
 // KIND: 0 = self-attention, 1 = short-context (text) attention: distinct profiler symbols.
 // PRE: q was multiplied by softmax_scale * log2(e) by its producer, BEFORE its one rounding to bf16 (in the DiT: folded into the
@@ -198,7 +258,6 @@ constexpr float RESCALE_THR_LOG2 = 8.0f;
 template <int KIND, bool PRE, bool FULL = false, bool SHORT = false>
 __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [4 K tiles][4 V tiles], each a ring
-  ATTN_STAMP_DECL();
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -208,12 +267,6 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   //  balances the halves -- priority in one part of the step only, turns by step or by tile -- is slower: while the leader waits its
   //  partner has the SIMD to itself.  profiles/r4u_attn_wave_priority_modes_and_barrier_wait.txt)
 
-  // workgroups bid = 8 * local + xcd go to XCD `xcd` in the order of `local`: an XCD walks a contiguous eighth of the work list
-  auto eighth = [](int n, int xcd, int local) -> int {      // index into a list of n items, -1 past this XCD's share
-    const int q = n >> 3, rr = n & 7;
-    if (local >= q + (xcd < rr ? 1 : 0)) return -1;
-    return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + local;
-  };
   int split = 0, ul, unit, tps = p.tiles_per_split, partial = p.partial;
   int unit_end;                              // SHORT: this workgroup walks units [unit, unit_end)
   if constexpr (SHORT) {
@@ -221,23 +274,8 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     ul = unit = (int)(all * blockIdx.x / gridDim.x);
     unit_end = (int)(all * (blockIdx.x + 1) / gridDim.x);
     if (unit >= unit_end) return;
-  } else {
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int wmax = (p.whole_units + 7) >> 3;
-    if (local < wmax) {                              // (whole_units = 0: wmax = 0)
-      unit = eighth(p.whole_units, xcd, local);
-      if (unit < 0) return;
-      ul = unit;
-      tps = (p.Lk + KVBLK - 1) / KVBLK;
-      partial = 0;
-    } else {
-      // consecutive workgroups: the units of one split, i.e. q blocks of one head first -> same K/V range in L2
-      const int j = eighth(p.n_units * p.kv_splits, xcd, local - wmax);
-      if (j < 0) return;
-      split = j / p.n_units;
-      ul = j - split * p.n_units;                    // unit index inside the launch's split (or only) part
-      unit = p.unit0 + ul;
-    }
+  } else if (!unit_of_workgroup(p, split, ul, unit, tps, partial)) {
+    return;
   }
   if constexpr (!SHORT) unit_end = unit + 1;
   // (batch, head) of the unit being worked on: set at the top of every unit of the walk below
@@ -469,33 +507,12 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   // A half-tile step g in two parts.  Part A: first half of S(g+1) on the matrix pipe (fragments read during the previous step) |
   // row maximum of S(g) on the VALU, and the (rare) deferred rescale.  Part B: second half of S(g+1) and PV(g-1) on the matrix pipe |
   // exp2 / row sum / pack of S(g) on the VALU.
-  // DEF scores of every half are exponentiated one part later -- in part A of the NEXT step, whose 4 MFMAs otherwise run beside a
-  // dependent chain of 9 maxima only -- instead of in part B beside 12 MFMAs, 16 exp2, 16 adds and 8 packs: P(g) is not needed
-  // before PV(g) in part B of step g+1.  They wait in s_pend in the units of the reference of their own step; finish_pending runs
-  // BEFORE the next step's rescale decision, so a rescale finds them where it expects them: in l_run and in the packed pf_prev.
-  // With a key-mask branch in every step (r4g) 4 of 16 paid (-0.6 ... -0.9 % of a step); since the step is one basic block (FULL) none
-  // is best: 0 / 1 / 2 / 4 / 6 / 8 deferred = -0.3 ... -0.8 / +0.3 / -0.4 / 0 / +0.7 / +0.5 % (profiles/r4ab_*).  Default 0.
-  constexpr int DEF = PRE ? A32_DEFER : 0;
-  float s_pend[DEF > 0 ? DEF : 1];
-#pragma unroll
-  for (int i = 0; i < (DEF > 0 ? DEF : 1); ++i) s_pend[i] = -INFINITY;
-  auto finish_pending = [&]() __attribute__((always_inline)) {
-    if constexpr (DEF > 0) {
-      float ps = 0.f;
-#pragma unroll
-      for (int i = 0; i < DEF; ++i) {
-        const float pv = __builtin_amdgcn_exp2f(s_pend[i]);
-        ps = i == 0 ? pv : ps + pv;
-        pf_prev[1][8 - DEF + i] = f2bf(pv);
-      }
-      l_run += ps;
-    }
-  };
+  // (Tried and not kept: 1..8 scores of every half exponentiated one part later, in part A of the next step.  It paid with a key-mask
+  // branch in every step, profiles/r4g_*; with the one-block step none deferred is best, profiles/r4ab_*.)
   auto stepA = [&](int g, f32x16& s_cur, f32x16& s_nxt, auto mask_c) __attribute__((always_inline)) {
     if constexpr (FULL && decltype(mask_c)::value) mask_shift(g, s_cur);
     mask_half(g, s_cur);             // keys past Lk -> -inf (uniform branch, only taken in the last tile)
     qk_mma(IC<0>{}, kf_pre, s_nxt);
-    finish_pending();
     const float m0 = vmax8(s_cur[0], s_cur[1], s_cur[2], s_cur[3], s_cur[4], s_cur[5], s_cur[6], s_cur[7]);
     const float m1 = vmax8(s_cur[8], s_cur[9], s_cur[10], s_cur[11], s_cur[12], s_cur[13], s_cur[14], s_cur[15]);
     // the test needs no row maximum: any(lane maximum > THR) over the wave is any(row maximum > THR); the exchange between the
@@ -554,17 +571,14 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     qk_read(IC<((g8 + 2) & 7)>{}, IC<0>{}, kf_pre);          // for the next step's part A
     const float mc = PRE ? 0.f : m_run * c;
 #pragma unroll
-    for (int e = 0; e < 16 - DEF; ++e) {
+    for (int e = 0; e < 16; ++e) {
       const float pv = PRE ? __builtin_amdgcn_exp2f(s_cur[e]) : __builtin_amdgcn_exp2f(__builtin_fmaf(s_cur[e], c, -mc));
       psum = e == 0 ? pv : psum + pv;                       // (0 + x is an instruction: x may be -0 as far as the compiler knows)
       pn[e >> 3][e & 7] = f2bf(pv);
     }
-#pragma unroll
-    for (int i = 0; i < DEF; ++i) s_pend[i] = s_cur[16 - DEF + i];
     l_run += psum;
     pf_prev[0] = pn[0];            // PV(g-1) above consumed the old value (program order)
-#pragma unroll
-    for (int e = 0; e < 8 - DEF; ++e) pf_prev[1][e] = pn[1][e];      // the other DEF elements: finish_pending
+    pf_prev[1] = pn[1];
     // pin the softmax results here: hipcc otherwise sinks the whole exp chain below the next step's branch
     asm volatile("" : "+v"(pf_prev[0]), "+v"(pf_prev[1]), "+v"(l_run));
     // Block B schedule: hipcc otherwise emits the 12 MFMAs first and the exp chain after them, leaving the matrix
@@ -574,7 +588,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     for (int i = 0; i < 12; ++i) {
       __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS read
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-      __builtin_amdgcn_sched_group_barrier(0x002, PRE ? (DEF >= 4 ? 3 : 4) : 5, 0);   // VALU (exp2 / fma / add / cvt)
+      __builtin_amdgcn_sched_group_barrier(0x002, PRE ? 4 : 5, 0);   // VALU (exp2 / fma / add / cvt)
     }
   };
 
@@ -590,7 +604,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
         // tt-2 (last read by the PV of its second half) is free again
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-        ATTN_STAMP_BARRIER(__builtin_amdgcn_s_barrier());
+        __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
       }
       // K pieces of tile tt+2 now, its V pieces half a tile later: two short bursts of LDS-DMA issue per tile instead
@@ -609,7 +623,6 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     stepA(2 * t + 1, s_b, s_a, mask_c);
     stepB(IC<2 * t4 + 1>{}, s_b, s_a);
   };
-  ATTN_STAMP_BEGIN();
   using MaskOn = std::integral_constant<bool, true>;
   using MaskOff = std::integral_constant<bool, false>;
   int t = 0;
@@ -626,57 +639,20 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   if (rem > 2) tile(t + 2, IC<2>{}, MaskOn{});
   if (rem > 3) tile(t + 3, IC<3>{}, MaskOn{});
   // pending PV of the last half (2*ntiles - 1): its slot is (ntiles - 1) & 3
-  finish_pending();
   switch ((ntiles - 1) & 3) {
     case 0: pv_half(IC<1>{}); break;
     case 1: pv_half(IC<3>{}); break;
     case 2: pv_half(IC<5>{}); break;
     default: pv_half(IC<7>{}); break;
   }
-  ATTN_STAMP_END();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  // ---- epilogue: O[q][32dt + 8i + 4h + (0..3)] = o_acc[dt][4i + (0..3)] / l
   const float l_tot = pair_sum(l_run);
-  const int qi = q0 + r;
-  if (partial) {                           // partial result of this key range; attn_merge_kernel finishes the softmax
-    if (qi < p.Lq) {
-      const int64_t row = ((int64_t)(p.slot0 + split) * p.n_units + ul) * QBLK + wave * 32 + r;
-      float* orow = p.ws_o + row * HD;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          f32x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = o_acc[dt][4 * i + e];
-          *(f32x4*)(orow + 32 * dt + 8 * i + 4 * h) = ov;
-        }
-      if (h == 0) *(f32x2*)(p.ws_ml + row * 2) = (f32x2){PRE ? ref : m_run, l_tot};      // PRE: reference in exp2 units
-    }
+  if (partial) {
+    store_partial<false>(p, o_acc, 1.0f, PRE ? ref : m_run, l_tot, split, ul, wave, r, h, q0 + r);      // PRE: reference in exp2 units
     return;
   }
-  // A lane holds 4 of the 8 columns of each 8-column group of its row, its partner (lane ^ 32) the other 4.  One half exchange
-  // per dword between the groups of a pair (lower lanes give their part of the odd group, upper lanes their part of the even
-  // one) leaves 16 contiguous bytes in every lane: 8 stores of 16 B instead of 16 of 8 B (the tail is store-issue bound).
-  const float inv_l = 1.0f / l_tot;
-  bf16* orow = p.o + (int64_t)b * p.o_bs + (int64_t)min(qi, p.Lq - 1) * p.o_rs + head * HD + 8 * h;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int i = 0; i < 4; i += 2) {
-      bf16x4 even, odd;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        even[e] = f2bf(o_acc[dt][4 * i + e] * inv_l);
-        odd[e] = f2bf(o_acc[dt][4 * i + 4 + e] * inv_l);
-      }
-      const u32x2 ev = __builtin_bit_cast(u32x2, even), od = __builtin_bit_cast(u32x2, odd);
-      unsigned a0 = ev[0], a1 = ev[1], c0 = od[0], c1 = od[1];
-      half_swap_u32(a0, c0);
-      half_swap_u32(a1, c1);
-      if (qi < p.Lq) *(u32x4*)(orow + 32 * dt + 8 * i) = (u32x4){a0, a1, c0, c1};
-    }
+  store_output(p, o_acc, 1.0f / l_tot, b, head, q0 + r, h);
   }   // q blocks of this workgroup
 }
 
@@ -713,97 +689,108 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(AttnParams p) {
   }
 }
 
-int attn_run(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v, int64_t v_bs,
-             int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int Lk, int head_dim, float softmax_scale,
-             int kv_splits, int split_from_unit, float* ws_o, float* ws_ml, void* stream, int partial_slot0 = -1, float last_key_bias = 0.f,
-             const void* q8 = nullptr, const void* qs = nullptr, const void* kv8 = nullptr, int kv8_chunk_tiles = 0) {
-  FX_REQUIRE(((q && k && v) || (q8 && qs && kv8)) && (o || partial_slot0 >= 0), FLEXAM_E_ARG, "attn_fwd: null pointer");
-  FX_REQUIRE(head_dim == HD, FLEXAM_E_SHAPE, "attn_fwd: head_dim %d unsupported (128 only)", head_dim);
-  FX_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, FLEXAM_E_SHAPE, "attn_fwd: empty problem B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
-  FX_REQUIRE(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && o_rs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0 &&
-                 o_bs % 8 == 0,
-             FLEXAM_E_SHAPE, "attn_fwd: strides must keep 16-byte alignment of head rows");
-  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o) % 16 == 0, FLEXAM_E_ARG, "attn_fwd: misaligned pointer");
-  const int tiles_all = (Lk + KVBLK - 1) / KVBLK;
-  FX_REQUIRE(kv_splits >= 1 && kv_splits <= tiles_all, FLEXAM_E_ARG, "attn_fwd: %d key splits for %d key tiles", kv_splits, tiles_all);
-  FX_REQUIRE((kv_splits == 1 && partial_slot0 < 0) || (ws_o && ws_ml), FLEXAM_E_ARG, "attn_fwd: split-KV needs both workspaces");
-  AttnParams p;
-  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v; p.o = (bf16*)o;
-  p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs; p.v_bs = v_bs; p.v_rs = v_rs; p.o_bs = o_bs; p.o_rs = o_rs;
-  p.B = B; p.H = H; p.Lq = Lq; p.Lk = Lk;
+// One attention call as its entry point states it: every extern "C" entry fills the fields it has.
+struct AttnCall {
+  const void *q = nullptr, *k = nullptr, *v = nullptr;
+  void *o = nullptr, *stream = nullptr;
+  int64_t q_bs = 0, q_rs = 0, k_bs = 0, k_rs = 0, v_bs = 0, v_rs = 0, o_bs = 0, o_rs = 0;
+  int B = 0, H = 0, Lq = 0, Lk = 0, head_dim = 0;
+  float softmax_scale = 0.f, last_key_bias = 0.f;
+  // units from split_from_unit on run as kv_splits key ranges each; partial_slot0 >= 0: partials of every unit into the workspace slots from it on, no merge
+  int kv_splits = 1, split_from_unit = 0, partial_slot0 = -1;
+  float *ws_o = nullptr, *ws_ml = nullptr;
+  const void *q8 = nullptr, *qs = nullptr, *kv8 = nullptr;   // MXFP8 operands (flexam_attn_fp8_pack) instead of q / k / v
+  int kv8_chunk_tiles = 0;                     // 0 = one chunk holds all key tiles
+};
+// The seven instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
+// cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
+struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
+AttnInstance attn_instance(bool fp8, bool cross, bool prescaled, bool full, bool short_ctx) {
+  constexpr int BF = NSLOT * 2 * KV_TILE_BYTES, F8 = NSLOT * REC_BYTES;
+  static const AttnInstance table[7] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
+                                        {attn_fwd_kernel<1, true>, BF, 3}, {attn_fwd_kernel<0, true, true>, BF, 4},
+                                        {attn_fwd_kernel<1, true, false, true>, BF, 5}, {attn8_fwd_kernel<0>, F8, 6}};
+  return table[fp8 ? 6 : full ? 4 : short_ctx ? 5 : (cross ? 1 : 0) + (prescaled ? 2 : 0)];
+}
+// FLEXAM_ATTN_FULL / _SHORT / _FUSED_TAIL, read per call (A/B in one process): 0 = the general instance / one workgroup per q block / two launches
+bool attn_switch(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }
+void scale_and_blocks(AttnParams& p, float softmax_scale) {      // what the attention launches and the merge alone derive alike
   p.prescaled = softmax_scale < 0.f;                   // FLEXAM_ATTN_PRESCALED: q already carries softmax_scale * log2(e)
   p.scale_log2e = p.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
-  p.q_blocks = (Lq + QBLK - 1) / QBLK;
-  p.tiles_per_split = (tiles_all + kv_splits - 1) / kv_splits;
-  p.kv_splits = (tiles_all + p.tiles_per_split - 1) / p.tiles_per_split;     // drop empty trailing splits
-  p.ws_o = ws_o; p.ws_ml = ws_ml;
-  p.partial = 0; p.slot0 = 0; p.n_slots = p.kv_splits; p.whole_units = 0;
-  p.last_key_bias = last_key_bias;
-  p.q8 = (const unsigned char*)q8; p.qs = (const unsigned*)qs; p.kv8 = (const unsigned char*)kv8;
-  p.lq_pad = p.q_blocks * QBLK;
-  p.kv8_chunk_tiles = kv8_chunk_tiles > 0 ? kv8_chunk_tiles : tiles_all;
+  p.q_blocks = (p.Lq + QBLK - 1) / QBLK;
+}
+void split_part(AttnParams& p, int unit0, int n_units, int S, int tps) {      // n_units units from unit0 on as S key ranges of tps tiles each, written as partials
+  p.unit0 = unit0; p.n_units = n_units; p.kv_splits = S; p.tiles_per_split = tps; p.partial = 1; p.n_slots = S;
+}
+void launch_merge(const AttnParams& p, void* stream) {      // one wave per row of the launch's units, grid-stride past 16384 workgroups
+  const int64_t g = ((int64_t)p.n_units * QBLK + 3) / 4;
+  hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, (hipStream_t)stream, p);
+}
+
+int attn_run(const AttnCall& c) {
+  FX_REQUIRE(((c.q && c.k && c.v) || (c.q8 && c.qs && c.kv8)) && (c.o || c.partial_slot0 >= 0), FLEXAM_E_ARG, "attn_fwd: null pointer");
+  FX_REQUIRE(c.head_dim == HD, FLEXAM_E_SHAPE, "attn_fwd: head_dim %d unsupported (128 only)", c.head_dim);
+  FX_REQUIRE(c.B > 0 && c.H > 0 && c.Lq > 0 && c.Lk > 0, FLEXAM_E_SHAPE, "attn_fwd: empty problem B=%d H=%d Lq=%d Lk=%d", c.B, c.H, c.Lq, c.Lk);
+  FX_REQUIRE(c.q_rs % 8 == 0 && c.k_rs % 8 == 0 && c.v_rs % 8 == 0 && c.o_rs % 8 == 0 && c.q_bs % 8 == 0 && c.k_bs % 8 == 0 && c.v_bs % 8 == 0 && c.o_bs % 8 == 0,
+             FLEXAM_E_SHAPE, "attn_fwd: strides must keep 16-byte alignment of head rows");
+  FX_REQUIRE(((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v | (uintptr_t)c.o) % 16 == 0, FLEXAM_E_ARG, "attn_fwd: misaligned pointer");
+  const int tiles_all = (c.Lk + KVBLK - 1) / KVBLK;
+  FX_REQUIRE(c.kv_splits >= 1 && c.kv_splits <= tiles_all, FLEXAM_E_ARG, "attn_fwd: %d key splits for %d key tiles", c.kv_splits, tiles_all);
+  FX_REQUIRE((c.kv_splits == 1 && c.partial_slot0 < 0) || (c.ws_o && c.ws_ml), FLEXAM_E_ARG, "attn_fwd: split-KV needs both workspaces");
+  AttnParams p;
+  p.q = (const bf16*)c.q; p.k = (const bf16*)c.k; p.v = (const bf16*)c.v; p.o = (bf16*)c.o; p.B = c.B; p.H = c.H; p.Lq = c.Lq; p.Lk = c.Lk;
+  p.q_bs = c.q_bs; p.q_rs = c.q_rs; p.k_bs = c.k_bs; p.k_rs = c.k_rs; p.v_bs = c.v_bs; p.v_rs = c.v_rs; p.o_bs = c.o_bs; p.o_rs = c.o_rs;
+  scale_and_blocks(p, c.softmax_scale);
+  const int tps = (tiles_all + c.kv_splits - 1) / c.kv_splits;
+  const int S = (tiles_all + tps - 1) / tps;           // drop empty trailing splits
+  p.ws_o = c.ws_o; p.ws_ml = c.ws_ml; p.last_key_bias = c.last_key_bias;
+  p.partial = 0; p.slot0 = 0; p.n_slots = S; p.whole_units = 0;
+  p.q8 = (const unsigned char*)c.q8; p.qs = (const unsigned*)c.qs; p.kv8 = (const unsigned char*)c.kv8; p.lq_pad = p.q_blocks * QBLK;
+  p.kv8_chunk_tiles = c.kv8_chunk_tiles > 0 ? c.kv8_chunk_tiles : tiles_all;
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
-  FX_REQUIRE(q8 || (int64_t)Lk * k_rs * 2 < (1ll << 31) && (int64_t)Lk * v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
+  FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
-  const int smem = q8 ? NSLOT * REC_BYTES : NSLOT * 2 * KV_TILE_BYTES;   // ring of 4 K tiles, then ring of 4 V tiles: 128 KiB (fp8: 4 records, 68 KiB)
-  const bool cross = Lk <= 1024;        // separate symbol for the short-context (text) launches
-  auto kern = cross ? (p.prescaled ? attn_fwd_kernel<1, true> : attn_fwd_kernel<1, false>)
-                    : (p.prescaled ? attn_fwd_kernel<0, true> : attn_fwd_kernel<0, false>);
-  bool body16 = false;
-  // the text cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup
-  const char* se_ = getenv("FLEXAM_ATTN_SHORT");       // read per call (A/B in one process); 0 = one workgroup per q block
-  const bool short_ctx = !q8 && cross && p.prescaled && tiles_all <= NSLOT && kv_splits == 1 && partial_slot0 < 0 && !body16 && !(se_ && atoi(se_) == 0);
-  if (short_ctx) kern = attn_fwd_kernel<1, true, false, true>;
-  const char* fe_ = getenv("FLEXAM_ATTN_FULL");        // read per call (A/B in one process); 0 = the general instance
-  const bool full = !q8 && !cross && p.prescaled && Lk >= KVBLK && last_key_bias == 0.f && !body16 && !(fe_ && atoi(fe_) == 0);
-  if (full) kern = attn_fwd_kernel<0, true, true>;
-  if (q8) kern = attn8_fwd_kernel<0>;
-  static bool attr_set[FLEXAM_MAX_DEVICES][11] = {};      // per device and kernel instance
-  const int which = q8 ? 8 : full ? 9 : short_ctx ? 10 : (cross ? 1 : 0) + (p.prescaled ? 2 : 0) + (body16 ? 4 : 0);
-  const int dev = flexam_current_device();
-  if (!attr_set[dev][which]) {
-    if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-      return flexam_fail(FLEXAM_E_LAUNCH, "attn_fwd: cannot raise dynamic LDS to %d bytes", smem);
-    attr_set[dev][which] = true;
+  const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
+  const bool short_ctx = !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
+  const bool full = !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
+  const AttnInstance inst = attn_instance(fp8, cross, p.prescaled, full, short_ctx);
+  static bool attr_set[FLEXAM_MAX_DEVICES][7] = {};      // per device and kernel instance
+  bool& lds_raised = attr_set[flexam_current_device()][inst.slot];
+  if (!lds_raised) {
+    if (hipFuncSetAttribute((const void*)inst.kern, hipFuncAttributeMaxDynamicSharedMemorySize, inst.smem) != hipSuccess)
+      return flexam_fail(FLEXAM_E_LAUNCH, "attn_fwd: cannot raise dynamic LDS to %d bytes", inst.smem);
+    lds_raised = true;
   }
-  const int units = B * H * p.q_blocks;
-  FX_REQUIRE(split_from_unit >= 0 && split_from_unit <= units, FLEXAM_E_ARG, "attn_fwd: split_from_unit %d of %d units", split_from_unit, units);
-  const int S = p.kv_splits, tps = p.tiles_per_split;
-  if (partial_slot0 >= 0) {                // every unit, this call's keys only: partials into slots slot0 .. slot0 + S - 1, no merge
-    FX_REQUIRE(S == kv_splits, FLEXAM_E_ARG, "attn_fwd_partial: %d key ranges requested but %d key tiles give %d (use ceil(tiles / ceil(tiles / S)))",
-               kv_splits, tiles_all, S);
-    p.unit0 = 0; p.n_units = units; p.kv_splits = S; p.tiles_per_split = tps; p.partial = 1; p.slot0 = partial_slot0;
-    hipLaunchKernelGGL(kern, dim3(p.n_units * S), dim3(NT), smem, (hipStream_t)stream, p);
+  const int units = c.B * c.H * p.q_blocks;
+  FX_REQUIRE(c.split_from_unit >= 0 && c.split_from_unit <= units, FLEXAM_E_ARG, "attn_fwd: split_from_unit %d of %d units", c.split_from_unit, units);
+  auto launch = [&](int grid) { hipLaunchKernelGGL(inst.kern, dim3(grid), dim3(NT), inst.smem, (hipStream_t)c.stream, p); };
+  auto launch_whole = [&](int n_units, int grid) { p.unit0 = 0; p.n_units = n_units; p.kv_splits = 1; p.tiles_per_split = tiles_all; launch(grid); };
+  if (c.partial_slot0 >= 0) {              // (a) every unit, this call's keys only: partials into slots slot0 .. slot0 + S - 1, no merge
+    FX_REQUIRE(S == c.kv_splits, FLEXAM_E_ARG, "attn_fwd_partial: %d key ranges requested but %d key tiles give %d (use ceil(tiles / ceil(tiles / S)))",
+               c.kv_splits, tiles_all, S);
+    split_part(p, 0, units, S, tps);
+    p.slot0 = c.partial_slot0;
+    launch(units * S);
     return flexam_check_launch("flexam_attn_fwd_partial");
   }
-  if (S == 1) split_from_unit = units;
-  if (short_ctx) {                         // one persistent workgroup per CU, each with a contiguous share of the units
-    p.unit0 = 0; p.n_units = units; p.kv_splits = 1; p.tiles_per_split = tiles_all;
+  const int whole = S == 1 ? units : c.split_from_unit;      // units [0, whole): one pass over all keys; the rest: S key ranges each, then the merge
+  if (short_ctx) {                         // (b) one persistent workgroup per CU, each with a contiguous share of the units
     const int cus = flexam_num_cus();
-    hipLaunchKernelGGL(kern, dim3(units < cus ? units : cus), dim3(NT), smem, (hipStream_t)stream, p);
-    return flexam_check_launch("flexam_attn_fwd");
-  }
-  const char* fe = getenv("FLEXAM_ATTN_FUSED_TAIL");     // read per call (A/B in one process); 0 = the two-launch form
-  if (split_from_unit > 0 && split_from_unit < units && (!fe || atoi(fe) != 0)) {
-    // one launch: whole units and the split tail side by side on every XCD (see AttnParams::whole_units), then the merge
-    p.whole_units = split_from_unit;
-    p.unit0 = split_from_unit; p.n_units = units - split_from_unit; p.kv_splits = S; p.tiles_per_split = tps; p.partial = 1; p.n_slots = S;
-    const int grid = 8 * ((p.whole_units + 7) / 8 + (p.n_units * S + 7) / 8);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), smem, (hipStream_t)stream, p);
-    const int64_t g = ((int64_t)p.n_units * QBLK + 3) / 4;
-    hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, (hipStream_t)stream, p);
-    return flexam_check_launch("flexam_attn_fwd");
-  }
-  if (split_from_unit > 0) {               // units [0, split_from_unit): one pass over all keys
-    p.unit0 = 0; p.n_units = split_from_unit; p.kv_splits = 1; p.tiles_per_split = tiles_all;
-    hipLaunchKernelGGL(kern, dim3(p.n_units), dim3(NT), smem, (hipStream_t)stream, p);
-  }
-  if (split_from_unit < units) {           // the rest: S key ranges each, then the merge
-    p.unit0 = split_from_unit; p.n_units = units - split_from_unit; p.kv_splits = S; p.tiles_per_split = tps; p.partial = 1; p.n_slots = S;
-    hipLaunchKernelGGL(kern, dim3(p.n_units * S), dim3(NT), smem, (hipStream_t)stream, p);
-    const int64_t g = ((int64_t)p.n_units * QBLK + 3) / 4;
-    hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, (hipStream_t)stream, p);
+    launch_whole(units, units < cus ? units : cus);
+  } else if (whole > 0 && whole < units && attn_switch("FLEXAM_ATTN_FUSED_TAIL")) {
+    // (c) one launch: whole units and the split tail side by side on every XCD (see AttnParams::whole_units), then the merge
+    p.whole_units = whole;
+    split_part(p, whole, units - whole, S, tps);
+    launch(8 * ((whole + 7) / 8 + (p.n_units * S + 7) / 8));
+    launch_merge(p, c.stream);
+  } else {                                 // (d) a launch for each kind
+    if (whole > 0) launch_whole(whole, whole);
+    if (whole < units) {
+      split_part(p, whole, units - whole, S, tps);
+      launch(p.n_units * S);
+      launch_merge(p, c.stream);
+    }
   }
   return flexam_check_launch("flexam_attn_fwd");
 }
@@ -813,32 +800,42 @@ int attn_run(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k
 extern "C" int flexam_attn_fwd(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
                                const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
                                int Lq, int Lk, int head_dim, float softmax_scale, void* stream) {
-  return attn_run(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk, head_dim, softmax_scale, 1, 0, nullptr,
-                  nullptr, stream);
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  return attn_run(c);
 }
 
 extern "C" int flexam_attn_fwd_lastkey(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
                                        const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
                                        int Lq, int Lk, int head_dim, float softmax_scale, float last_key_multiplicity, void* stream) {
   FX_REQUIRE(last_key_multiplicity >= 1.0f, FLEXAM_E_ARG, "attn_fwd_lastkey: multiplicity %g < 1", (double)last_key_multiplicity);
-  return attn_run(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk, head_dim, softmax_scale, 1, 0, nullptr,
-                  nullptr, stream, -1, log2f(last_key_multiplicity));
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream; c.last_key_bias = log2f(last_key_multiplicity);
+  return attn_run(c);
 }
 
 extern "C" int flexam_attn_fwd_splitkv(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
                                        const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
                                        int Lq, int Lk, int head_dim, float softmax_scale, int kv_splits, int split_from_unit,
                                        float* ws_o, float* ws_ml, void* stream) {
-  return attn_run(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, o, o_bs, o_rs, B, H, Lq, Lk, head_dim, softmax_scale, kv_splits,
-                  split_from_unit, ws_o, ws_ml, stream);
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  c.kv_splits = kv_splits; c.split_from_unit = split_from_unit; c.ws_o = ws_o; c.ws_ml = ws_ml;
+  return attn_run(c);
 }
 
 extern "C" int flexam_attn_fwd_partial(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
                                        const void* v, int64_t v_bs, int64_t v_rs, int B, int H, int Lq, int Lk, int head_dim,
                                        float softmax_scale, int kv_splits, int slot0, float* ws_o, float* ws_ml, void* stream) {
   FX_REQUIRE(slot0 >= 0, FLEXAM_E_ARG, "attn_fwd_partial: negative slot");
-  return attn_run(q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, nullptr, 0, 0, B, H, Lq, Lk, head_dim, softmax_scale, kv_splits, 0, ws_o,
-                  ws_ml, stream, slot0);
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  c.kv_splits = kv_splits; c.partial_slot0 = slot0; c.ws_o = ws_o; c.ws_ml = ws_ml;
+  return attn_run(c);
 }
 
 extern "C" int flexam_attn_fp8_pack(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
@@ -879,8 +876,11 @@ extern "C" int flexam_attn_fwd_fp8(const void* q8, const void* qs, const void* k
                                    int head_dim, int kv_splits, int split_from_unit, float* ws_o, float* ws_ml, void* stream) {
   FX_REQUIRE(q8 && qs && kv8, FLEXAM_E_ARG, "attn_fwd_fp8: null pointer");
   FX_REQUIRE(((uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG, "attn_fwd_fp8: misaligned pointer");
-  return attn_run(nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, o, o_bs, o_rs, B, H, L, L, head_dim, FLEXAM_ATTN_PRESCALED, kv_splits,
-                  split_from_unit, ws_o, ws_ml, stream, -1, 0.f, q8, qs, kv8);
+  AttnCall c;
+  c.q8 = q8; c.qs = qs; c.kv8 = kv8; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = FLEXAM_ATTN_PRESCALED; c.stream = stream;
+  c.kv_splits = kv_splits; c.split_from_unit = split_from_unit; c.ws_o = ws_o; c.ws_ml = ws_ml;
+  return attn_run(c);
 }
 
 extern "C" int flexam_attn_fwd_fp8_chunked(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
@@ -889,8 +889,11 @@ extern "C" int flexam_attn_fwd_fp8_chunked(const void* q8, const void* qs, const
   FX_REQUIRE(q8 && qs && kv8, FLEXAM_E_ARG, "attn_fwd_fp8_chunked: null pointer");
   FX_REQUIRE(((uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG, "attn_fwd_fp8_chunked: misaligned pointer");
   FX_REQUIRE(chunk_tiles > 0, FLEXAM_E_SHAPE, "attn_fwd_fp8_chunked: chunk_tiles = %d", chunk_tiles);
-  return attn_run(nullptr, 0, 0, nullptr, 0, 0, nullptr, 0, 0, o, o_bs, o_rs, B, H, Lq, Lk, head_dim, FLEXAM_ATTN_PRESCALED, kv_splits,
-                  split_from_unit, ws_o, ws_ml, stream, -1, 0.f, q8, qs, kv8, chunk_tiles);
+  AttnCall c;
+  c.q8 = q8; c.qs = qs; c.kv8 = kv8; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = FLEXAM_ATTN_PRESCALED; c.stream = stream;
+  c.kv_splits = kv_splits; c.split_from_unit = split_from_unit; c.ws_o = ws_o; c.ws_ml = ws_ml; c.kv8_chunk_tiles = chunk_tiles;
+  return attn_run(c);
 }
 
 extern "C" int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int head_dim, float softmax_scale,
@@ -900,12 +903,8 @@ extern "C" int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int
   FX_REQUIRE(o_rs % 4 == 0 && o_bs % 4 == 0 && (uintptr_t)o % 8 == 0, FLEXAM_E_SHAPE, "attn_merge: output rows must keep 8-byte alignment");
   AttnParams p{};
   p.o = (bf16*)o; p.o_bs = o_bs; p.o_rs = o_rs; p.B = B; p.H = H; p.Lq = Lq;
-  p.prescaled = softmax_scale < 0.f;
-  p.scale_log2e = p.prescaled ? 1.0f : softmax_scale * 1.4426950408889634f;
-  p.q_blocks = (Lq + QBLK - 1) / QBLK;
-  p.unit0 = 0; p.n_units = B * H * p.q_blocks; p.n_slots = n_slots;
-  p.ws_o = const_cast<float*>(ws_o); p.ws_ml = const_cast<float*>(ws_ml);
-  const int64_t g = ((int64_t)p.n_units * QBLK + 3) / 4;
-  hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, (hipStream_t)stream, p);
+  scale_and_blocks(p, softmax_scale);
+  p.unit0 = 0; p.n_units = B * H * p.q_blocks; p.n_slots = n_slots; p.ws_o = const_cast<float*>(ws_o); p.ws_ml = const_cast<float*>(ws_ml);
+  launch_merge(p, stream);
   return flexam_check_launch("flexam_attn_merge");
 }

@@ -1,8 +1,8 @@
 // flexam_amd/csrc/attn_fp8.inc -- self-attention with MXFP8 operands (OCP e4m3 + one E8M0 scale per 32 elements), the quantised
 // variant behind VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION (FlexAM/models/attention_utils.py:195-203 calls the third-party `sageattn`,
 // which quantises Q, K and P.V the same way; what is kept here is its contract -- softmax attention within a stated tolerance --
-// not its int8 / per-block format).  Included by attn.hip inside its namespace: shares AttnParams, the work-unit walk, the split-KV
-// workspace and attn_merge_kernel with the bf16 kernel.
+// not its int8 / per-block format).  Included by attn.hip inside its namespace: shares AttnParams, the work-unit walk
+// (unit_of_workgroup), the epilogue (store_partial / store_output), the split-KV workspace and attn_merge_kernel with the bf16 kernel.
 //
 // Both products run on v_mfma_scale_f32_32x32x64_f8f6f4 (2 x the bf16 MFMA rate).  Operand maps of that instruction with e4m3 data,
 // found with exact integers (tools/probes/mfma_scale32_map.hip, mfma_scale32_probe.hip): lane (r = l & 31, h = l >> 5) holds, in
@@ -47,29 +47,8 @@ __global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r_ = lane & 31, h_ = lane >> 5;
 
-  auto eighth = [](int n, int xcd, int local) -> int {
-    const int q = n >> 3, rr = n & 7;
-    if (local >= q + (xcd < rr ? 1 : 0)) return -1;
-    return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + local;
-  };
   int split = 0, ul, unit, tps = p.tiles_per_split, partial = p.partial;
-  {
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int wmax = (p.whole_units + 7) >> 3;
-    if (local < wmax) {
-      unit = eighth(p.whole_units, xcd, local);
-      if (unit < 0) return;
-      ul = unit;
-      tps = (p.Lk + KVBLK - 1) / KVBLK;
-      partial = 0;
-    } else {
-      const int j = eighth(p.n_units * p.kv_splits, xcd, local - wmax);
-      if (j < 0) return;
-      split = j / p.n_units;
-      ul = j - split * p.n_units;
-      unit = p.unit0 + ul;
-    }
-  }
+  if (!unit_of_workgroup(p, split, ul, unit, tps, partial)) return;
   const int qb = unit % p.q_blocks;
   const int bh = unit / p.q_blocks;
   const int head = bh % p.H, b = bh / p.H;
@@ -321,47 +300,16 @@ __global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
-  // ---- epilogue (the bf16 kernel's): O[q][32dt + 8i + 4h + (0..3)] = o_acc[dt][4i + (0..3)] / l.  Lane-derived values are rebuilt
-  // from a fresh lane id: kept alive across the loop they are registers it does not have (spill slots)
+  // ---- epilogue (store_partial / store_output of attn.hip).  Lane-derived values are rebuilt from a fresh lane id: kept alive across
+  // the loop they are registers it does not have (spill slots)
   const float l_tot = pair_sum(l_run);
   const float osc = __builtin_amdgcn_exp2f(-rd);       // O is in the units of the first reference, the row sum in those of the last
   const int le = fresh_lane(), r = le & 31, h = le >> 5;
-  const int qi = q0 + r;
   if (partial) {
-    if (qi < p.Lq) {
-      const int64_t row = ((int64_t)(p.slot0 + split) * p.n_units + ul) * QBLK + wave * 32 + r;
-      float* orow = p.ws_o + row * HD;
-#pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          f32x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) ov[e] = o_acc[dt][4 * i + e] * osc;
-          *(f32x4*)(orow + 32 * dt + 8 * i + 4 * h) = ov;
-        }
-      if (h == 0) *(f32x2*)(p.ws_ml + row * 2) = (f32x2){ref, l_tot};      // reference in exp2 units (the merge runs in its prescaled form)
-    }
+    store_partial<true>(p, o_acc, osc, ref, l_tot, split, ul, wave, r, h, q0 + r);      // reference in exp2 units (the merge runs in its prescaled form)
     return;
   }
-  const float inv_l = osc / l_tot;
-  bf16* orow = p.o + (int64_t)b * p.o_bs + (int64_t)min(qi, p.Lq - 1) * p.o_rs + head * HD + 8 * h;
-#pragma unroll
-  for (int dt = 0; dt < 4; ++dt)
-#pragma unroll
-    for (int i = 0; i < 4; i += 2) {
-      bf16x4 even, odd;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        even[e] = f2bf(o_acc[dt][4 * i + e] * inv_l);
-        odd[e] = f2bf(o_acc[dt][4 * i + 4 + e] * inv_l);
-      }
-      const u32x2 ev = __builtin_bit_cast(u32x2, even), od = __builtin_bit_cast(u32x2, odd);
-      unsigned a0 = ev[0], a1 = ev[1], c0 = od[0], c1 = od[1];
-      half_swap_u32(a0, c0);
-      half_swap_u32(a1, c1);
-      if (qi < p.Lq) *(u32x4*)(orow + 32 * dt + 8 * i) = (u32x4){a0, a1, c0, c1};
-    }
+  store_output(p, o_acc, osc / l_tot, b, head, q0 + r, h);
 }
 
 // ---- the pack kernel: q, k (after RMSNorm + RoPE; q carrying softmax_scale * log2 e) and v, bf16 [B, L, H, 128] -> MXFP8 operands.
