@@ -7,7 +7,9 @@ Exports the reference's names (FlexAM/models/__init__.py, FlexAM/pipeline/__init
 and, for the step in front of the sampler, `visualize_tracking_DELTA` (pipelines.py:1852: tracks -> conditioning videos), and the
 qfloat8 helpers of FlexAM/utils/fp8_optimization.py (`convert_model_weight_to_float8`, `convert_weight_dtype_wrapper`, ...), and
 demo.py's edit masks (`generate_mask_fg_tracking_for_validation`, `generate_mask_bg_tracking_for_validation`), and the edit tracks
-of pipelines.py (`CameraMotionGenerator`, `ObjectMotionGenerator`, `convert_moge_to_delta_format`; `moge_tracks` fuses demo.py:222-266).
+of pipelines.py (`CameraMotionGenerator`, `ObjectMotionGenerator`, `convert_moge_to_delta_format`; `moge_tracks` fuses demo.py:222-266),
+and the frames that cross the boundary (`get_maskvideo_to_video_latent`, `get_video_to_video_latent`'s tensor branch, `resize_frames`,
+`frames_to_bytes`: flexam_amd/frames.py).
 Arithmetic runs in libflexam_hip.so (hand-written gfx950 HIP kernels, C ABI in
 include/flexam_hip.h); this package is the host-side mirror of the reference interface.
 """
@@ -16,7 +18,8 @@ __all__ = ["Wan2_2Transformer3DModel_FlexAM", "WanTransformer3DModel_FlexAM", "A
            "FlowDPMSolverMultistepScheduler", "WanT5EncoderModel", "attention", "visualize_tracking_DELTA",
            "replace_parameters_by_name", "convert_model_weight_to_float8", "autocast_model_forward", "convert_weight_dtype_wrapper",
            "generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation",
-           "CameraMotionGenerator", "ObjectMotionGenerator", "convert_moge_to_delta_format", "moge_tracks"]
+           "CameraMotionGenerator", "ObjectMotionGenerator", "convert_moge_to_delta_format", "moge_tracks",
+           "resize_tables", "resize_frames", "frames_to_bytes", "get_maskvideo_to_video_latent", "get_video_to_video_latent"]
 
 
 def __getattr__(name):
@@ -56,5 +59,8 @@ def __getattr__(name):
         return getattr(m, name)
     if name in ("CameraMotionGenerator", "ObjectMotionGenerator", "convert_moge_to_delta_format", "moge_tracks"):
         from . import motion as m
+        return getattr(m, name)
+    if name in ("resize_tables", "resize_frames", "frames_to_bytes", "get_maskvideo_to_video_latent", "get_video_to_video_latent"):
+        from . import frames as m
         return getattr(m, name)
     raise AttributeError(name)

@@ -1088,6 +1088,58 @@ def edit_mask_dilate(runs, nruns, width, half_widths, out=None):
     return out
 
 
+# ----------------------------------------------------------------------------- frames across the boundary (csrc/frames.hip)
+FRAMES_MAX_TAPS = abi.CONSTANTS["FLEXAM_FRAMES_MAX_TAPS"]
+
+
+def _tap_table(table, n_out, n_in, device, what):
+    index, weights = table
+    if tuple(index.shape) != (n_out, 2) or index.dtype != I32 or not index.is_contiguous() or index.device != device:
+        raise RuntimeError(f"{what}: tap index must be contiguous int32 [{n_out}, 2] on {device}, got {tuple(index.shape)} {index.dtype}")
+    if weights.dim() != 2 or weights.shape[0] != n_out or weights.dtype != F32 or not weights.is_contiguous() or weights.device != device:
+        raise RuntimeError(f"{what}: tap weights must be contiguous float32 [{n_out}, k] on {device}, got {tuple(weights.shape)} {weights.dtype}")
+    k = weights.shape[1]
+    if not 1 <= k <= min(FRAMES_MAX_TAPS, n_in):
+        raise RuntimeError(f"{what}: {k} taps per output, 1 .. min({FRAMES_MAX_TAPS}, source size {n_in}) allowed")
+    return index, weights, k
+
+
+def frames_resize(src, dst, y_table, x_table, mul=1.0, div=1.0, add=0.0):
+    """src: (t, c, y, x) view [T, C, H, W], uint8 or float32, any non-negative strides; dst: (t, c, y, x) view [T, C, oh, ow] float32 with
+    contiguous columns; *_table = (index [n_out, 2] int32 (first, count), weights [n_out, k] float32) as flexam_amd.frames builds them.
+    dst = resize(src) * mul / div + add (flexam_frames_resize)."""
+    if src.dim() != 4 or src.dtype not in (U8, F32) or not src.is_cuda:
+        raise RuntimeError(f"frames_resize: a uint8 or float32 GPU view [T, C, H, W] is required, got {tuple(src.shape)} {src.dtype} on {src.device}")
+    T, C, H, W = src.shape
+    if dst.dim() != 4 or dst.dtype != F32 or dst.device != src.device or dst.shape[:2] != (T, C) or (dst.shape[3] > 1 and dst.stride(3) != 1):
+        raise RuntimeError(f"frames_resize: dst must be a float32 view [{T}, {C}, oh, ow] with contiguous columns on {src.device}, got "
+                           f"{tuple(dst.shape)} {dst.dtype} stride {dst.stride()}")
+    oh, ow = dst.shape[2:]
+    if min(T, C, H, W, oh, ow) < 1 or min(src.stride() + dst.stride()) < 0:
+        raise RuntimeError(f"frames_resize: empty frames or negative strides: {tuple(src.shape)} -> {tuple(dst.shape)}")
+    if float(div) == 0.0:
+        raise RuntimeError("frames_resize: div = 0")
+    yi, yw, ky = _tap_table(y_table, oh, H, src.device, "frames_resize (y)")
+    xi, xw, kx = _tap_table(x_table, ow, W, src.device, "frames_resize (x)")
+    _call("flexam_frames_resize", _ptr(src), int(src.dtype == U8), *src.stride(), T, C, H, W, _ptr(dst, F32), *dst.stride()[:3], oh, ow,
+          _ptr(yi, I32), _ptr(yw, F32), ky, _ptr(xi, I32), _ptr(xw, F32), kx, float(mul), float(div), float(add))
+    return dst
+
+
+def frames_to_bytes(video, signed=True, out=None):
+    """video [C, T, H, W] float32 or bf16, contiguous, C <= 4 -> out [T, H, W, C] uint8 (flexam_frames_to_bytes): signed: x / 2 + 0.5
+    first; clamp to [0, 1], * 255, truncation; NaN -> 0."""
+    if video.dim() != 4 or video.dtype not in (F32, BF16) or not video.is_contiguous() or not 1 <= video.shape[0] <= 4 or video.numel() == 0:
+        raise RuntimeError(f"frames_to_bytes: a contiguous float32 or bf16 clip [C <= 4, T, H, W] is required, got {tuple(video.shape)} {video.dtype}")
+    C, T, H, W = video.shape
+    if out is None:
+        out = torch.empty(T, H, W, C, device=video.device, dtype=U8)
+    elif tuple(out.shape) != (T, H, W, C) or out.dtype != U8 or not out.is_contiguous() or out.device != video.device:
+        raise RuntimeError(f"frames_to_bytes: out must be contiguous uint8 {(T, H, W, C)} on {video.device}")
+    _call("flexam_frames_to_bytes", _ptr(video), int(video.dtype == BF16), C, T, H, W, int(bool(signed)), _ptr(out, U8))
+    return out
+
+
 # ----------------------------------------------------------------------------- edit tracks: camera / object motion (csrc/motion.hip)
 MOTION_CHUNK = abi.CONSTANTS["FLEXAM_MOTION_CHUNK"]
 F64 = torch.float64

@@ -500,6 +500,24 @@ int flexam_raster_colors_depth(const float* points, const unsigned char* visible
                                const unsigned char* lut, unsigned char* colors, void* stream);
 int flexam_raster_colors_cosine(const float* code, int64_t N, unsigned char* colors, void* stream);
 
+/* Frames across the boundary (flexam_amd/frames.py; csrc/frames.hip).  Replaces the host resizes of FlexAM/utils/utils.py:473-517
+ * get_maskvideo_to_video_latent (torchvision resize of float frames: bilinear, antialiased) and :424-438 get_video_to_video_latent's
+ * tensor branch (F.interpolate bilinear, align_corners=False, then * 255, / 255 in numpy / torch), and the byte conversion of
+ * utils.py:59-88 save_videos_grid behind the pipeline's decode_latents.
+ * frames_resize: dst[t][c][oy][ox] = (sum_j wy[oy][j] * sum_i wx[ox][i] * src[t][c][y0 + j][x0 + i]) * mul / div + add, fp32, taps in
+ *   ascending order, the three closing steps rounded one at a time (each skipped at its neutral value 1, 1, 0; div != 0).  src: uint8
+ *   (src_is_u8 != 0; widened exactly) or float32, element strides s_t, s_c, s_y, s_x (>= 0), so [T, H, W, C] and [T, C, H, W] are both
+ *   views of it; dst float32, element strides d_t, d_c, d_y, columns contiguous.  Per axis a table made on the host: index [n_out][2] =
+ *   (first source index, tap count), weights [n_out][k] fp32 padded with zeros to the axis's largest tap count k (1 <= k <=
+ *   FLEXAM_FRAMES_MAX_TAPS, k <= the axis's source size).  The kernel clamps what it reads from a table into the source.
+ * frames_to_bytes: src [C][T][H][W] float32 or bf16 (C <= 4) -> dst [T][H][W][C] bytes.  is_signed != 0: x / 2, + 0.5 first; then clamp
+ *   to [0, 1], * 255, truncation toward zero; every step one float32 rounding.  NaN -> 0. */
+#define FLEXAM_FRAMES_MAX_TAPS 256
+int flexam_frames_resize(const void* src, int src_is_u8, int64_t s_t, int64_t s_c, int64_t s_y, int64_t s_x, int T, int C, int H, int W,
+                         float* dst, int64_t d_t, int64_t d_c, int64_t d_y, int oh, int ow, const int* y_index, const float* y_weights,
+                         int ky, const int* x_index, const float* x_weights, int kx, float mul, float div, float add, void* stream);
+int flexam_frames_to_bytes(const void* src, int src_is_bf16, int C, int T, int H, int W, int is_signed, unsigned char* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
