@@ -9,7 +9,7 @@ qfloat8 helpers of FlexAM/utils/fp8_optimization.py (`convert_model_weight_to_fl
 demo.py's edit masks (`generate_mask_fg_tracking_for_validation`, `generate_mask_bg_tracking_for_validation`), and the edit tracks
 of pipelines.py (`CameraMotionGenerator`, `ObjectMotionGenerator`, `convert_moge_to_delta_format`; `moge_tracks` fuses demo.py:222-266),
 and the frames that cross the boundary (`get_maskvideo_to_video_latent`, `get_video_to_video_latent`'s tensor branch, `resize_frames`,
-`frames_to_bytes`: flexam_amd/frames.py).
+`frames_to_bytes`: flexam_amd/frames.py), and FlexAM/utils/lora_utils.py's `merge_lora` / `unmerge_lora` (flexam_amd/lora_utils.py).
 Arithmetic runs in libflexam_hip.so (hand-written gfx950 HIP kernels, C ABI in
 include/flexam_hip.h); this package is the host-side mirror of the reference interface.
 """
@@ -19,7 +19,8 @@ __all__ = ["Wan2_2Transformer3DModel_FlexAM", "WanTransformer3DModel_FlexAM", "A
            "replace_parameters_by_name", "convert_model_weight_to_float8", "autocast_model_forward", "convert_weight_dtype_wrapper",
            "generate_mask_fg_tracking_for_validation", "generate_mask_bg_tracking_for_validation",
            "CameraMotionGenerator", "ObjectMotionGenerator", "convert_moge_to_delta_format", "moge_tracks",
-           "resize_tables", "resize_frames", "frames_to_bytes", "get_maskvideo_to_video_latent", "get_video_to_video_latent"]
+           "resize_tables", "resize_frames", "frames_to_bytes", "get_maskvideo_to_video_latent", "get_video_to_video_latent",
+           "merge_lora", "unmerge_lora"]
 
 
 def __getattr__(name):
@@ -62,5 +63,8 @@ def __getattr__(name):
         return getattr(m, name)
     if name in ("resize_tables", "resize_frames", "frames_to_bytes", "get_maskvideo_to_video_latent", "get_video_to_video_latent"):
         from . import frames as m
+        return getattr(m, name)
+    if name in ("merge_lora", "unmerge_lora"):
+        from . import lora_utils as m
         return getattr(m, name)
     raise AttributeError(name)

@@ -1342,3 +1342,33 @@ def raster_colors_cosine(code):
     out = torch.empty(code.shape[0], 3, device=code.device, dtype=U8)
     _call("flexam_raster_colors_cosine", _ptr(code, F32), code.shape[0], _ptr(out, U8))
     return out
+
+
+# ----------------------------------------------------------------------------- LoRA merge (csrc/lora.hip)
+_LORA_CODES = {BF16: abi.CONSTANTS["FLEXAM_LORA_BF16"], F32: abi.CONSTANTS["FLEXAM_LORA_F32"], F8: abi.CONSTANTS["FLEXAM_LORA_E4M3"]}
+
+
+def lora_merge(w, up, down, scale):
+    """w [N, K] (bf16, float32 or float8_e4m3fn; rows contiguous, any row stride >= K: a row range of a fused buffer is fine) +=
+    scale * up [N, r] @ down [r, K] in place (flexam_lora_merge): factors both float32 or both bf16, fp32 products and sums over j
+    ascending, one rounding to w's dtype (e4m3 saturates at +-448).  Unmerge: the same call with -scale."""
+    for name, t in (("w", w), ("up", up), ("down", down)):
+        if not torch.is_tensor(t) or t.dim() != 2 or not t.is_cuda:
+            raise RuntimeError(f"lora_merge: {name} must be a 2-D GPU tensor, got "
+                               f"{(tuple(t.shape), t.dtype, str(t.device)) if torch.is_tensor(t) else type(t)}")
+        if t.numel() == 0 or (t.shape[1] > 1 and t.stride(1) != 1) or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+            raise RuntimeError(f"lora_merge: {name} must be non-empty with contiguous rows that do not overlap, got shape "
+                               f"{tuple(t.shape)} stride {t.stride()}")
+    if w.dtype not in _LORA_CODES:
+        raise RuntimeError(f"lora_merge: w is stored as bf16, float32 or float8_e4m3fn, not {w.dtype}")
+    if up.dtype not in (F32, BF16) or down.dtype != up.dtype:
+        raise RuntimeError(f"lora_merge: up and down must both be float32 or both bf16, got {up.dtype} and {down.dtype}")
+    if up.device != w.device or down.device != w.device:
+        raise RuntimeError(f"lora_merge: w on {w.device}, up on {up.device}, down on {down.device}")
+    (N, K), r = w.shape, up.shape[1]
+    if up.shape[0] != N or tuple(down.shape) != (r, K):
+        raise RuntimeError(f"lora_merge: w {tuple(w.shape)} needs up [{N}, r] and down [r, {K}], got {tuple(up.shape)} and {tuple(down.shape)}")
+    ld = lambda t: max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
+    _call("flexam_lora_merge", _ptr(w), _LORA_CODES[w.dtype], ld(w), N, K, _ptr(up), _LORA_CODES[up.dtype], ld(up), _ptr(down),
+          _LORA_CODES[down.dtype], ld(down), r, float(scale))
+    return w

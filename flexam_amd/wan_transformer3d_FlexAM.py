@@ -537,8 +537,14 @@ class WanTransformer3DModel_FlexAM(nn.Module):
 
     def invalidate_engine(self):
         """Drops the device-side parameter packs and per-clip caches.  Needed only after edits the version counters cannot see
-        (`param.data` arithmetic on fp32 / bias / norm parameters; bf16 weight matrices are shared with the engine, not copied)."""
+        (`param.data` arithmetic on fp32 / bias / norm parameters, a kernel's write into a weight: flexam_amd.lora_utils; bf16 weight
+        matrices are shared with the engine, not copied).  The packs that live on the modules go too (`_Block.packed()` and its
+        attention packs, HipLinear's): their signature is the same version counters, and the e4m3 operand copies of enable_fp8_gemm
+        hang on them (dit_engine._fp8_weight)."""
         self._engine = None
+        for mod in self.modules():
+            if getattr(mod, "_pk", None) is not None:
+                mod._pk = None
         self._cond_key = None
         self._cond_ident = None
 

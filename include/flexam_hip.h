@@ -518,6 +518,21 @@ int flexam_frames_resize(const void* src, int src_is_u8, int64_t s_t, int64_t s_
                          int ky, const int* x_index, const float* x_weights, int kx, float mul, float div, float add, void* stream);
 int flexam_frames_to_bytes(const void* src, int src_is_bf16, int C, int T, int H, int W, int is_signed, unsigned char* dst, void* stream);
 
+/* LoRA merge into stored weights (flexam_amd/lora_utils.py; csrc/lora.hip).  Replaces `weight.data += multiplier * alpha *
+ * torch.mm(up, down)` of FlexAM/utils/lora_utils.py:480-485 (and `-=` of :594-599: unmerge is the same call with -s).
+ * lora_merge: W[n][k] <- round_to_W_dtype(float(W[n][k]) + s * sum_{j < r} U[n][j] * D[j][k]).  W [N][K], row stride ldw elements
+ *   (>= K: the rows of a fused q|k|v buffer are views), stored as bf16, fp32 or OCP e4m3 (w_dtype = FLEXAM_LORA_*); U [N][r], row
+ *   stride ldu; D [r][K], row stride ldd; both fp32 or both bf16 (u_dtype == d_dtype; e4m3 factors are refused).  Every product and
+ *   sum is fp32: acc = fma(U[n][j], D[j][k], acc) from 0 with j ascending, then fma(s, acc, W[n][k]); the result is rounded to the
+ *   storage type once, to nearest even.  e4m3: a result whose magnitude exceeds 448 saturates to +-448 (NaN stays NaN).  Any N, K,
+ *   r >= 1; in place, no allocation, no workspace.  FLEXAM_E_ARG: null pointer, unknown or mismatched dtype code; FLEXAM_E_SHAPE: a
+ *   size < 1 or a row stride shorter than its row. */
+#define FLEXAM_LORA_BF16 0
+#define FLEXAM_LORA_F32 1
+#define FLEXAM_LORA_E4M3 2
+int flexam_lora_merge(void* W, int w_dtype, int64_t ldw, int64_t N, int64_t K, const void* U, int u_dtype, int64_t ldu, const void* D,
+                      int d_dtype, int64_t ldd, int r, float s, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
