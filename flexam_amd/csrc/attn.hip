@@ -838,38 +838,102 @@ extern "C" int flexam_attn_fwd_partial(const void* q, int64_t q_bs, int64_t q_rs
   return attn_run(c);
 }
 
-extern "C" int flexam_attn_fp8_pack(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
-                                    int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
-                                    void* stream) {
+// the pack and the fused producer, without (k_shift = nullptr: the instances the plain entry points have always launched) and with smooth-K
+static int attn8_pack_run(const char* who, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                          int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim, const float* k_shift,
+                          void* stream) {
   FX_REQUIRE(v && q8 && qs && kv8 && ((q == nullptr) == (k == nullptr)), FLEXAM_E_ARG, "attn_fp8_pack: null pointer (q and k: both or neither)");
   FX_REQUIRE(head_dim == HD && B > 0 && H > 0 && L > 0, FLEXAM_E_SHAPE, "attn_fp8_pack: bad sizes (head_dim 128 only)");
   FX_REQUIRE(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0, FLEXAM_E_SHAPE,
              "attn_fp8_pack: strides must keep 16-byte alignment of head rows");
-  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG,
+  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8 | (uintptr_t)k_shift) % 16 == 0, FLEXAM_E_ARG,
              "attn_fp8_pack: misaligned pointer");
   Attn8Pack a;
   a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v;
   a.q_bs = q_bs; a.q_rs = q_rs; a.k_bs = k_bs; a.k_rs = k_rs; a.v_bs = v_bs; a.v_rs = v_rs;
   a.q8 = (unsigned char*)q8; a.qs = (unsigned char*)qs; a.kv8 = (unsigned char*)kv8;
-  a.H = H; a.L = L; a.lq_pad = (L + QBLK - 1) / QBLK * QBLK; a.tiles = (L + KVBLK - 1) / KVBLK;
-  hipLaunchKernelGGL(attn8_pack_kernel, dim3(a.lq_pad / KVBLK, H, B), dim3(256), 0, (hipStream_t)stream, a);
-  return flexam_check_launch("flexam_attn_fp8_pack");
+  a.H = H; a.L = L; a.lq_pad = (L + QBLK - 1) / QBLK * QBLK; a.tiles = (L + KVBLK - 1) / KVBLK; a.k_shift = k_shift;
+  const dim3 grid(a.lq_pad / KVBLK, H, B);
+  if (k_shift) hipLaunchKernelGGL(attn8_pack_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(attn8_pack_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return flexam_check_launch(who);
+}
+
+extern "C" int flexam_attn_fp8_pack(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                    int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
+                                    void* stream) {
+  return attn8_pack_run("flexam_attn_fp8_pack", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, nullptr, stream);
+}
+
+extern "C" int flexam_attn_fp8_pack_shift(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                          int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
+                                          const float* k_shift, void* stream) {
+  FX_REQUIRE(k_shift && k, FLEXAM_E_ARG, "attn_fp8_pack_shift: null pointer (the shift needs its k)");
+  return attn8_pack_run("flexam_attn_fp8_pack_shift", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, k_shift, stream);
+}
+
+static int rmsnorm_rope_mx_run(const char* who, const void* q, int64_t ldq, const float* wq, const void* k, int64_t ldk, const float* wk, void* q8,
+                               void* qs, void* kv8, int64_t M, int C, float eps, const float* rope_cos, const float* rope_sin,
+                               int64_t tokens_per_batch, int64_t token_offset, int H, int head_dim, const float* k_shift, void* stream) {
+  FX_REQUIRE(q && k && wq && wk && q8 && qs && kv8 && rope_cos && rope_sin, FLEXAM_E_ARG, "rmsnorm_rope_mx: null pointer");
+  FX_REQUIRE(head_dim == HD && H == 24 && C == H * HD, FLEXAM_E_SHAPE, "rmsnorm_rope_mx: 24 heads of 128 channels only (C = %d, H = %d)", C, H);
+  FX_REQUIRE(M > 0 && tokens_per_batch > 0 && M % tokens_per_batch == 0 && ldq % 8 == 0 && ldk % 8 == 0, FLEXAM_E_SHAPE, "rmsnorm_rope_mx: bad sizes");
+  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8 | (uintptr_t)k_shift) % 16 == 0, FLEXAM_E_ARG, "rmsnorm_rope_mx: misaligned pointer");
+  RmsRopeMx a;
+  a.q = (const bf16*)q; a.k = (const bf16*)k; a.ldq = ldq; a.ldk = ldk; a.wq = wq; a.wk = wk; a.cs = rope_cos; a.sn = rope_sin;
+  a.q8 = (unsigned char*)q8; a.qs = (unsigned char*)qs; a.kv8 = (unsigned char*)kv8;
+  a.tokens_per_batch = tokens_per_batch; a.token_offset = token_offset; a.H = H; a.L = (int)tokens_per_batch;
+  a.lq_pad = (a.L + QBLK - 1) / QBLK * QBLK; a.tiles = (a.L + KVBLK - 1) / KVBLK; a.eps = eps; a.k_shift = k_shift;
+  // with a shift: the Q half by the plain instance (blockIdx.y = 0 only: its bytes are those of the plain call), the K half by the SHIFT one
+  hipLaunchKernelGGL(rmsnorm_rope_mx_kernel<false>, dim3((unsigned)M, k_shift ? 1 : 2), dim3(128), 0, (hipStream_t)stream, a);
+  if (k_shift) hipLaunchKernelGGL(rmsnorm_rope_mx_kernel<true>, dim3((unsigned)M, 1), dim3(128), 0, (hipStream_t)stream, a);
+  return flexam_check_launch(who);
 }
 
 extern "C" int flexam_rmsnorm_rope_mx(const void* q, int64_t ldq, const float* wq, const void* k, int64_t ldk, const float* wk, void* q8,
                                       void* qs, void* kv8, int64_t M, int C, float eps, const float* rope_cos, const float* rope_sin,
                                       int64_t tokens_per_batch, int64_t token_offset, int H, int head_dim, void* stream) {
-  FX_REQUIRE(q && k && wq && wk && q8 && qs && kv8 && rope_cos && rope_sin, FLEXAM_E_ARG, "rmsnorm_rope_mx: null pointer");
-  FX_REQUIRE(head_dim == HD && H == 24 && C == H * HD, FLEXAM_E_SHAPE, "rmsnorm_rope_mx: 24 heads of 128 channels only (C = %d, H = %d)", C, H);
-  FX_REQUIRE(M > 0 && tokens_per_batch > 0 && M % tokens_per_batch == 0 && ldq % 8 == 0 && ldk % 8 == 0, FLEXAM_E_SHAPE, "rmsnorm_rope_mx: bad sizes");
-  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG, "rmsnorm_rope_mx: misaligned pointer");
-  RmsRopeMx a;
-  a.q = (const bf16*)q; a.k = (const bf16*)k; a.ldq = ldq; a.ldk = ldk; a.wq = wq; a.wk = wk; a.cs = rope_cos; a.sn = rope_sin;
-  a.q8 = (unsigned char*)q8; a.qs = (unsigned char*)qs; a.kv8 = (unsigned char*)kv8;
-  a.tokens_per_batch = tokens_per_batch; a.token_offset = token_offset; a.H = H; a.L = (int)tokens_per_batch;
-  a.lq_pad = (a.L + QBLK - 1) / QBLK * QBLK; a.tiles = (a.L + KVBLK - 1) / KVBLK; a.eps = eps;
-  hipLaunchKernelGGL(rmsnorm_rope_mx_kernel, dim3((unsigned)M, 2), dim3(128), 0, (hipStream_t)stream, a);
-  return flexam_check_launch("flexam_rmsnorm_rope_mx");
+  return rmsnorm_rope_mx_run("flexam_rmsnorm_rope_mx", q, ldq, wq, k, ldk, wk, q8, qs, kv8, M, C, eps, rope_cos, rope_sin, tokens_per_batch,
+                             token_offset, H, head_dim, nullptr, stream);
+}
+
+extern "C" int flexam_rmsnorm_rope_mx_shift(const void* q, int64_t ldq, const float* wq, const void* k, int64_t ldk, const float* wk, void* q8,
+                                            void* qs, void* kv8, int64_t M, int C, float eps, const float* rope_cos, const float* rope_sin,
+                                            int64_t tokens_per_batch, int64_t token_offset, int H, int head_dim, const float* k_shift,
+                                            void* stream) {
+  FX_REQUIRE(k_shift, FLEXAM_E_ARG, "rmsnorm_rope_mx_shift: null shift");
+  return rmsnorm_rope_mx_run("flexam_rmsnorm_rope_mx_shift", q, ldq, wq, k, ldk, wk, q8, qs, kv8, M, C, eps, rope_cos, rope_sin,
+                             tokens_per_batch, token_offset, H, head_dim, k_shift, stream);
+}
+
+extern "C" int flexam_k_mean(const void* k, int64_t ldk, const float* wk, int64_t M, int C, float eps, const float* rope_cos,
+                             const float* rope_sin, int64_t tokens_per_batch, int64_t token_offset, int head_dim, int parts, float* partial,
+                             float* mean, void* stream) {
+  FX_REQUIRE(k && partial && mean, FLEXAM_E_ARG, "k_mean: null pointer");
+  FX_REQUIRE(!wk || (rope_cos && rope_sin && head_dim == HD && C % HD == 0), FLEXAM_E_ARG,
+             "k_mean: with a norm weight the RoPE tables are mandatory and heads are 128 channels (head_dim = %d, C = %d)", head_dim, C);
+  FX_REQUIRE(M > 0 && tokens_per_batch > 0 && tokens_per_batch < (1 << 30) && M % tokens_per_batch == 0 && M / tokens_per_batch <= 65535 && C > 0 &&
+                 C % 8 == 0 && ldk % 8 == 0 && ldk >= C && parts >= 1 && parts <= 65535 && parts <= tokens_per_batch,
+             FLEXAM_E_SHAPE, "k_mean: bad sizes (M = %lld, tokens_per_batch = %lld, C = %d, ldk = %lld, parts = %d)", (long long)M,
+             (long long)tokens_per_batch, C, (long long)ldk, parts);
+  FX_REQUIRE(C <= (wk ? 3072 : 5120), FLEXAM_E_SHAPE, "k_mean: at most %d channels (C = %d)", wk ? 3072 : 5120, C);
+  FX_REQUIRE(((uintptr_t)k | (uintptr_t)wk | (uintptr_t)partial | (uintptr_t)mean | (uintptr_t)rope_cos | (uintptr_t)rope_sin) % 16 == 0, FLEXAM_E_ARG,
+             "k_mean: misaligned pointer");
+  KMean a;
+  a.k = (const bf16*)k; a.ldk = ldk; a.token_offset = token_offset; a.wk = wk; a.cs = rope_cos; a.sn = rope_sin; a.partial = partial; a.mean = mean;
+  a.C = C; a.L = (int)tokens_per_batch; a.parts = parts; a.tpp = (a.L + parts - 1) / parts; a.eps = eps; a.inv_l = 1.0f / (float)a.L;
+  const int B = (int)(M / tokens_per_batch), vpt = (C / 8 + 63) / 64;
+  const dim3 grid(parts, B);
+#define K_MEAN_LAUNCH(V, N) hipLaunchKernelGGL((k_mean_part_kernel<V, N>), grid, dim3(64), 0, (hipStream_t)stream, a)
+  if (wk) {
+    if (vpt <= 1) K_MEAN_LAUNCH(1, true); else if (vpt <= 2) K_MEAN_LAUNCH(2, true); else if (vpt <= 4) K_MEAN_LAUNCH(4, true); else K_MEAN_LAUNCH(6, true);
+  } else {
+    if (vpt <= 1) K_MEAN_LAUNCH(1, false); else if (vpt <= 2) K_MEAN_LAUNCH(2, false); else if (vpt <= 4) K_MEAN_LAUNCH(4, false);
+    else if (vpt <= 6) K_MEAN_LAUNCH(6, false); else K_MEAN_LAUNCH(10, false);
+  }
+#undef K_MEAN_LAUNCH
+  hipLaunchKernelGGL(k_mean_finish_kernel, dim3((B * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, a, B);
+  return flexam_check_launch("flexam_k_mean");
 }
 
 extern "C" int flexam_attn_fwd_fp8(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,

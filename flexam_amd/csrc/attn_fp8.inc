@@ -322,6 +322,7 @@ struct Attn8Pack {
   unsigned char* qs;      // [B][H][lq_pad][4] E8M0 bytes (read as one dword per row by the attention kernel)
   unsigned char* kv8;
   int H, L, lq_pad, tiles;
+  const float* k_shift;   // SHIFT instance only (flexam_attn_fp8_pack_shift): fp32 [B][H * 128], subtracted from K before it is quantised
 };
 
 // smallest power of two 2^e with amax * 2^-e <= 448 (the largest e4m3 number): returns the E8M0 byte e + 127 and 2^-e
@@ -333,6 +334,7 @@ __device__ __forceinline__ unsigned mx_scale(float amax, float& inv) {
   return (unsigned)e;
 }
 
+template <bool SHIFT>
 __global__ __launch_bounds__(256) void attn8_pack_kernel(Attn8Pack a) {
   __shared__ __attribute__((aligned(16))) bf16 vt[64 * 128];
   const int tid = threadIdx.x, tile = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -364,6 +366,17 @@ __global__ __launch_bounds__(256) void attn8_pack_kernel(Attn8Pack a) {
           const bf16x8 v8 = *(const bf16x8*)(src + head * HD + 32 * blk + 8 * c);
 #pragma unroll
           for (int j = 0; j < 8; ++j) x[8 * c + j] = bf2f(v8[j]);
+        }
+        if constexpr (SHIFT) {
+          if (which == 0) {                              // smooth-K: k - shift in fp32, one rounding; rows past L stay zero rows
+            const float* sh = a.k_shift + bh * HD + 32 * blk;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+              const f32x4 s4 = *(const f32x4*)(sh + 4 * c);
+#pragma unroll
+              for (int j = 0; j < 4; ++j) x[4 * c + j] -= s4[j];
+            }
+          }
         }
       } else {
 #pragma unroll
@@ -437,12 +450,15 @@ struct RmsRopeMx {
   int64_t tokens_per_batch, token_offset;
   int H, L, lq_pad, tiles;
   float eps;
+  const float* k_shift;   // SHIFT instance only (flexam_rmsnorm_rope_mx_shift): fp32 [B][3072], subtracted from the rotated K in fp32.  That
+                          // instance writes the K half alone; the Q half of a shifted call is a launch of the plain instance: the same bytes
 };
 
+template <bool SHIFT>
 __global__ __launch_bounds__(128) void rmsnorm_rope_mx_kernel(RmsRopeMx a) {
   __shared__ float red[8];
   constexpr int VPT = 3, C = 24 * HD;                 // 3072 channels = 24 heads
-  const int which = blockIdx.y;                       // 0: q, 1: k
+  const int which = SHIFT ? 1 : blockIdx.y;           // 0: q, 1: k (the SHIFT instance is launched for k alone)
   const int64_t m = blockIdx.x;
   const bf16* xr = which == 0 ? a.q + m * a.ldq : a.k + m * a.ldk;
   const float* w = which == 0 ? a.wq : a.wk;
@@ -477,6 +493,14 @@ __global__ __launch_bounds__(128) void rmsnorm_rope_mx_kernel(RmsRopeMx a) {
       y[2 * j] = re * co[j] - im * si[j];
       y[2 * j + 1] = re * si[j] + im * co[j];
     }
+    if constexpr (SHIFT) {                              // smooth-K: behind the rotation, in front of the block amax
+      const f32x4 s0 = *(const f32x4*)(a.k_shift + (int64_t)b * C + c), s1 = *(const f32x4*)(a.k_shift + (int64_t)b * C + c + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        y[j] -= s0[j];
+        y[4 + j] -= s1[j];
+      }
+    }
     float amax = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(y[j]));
@@ -501,4 +525,113 @@ __global__ __launch_bounds__(128) void rmsnorm_rope_mx_kernel(RmsRopeMx a) {
       if ((threadIdx.x & 3) == 0) rec[REC_KS + 4 * row + blk] = (unsigned char)sb;
     }
   }
+}
+
+// ---- smooth-K (SageAttention's preprocessing of K): the mean over the tokens of K as the attention will see it, per (batch, channel).
+// softmax(q.(k_j - c)) = softmax(q.k_j - q.c) = softmax(q.k_j) for ANY c, since q.c is one number per query row: subtracting the mean
+// changes no output, only what e4m3 has to resolve -- a channel offset shared by all keys otherwise costs every score its relative error.
+// NORM: k is the projection's output and RMSNorm over the full row + RoPE come first (flexam_rmsnorm_rope's arithmetic: the fused
+// producer above never materialises that K); otherwise k is taken as given.
+// Deterministic, whatever the device: no atomics, no CU count.  ONE wave per (part, batch) sums the rows of ceil(L / parts) consecutive
+// tokens in token order in fp32 -- lane l holds channels 8 (l + 64 i) .. +7, i < VPT, so the sum of squares of a row is a wave
+// reduction (no LDS, no barrier) -- into partial[b][part][:]; k_mean_finish_kernel adds the parts in index order and multiplies by 1 / L.
+// The next token's row is loaded in front of the work on this one (past the end: the last row once more).
+struct KMean {
+  const bf16* k;
+  int64_t ldk, token_offset;
+  const float *wk, *cs, *sn;
+  float *partial, *mean;
+  int C, L, parts, tpp;      // tpp = ceil(L / parts) tokens per part
+  float eps, inv_l;
+};
+
+template <int VPT, bool NORM>
+__global__ __launch_bounds__(64) void k_mean_part_kernel(KMean a) {
+  const int lane = threadIdx.x, part = blockIdx.x, b = blockIdx.y;
+  const int nvec = a.C >> 3;
+  const int t0 = min(part * a.tpp, a.L), t1 = min(t0 + a.tpp, a.L);
+  const bf16* rows = a.k + (int64_t)b * a.L * a.ldk;
+  float acc[VPT][8];
+  float w[NORM ? VPT : 1][8];
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[i][j] = 0.f;
+    if constexpr (NORM) {
+      const int vec = min(lane + 64 * i, nvec - 1);
+      const f32x4 w0 = *(const f32x4*)(a.wk + vec * 8), w1 = *(const f32x4*)(a.wk + vec * 8 + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        w[i][j] = w0[j];
+        w[i][4 + j] = w1[j];
+      }
+    }
+  }
+  auto load_row = [&](int t, bf16x8 (&v)[VPT]) {
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const int vec = lane + 64 * i;
+      v[i] = (bf16x8){0, 0, 0, 0, 0, 0, 0, 0};
+      if (vec < nvec) v[i] = *(const bf16x8*)(rows + (int64_t)t * a.ldk + vec * 8);
+    }
+  };
+  bf16x8 cur[VPT], nxt[VPT];
+  if (t0 < t1) load_row(t0, cur);
+  for (int t = t0; t < t1; ++t) {
+    load_row(min(t + 1, t1 - 1), nxt);
+    if constexpr (NORM) {
+      const int64_t tok = a.token_offset + t;
+      const int pair0 = (lane * 8 & (HD - 1)) >> 1;     // 64 lanes x 8 channels = 4 heads: the same 4 pairs of a head for every i
+      const f32x4 co = *(const f32x4*)(a.cs + tok * (HD / 2) + pair0), si = *(const f32x4*)(a.sn + tok * (HD / 2) + pair0);
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < VPT; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float f = bf2f(cur[i][j]);
+          ss += f * f;
+        }
+      const float rn = __builtin_amdgcn_rsqf(wave_sum(ss) / (float)a.C + a.eps);
+#pragma unroll
+      for (int i = 0; i < VPT; ++i) {
+        float y[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) y[j] = bf2f(cur[i][j]) * rn * w[i][j];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float re = y[2 * j], im = y[2 * j + 1];
+          acc[i][2 * j] += re * co[j] - im * si[j];
+          acc[i][2 * j + 1] += re * si[j] + im * co[j];
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < VPT; ++i)
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[i][j] += bf2f(cur[i][j]);
+    }
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) cur[i] = nxt[i];
+  }
+  float* dst = a.partial + ((int64_t)b * a.parts + part) * a.C;
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    const int vec = lane + 64 * i;
+    if (vec < nvec) {
+      *(f32x4*)(dst + vec * 8) = (f32x4){acc[i][0], acc[i][1], acc[i][2], acc[i][3]};
+      *(f32x4*)(dst + vec * 8 + 4) = (f32x4){acc[i][4], acc[i][5], acc[i][6], acc[i][7]};
+    }
+  }
+}
+
+// thread = (batch, channel): the parts in index order (the loads do not depend on the sum: unrolled, they are all in flight together)
+__global__ __launch_bounds__(256) void k_mean_finish_kernel(KMean a, int B) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= B * a.C) return;
+  const int b = idx / a.C, c = idx - b * a.C;
+  const float* src = a.partial + (int64_t)b * a.parts * a.C + c;
+  float s = 0.f;
+#pragma unroll 16
+  for (int p = 0; p < a.parts; ++p) s += src[(int64_t)p * a.C];
+  a.mean[idx] = s * a.inv_l;
 }

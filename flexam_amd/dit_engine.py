@@ -26,7 +26,7 @@ from typing import List, Optional
 import torch
 
 from . import hip
-from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked
+from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, smooth_k_asked
 from .dit_sp import HeadAllToAll, KVGather, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
@@ -69,6 +69,7 @@ def _proj_fp8(h: torch.Tensor, pk: dict, wname: str, bias, epilogue: int = 0) ->
 
 class DiTEngine:
     _sage_warned = False
+    _smooth_k_warned = False
 
     def __init__(self, model):
         self.model = model
@@ -96,6 +97,8 @@ class DiTEngine:
         self.cfg_size, self.cfg_row = 1, 0          # cfg_size 2: this rank computes only CFG row `cfg_row`
         self._ws = {}
         self._attn8 = {}                            # MXFP8 operand buffers of the quantised self-attention (_attn8_buffers)
+        self._kmean = {}                            # smooth-K: K's token mean and the scratch of its parts (_k_mean_buffers)
+        self._smooth_k = self.sage_smooth_taken = False
         self._ws_gen = 0                            # bumped whenever the activation buffers are dropped: recorded launch plans name their addresses
         self._angles = None
         self.cond = None
@@ -347,6 +350,17 @@ class DiTEngine:
             cache[(nb, lc, heads)] = hip.attn_fp8_buffers(nb, heads, lc, self.device)      # (block 0 may run one sample: its own set, not a re-allocation per step)
         return cache[(nb, lc, heads)]
 
+    def _k_mean_buffers(self, nb, lc):
+        """(mean fp32 [nb, dim], scratch fp32 [nb, parts, dim]) of hip.k_mean under FLEXAM_SAGE_SMOOTH_K, cached as _attn8_buffers caches
+        the operands: one set per (samples, heads), block 0's one-sample run under share0 its own."""
+        cache = self._kmean
+        if (nb, lc, self.nh) not in cache:
+            if any(k[1:] != (lc, self.nh) for k in cache):
+                cache.clear()
+            cache[(nb, lc, self.nh)] = (torch.empty(nb, self.dim, device=self.device, dtype=F32),
+                                        torch.empty(nb, hip.k_mean_parts(lc), self.dim, device=self.device, dtype=F32))
+        return cache[(nb, lc, self.nh)]
+
     # ------------------------------------------------------------------ per-step
     def embed_time(self, t_rows: torch.Tensor):
         """t_rows [R] fp32 distinct timesteps -> e [R, d], e0 [R, 6, d] (fp32, FX.py:928-944)."""
@@ -377,6 +391,16 @@ class DiTEngine:
             warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored " +
                           "under sequence parallelism with the OVERLAPPED K|V all-gather (FLEXAM_SP_OVERLAP=1 / head-group pieces) or an all-to-all "
                           "over a padded sequence: self-attention runs the bf16 kernel", RuntimeWarning, stacklevel=3)
+        # FLEXAM_SAGE_SMOOTH_K=1 (default 0): the quantised self-attention quantises K - mean_tokens(K) (csrc/attn_fp8.inc).  Kept beside
+        # the mode, not in it, and part of a launch plan's key.  One rank only: under the record gather each rank would shift ITS keys by
+        # ITS mean, which is not exact (the all-to-all over heads could do it exactly and does not yet)
+        asked = smooth_k_asked(env)
+        self._smooth_k = bool(m.sage and m.sp == 1 and asked)
+        if asked and m.sage and m.sp > 1 and not DiTEngine._smooth_k_warned:       # said once per process
+            DiTEngine._smooth_k_warned = True
+            import warnings
+            warnings.warn("flexam_amd: FLEXAM_SAGE_SMOOTH_K=1 is ignored under sequence parallelism: K is quantised as it is",
+                          RuntimeWarning, stacklevel=3)
         return m
 
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
@@ -416,6 +440,7 @@ class DiTEngine:
             if m.sp > 1:
                 xr[b].copy_(full[m.tok0:m.tok0 + lc])
         self.share0_taken, self.sage_taken = m.share0, m.sage          # what this forward DID (bench.py labels its line from them)
+        self.sage_smooth_taken = self._smooth_k
         if not m.share0:
             for b in range(bx, B):
                 xr[b].copy_(xr[0])
@@ -488,7 +513,7 @@ class DiTEngine:
         address they carry.  Not with TeaCache (data-dependent skipping), per-layer tables or blocks called as modules (_Mode.use_plan)."""
         cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
         key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
-               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group))
+               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), self._smooth_k)
         plans = cd.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -546,18 +571,26 @@ class DiTEngine:
     def _norm_rope_qk(self, p, m, ws, nb, bufs=None):
         """RMSNorm + RoPE of q and k of the first nb samples at this chunk's token offset.  With bufs (SAGE_ATTENTION) q, k and v become
         the MXFP8 operands of the quantised attention (csrc/attn_fp8.inc): at the 5B model's 24 heads (sage_fused) the RMSNorm + RoPE
-        launch writes Q and K as operands directly and V is packed on its own; otherwise q and k are normed in bf16 and all three packed."""
+        launch writes Q and K as operands directly and V is packed on its own; otherwise q and k are normed in bf16 and all three packed.
+        Smooth-K (FLEXAM_SAGE_SMOOTH_K, _mode): one more pass over k, the token mean of the normed and rotated K (hip.k_mean: computed
+        from the raw k in the fused form, which never writes that K), is what the producer subtracts before it quantises K."""
         d, rows, cd = self.dim, nb * m.lc, self.cond
         q, k = ws["qkv"][:rows, 0:d], ws["qkv"][:rows, d:2 * d]
         q4, k4, v4, _ = self._heads(m, ws)
+        smooth = bufs is not None and self._smooth_k
+        mean, scratch = self._k_mean_buffers(nb, m.lc) if smooth else (None, None)
         if bufs is not None and m.sage_fused:
-            hip.rmsnorm_rope_mx(q, p["nq"], k, p["nk"], bufs, cd["cos"], cd["sin"], m.lc, m.tok0, eps=self.eps)
+            if smooth:
+                hip.k_mean(k, p["nk"], cd["cos"], cd["sin"], m.lc, m.tok0, eps=self.eps, head_dim=self.hd, out=mean, scratch=scratch)
+            hip.rmsnorm_rope_mx(q, p["nq"], k, p["nk"], bufs, cd["cos"], cd["sin"], m.lc, m.tok0, eps=self.eps, k_shift=mean)
             hip.attn_fp8_pack(None, None, v4[:nb], bufs)
             return
         hip.rmsnorm_rope(q, p["nq"], k, p["nk"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=m.lc,
                          token_offset=m.tok0, head_dim=self.hd)
+        if smooth:
+            hip.k_mean(k, None, None, None, m.lc, out=mean, scratch=scratch)
         if bufs is not None:
-            hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs)
+            hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs, k_shift=mean)
 
     def _self_attention(self, i, p, T, m, ws, ex=None):
         """LN + modulate -> q|k|v -> self-attention in this forward's layout (one rank, all-to-all over heads or K|V all-gather) ->

@@ -91,6 +91,12 @@ def sage_asked(env) -> bool:
     return env.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION"
 
 
+def smooth_k_asked(env) -> bool:
+    """FLEXAM_SAGE_SMOOTH_K=1 (default 0): quantise K - mean_tokens(K) in the MXFP8 self-attention.  Not a field of _Mode: DiTEngine._mode
+    keeps it beside the mode (it holds for `sage and sp == 1` only) and keys its launch plans on it."""
+    return env.get("FLEXAM_SAGE_SMOOTH_K", "0") == "1"
+
+
 def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, parallel: Parallel, B, L, dens_same,
                  bx, R, rows_per_batch, only_row, rows_shared, teacache: bool) -> _Mode:
     """The mode of one forward.  env: the environment mapping; fused .. parallel: the engine (all blocks native, layers, heads, head

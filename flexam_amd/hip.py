@@ -588,8 +588,56 @@ def _check_fp8_bufs(bufs, B, H, L, device, who):
                                f"on {t.device}, want {shape} {dt}")
 
 
-def attn_fp8_pack(q, k, v, bufs=None):
-    """q, k, v [B, L, H, 128] bf16 (q prescaled by softmax_scale * log2 e) -> the MXFP8 operand buffers of attn_fwd_fp8."""
+def _k_shift(who, k_shift, B, C, device):
+    """The smooth-K shift of the shifted producers: contiguous fp32 [B, C] on the operands' device (see flexam_hip.h)."""
+    if tuple(k_shift.shape) != (B, C) or k_shift.dtype != F32 or not k_shift.is_contiguous() or k_shift.device != torch.device(device):
+        raise RuntimeError(f"{who}: k_shift must be contiguous float32 [B={B}, {C}] on {device}, got {tuple(k_shift.shape)} {k_shift.dtype} "
+                           f"on {k_shift.device}")
+    return _ptr(k_shift, F32)
+
+
+def k_mean_parts(tokens_per_batch):
+    """The parts k_mean cuts a batch's tokens into: a function of the token count alone (never of the device), so that equal inputs give
+    equal bits everywhere.  16 tokens per part, at most 512 parts: one wave per part and batch."""
+    return max(1, min(-(-tokens_per_batch // 16), 512))
+
+
+def k_mean(k, wk, rope_cos, rope_sin, tokens_per_batch, token_offset=0, eps=1e-6, head_dim=128, out=None, scratch=None):
+    """mean over the tokens of K as the attention will see it -> out fp32 [B, C] (flexam_k_mean): k [M, C] bf16 rows, M = B *
+    tokens_per_batch; with wk, RMSNorm over the row + RoPE (rmsnorm_rope's arithmetic, unrounded) are applied first, with wk None k is
+    taken as given.  scratch: fp32 [B, parts, C], its second size IS the number of parts (default: k_mean_parts(tokens_per_batch))."""
+    M, C, ldk = _rows(k)
+    if tokens_per_batch <= 0 or M % tokens_per_batch:
+        raise RuntimeError(f"k_mean: {M} rows do not tile batches of {tokens_per_batch} tokens")
+    B = M // tokens_per_batch
+    if wk is not None:
+        if rope_cos is None or rope_sin is None or head_dim != ATTN_HEAD_DIM or C % head_dim:
+            raise RuntimeError(f"k_mean: with a norm weight the RoPE tables are mandatory and heads are {ATTN_HEAD_DIM} channels")
+        if wk.numel() != C or not wk.is_contiguous():
+            raise RuntimeError(f"k_mean: the norm weight must be contiguous float32 [{C}]")
+        for t in (rope_cos, rope_sin):
+            if t.dim() != 2 or t.shape[1] != head_dim // 2 or not t.is_contiguous() or t.shape[0] < token_offset + tokens_per_batch:
+                raise RuntimeError(f"k_mean: RoPE tables must be contiguous float32 [>= {token_offset + tokens_per_batch}, {head_dim // 2}], "
+                                   f"got {tuple(t.shape)}")
+    if scratch is None:
+        scratch = torch.empty(B, k_mean_parts(tokens_per_batch), C, device=k.device, dtype=F32)
+    if (scratch.dim() != 3 or scratch.shape[0] != B or scratch.shape[2] != C or not 1 <= scratch.shape[1] <= tokens_per_batch
+            or scratch.dtype != F32 or not scratch.is_contiguous() or scratch.device != k.device):
+        raise RuntimeError(f"k_mean: scratch must be contiguous float32 [B={B}, 1 <= parts <= {tokens_per_batch}, {C}] on {k.device}, got "
+                           f"{tuple(scratch.shape)} {scratch.dtype}")
+    if out is None:
+        out = torch.empty(B, C, device=k.device, dtype=F32)
+    if tuple(out.shape) != (B, C) or out.dtype != F32 or not out.is_contiguous() or out.device != k.device:
+        raise RuntimeError(f"k_mean: out must be contiguous float32 [B={B}, {C}] on {k.device}, got {tuple(out.shape)} {out.dtype}")
+    norm = wk is not None
+    _call("flexam_k_mean", _ptr(k, BF16), ldk, _ptr(wk, F32), M, C, eps, _ptr(rope_cos if norm else None, F32),
+          _ptr(rope_sin if norm else None, F32), tokens_per_batch, token_offset, head_dim, scratch.shape[1], _ptr(scratch, F32), _ptr(out, F32))
+    return out
+
+
+def attn_fp8_pack(q, k, v, bufs=None, k_shift=None):
+    """q, k, v [B, L, H, 128] bf16 (q prescaled by softmax_scale * log2 e) -> the MXFP8 operand buffers of attn_fwd_fp8.  k_shift
+    (smooth-K, fp32 [B, H * 128]): K is quantised from float(k) - k_shift (flexam_attn_fp8_pack_shift)."""
     B, L, H, D = v.shape
     if any(t is not None and t.shape != v.shape for t in (q, k)):
         raise RuntimeError(f"attn_fp8_pack: q, k, v must be [B, L, H, {ATTN_HEAD_DIM}], all of one shape")
@@ -601,22 +649,32 @@ def attn_fp8_pack(q, k, v, bufs=None):
     _check_fp8_bufs(bufs, B, H, L, v.device, "attn_fp8_pack")
     q8, qs, kv8 = bufs
     qk = (lambda t: (t.stride(0), t.stride(1))) if q is not None else (lambda t: (0, 0))
-    _call("flexam_attn_fp8_pack", _ptr(q, BF16), *qk(q), _ptr(k, BF16), *qk(k), _ptr(v, BF16), v.stride(0), v.stride(1), _raw(q8), _raw(qs),
-          _raw(kv8), B, H, L, D)
+    args = (_ptr(q, BF16), *qk(q), _ptr(k, BF16), *qk(k), _ptr(v, BF16), v.stride(0), v.stride(1), _raw(q8), _raw(qs), _raw(kv8), B, H, L, D)
+    if k_shift is None:
+        _call("flexam_attn_fp8_pack", *args)
+    else:
+        if k is None:
+            raise RuntimeError("attn_fp8_pack: k_shift needs its k")
+        _call("flexam_attn_fp8_pack_shift", *args, _k_shift("attn_fp8_pack", k_shift, B, H * D, v.device))
     return bufs
 
 
-def rmsnorm_rope_mx(q, wq, k, wk, bufs, rope_cos, rope_sin, tokens_per_batch, token_offset=0, eps=1e-6, heads=24):
+def rmsnorm_rope_mx(q, wq, k, wk, bufs, rope_cos, rope_sin, tokens_per_batch, token_offset=0, eps=1e-6, heads=24, k_shift=None):
     """RMSNorm + RoPE of q and k ([M, 3072] bf16 views) written as the MXFP8 operands of attn_fwd_fp8 (Q rows, K image and scales);
-    the V half of `bufs` comes from attn_fp8_pack(None, None, v, bufs)."""
+    the V half of `bufs` comes from attn_fp8_pack(None, None, v, bufs).  k_shift (smooth-K, fp32 [B, 3072]): the K half is that of
+    k - k_shift, subtracted behind the rotation (flexam_rmsnorm_rope_mx_shift)."""
     M, C, ldq = _rows(q)
     if tokens_per_batch <= 0 or M % tokens_per_batch or C != heads * ATTN_HEAD_DIM:
         raise RuntimeError(f"rmsnorm_rope_mx: {M} rows of {C} columns do not tile batches of {tokens_per_batch} tokens x {heads} heads x "
                            f"{ATTN_HEAD_DIM}")
     _check_fp8_bufs(bufs, M // tokens_per_batch, heads, tokens_per_batch, q.device, "rmsnorm_rope_mx")
     q8, qs, kv8 = bufs
-    _call("flexam_rmsnorm_rope_mx", _ptr(q, BF16), ldq, _ptr(wq, F32), _ptr(k, BF16), k.stride(0), _ptr(wk, F32), _raw(q8), _raw(qs),
-          _raw(kv8), M, C, eps, _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, heads, ATTN_HEAD_DIM)
+    args = (_ptr(q, BF16), ldq, _ptr(wq, F32), _ptr(k, BF16), k.stride(0), _ptr(wk, F32), _raw(q8), _raw(qs), _raw(kv8), M, C, eps,
+            _ptr(rope_cos, F32), _ptr(rope_sin, F32), tokens_per_batch, token_offset, heads, ATTN_HEAD_DIM)
+    if k_shift is None:
+        _call("flexam_rmsnorm_rope_mx", *args)
+    else:
+        _call("flexam_rmsnorm_rope_mx_shift", *args, _k_shift("rmsnorm_rope_mx", k_shift, M // tokens_per_batch, C, q.device))
     return bufs
 
 

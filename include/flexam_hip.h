@@ -182,6 +182,32 @@ int flexam_attn_fp8_pack(const void* q, int64_t q_bs, int64_t q_rs, const void* 
 int flexam_rmsnorm_rope_mx(const void* q, int64_t ldq, const float* wq, const void* k, int64_t ldk, const float* wk, void* q8, void* qs,
                            void* kv8, int64_t M, int C, float eps, const float* rope_cos, const float* rope_sin,
                            int64_t tokens_per_batch, int64_t token_offset, int H, int head_dim, void* stream);
+/* Smooth-K, SageAttention's preprocessing of K: the producers above with k_shift[b][c] (fp32 [B][H * 128], taken as given) subtracted
+ * from K before it is quantised.  softmax(q.(k_j - c)) = softmax(q.k_j - q.c) = softmax(q.k_j) for ANY vector c, q.c being one number
+ * per query row: the attention's result is that of the unshifted K, while e4m3 -- whose error is relative to the element -- no longer
+ * pays for a channel offset all keys share in every score.  With k_shift = the token mean (flexam_k_mean) the operands are those of
+ * K - mean_tokens(K); flexam_attn_fwd_fp8 is unchanged and cannot tell.
+ * flexam_attn_fp8_pack_shift: K rows below L are quantised from float(k) - k_shift[b][h * 128 + c], one fp32 subtraction; rows past L
+ * stay zero rows (codes 0, scale byte 1), not -shift; Q and V as flexam_attn_fp8_pack writes them (q and k must be given).
+ * flexam_rmsnorm_rope_mx_shift: the K half writes the operands of y - k_shift[b][c], subtracted in fp32 after the rotation and before
+ * the block amax (one more rounding than flexam_rmsnorm_rope_mx); the Q half is flexam_rmsnorm_rope_mx's, byte for byte (its own launch). */
+int flexam_attn_fp8_pack_shift(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                               int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
+                               const float* k_shift, void* stream);
+int flexam_rmsnorm_rope_mx_shift(const void* q, int64_t ldq, const float* wq, const void* k, int64_t ldk, const float* wk, void* q8,
+                                 void* qs, void* kv8, int64_t M, int C, float eps, const float* rope_cos, const float* rope_sin,
+                                 int64_t tokens_per_batch, int64_t token_offset, int H, int head_dim, const float* k_shift, void* stream);
+/* mean[b][c] (fp32 [B][C]) = the mean over the tokens_per_batch tokens of batch b of K as the attention will see it; k: M = B *
+ * tokens_per_batch bf16 rows of C channels, row pitch ldk.  wk != NULL: RMSNorm over the full row + RoPE are applied first --
+ * flexam_rmsnorm_rope's arithmetic in fp32, unrounded, with this eps, these tables and token(m) = token_offset + m % tokens_per_batch
+ * (head_dim 128, C <= 3072): the K flexam_rmsnorm_rope_mx quantises and never writes.  wk == NULL: k is taken as given, already
+ * normed and rotated (C <= 5120; rope_cos / rope_sin / eps unused).
+ * Deterministic and independent of the device: no atomics, no CU count.  Part p < parts of batch b adds the rows of tokens
+ * p * T .. min((p + 1) * T, L) - 1, T = ceil(L / parts), in token order in fp32 into partial[b][p][:] (caller's scratch, fp32
+ * [B][parts][C]; 1 <= parts <= tokens_per_batch; a part past the end holds zeros); a second launch adds the parts in index order and
+ * multiplies by the fp32 1 / L.  Equal arguments give equal bits. */
+int flexam_k_mean(const void* k, int64_t ldk, const float* wk, int64_t M, int C, float eps, const float* rope_cos, const float* rope_sin,
+                  int64_t tokens_per_batch, int64_t token_offset, int head_dim, int parts, float* partial, float* mean, void* stream);
 int flexam_attn_fwd_fp8(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
                         int head_dim, int kv_splits, int split_from_unit, float* ws_o, float* ws_ml, void* stream);
 /* The same kernel with Lq != Lk and the key records in CHUNKS of `chunk_tiles` 64-key tiles: kv8 = [n_chunks][B][H][chunk_tiles] records,
