@@ -4,14 +4,15 @@ the gfx950 flash-attention kernel.  Layout [B, L, N, D] like the reference; D mu
 The reference dispatches on VIDEOX_ATTENTION_TYPE to flash-attn / SageAttention / torch SDPA (attention_utils.py:195-233).
 Here FLASH_ATTENTION and every other value map to the bf16 HIP kernel; SAGE_ATTENTION -- the reference's quantised attention --
 maps to the MXFP8 kernel (csrc/attn_fp8.inc: e4m3 Q, K, P and V with E8M0 block scales, fp32 softmax) for self-attention shapes
-(Lq == Lk, no key lengths) and to the bf16 kernel otherwise; with FLEXAM_SAGE_SMOOTH_K=1 it quantises K - mean_tokens(K) (smooth-K).  Unsupported options raise instead of silently changing semantics."""
+(Lq == Lk, no key lengths) and to the bf16 kernel otherwise; with FLEXAM_SAGE_SMOOTH_K=1 it quantises K - mean_tokens(K) (smooth-K), with
+FLEXAM_SAGE_SMOOTH_V=1 V - mean_tokens(V), the mean added back to the output in fp32 (smooth-V).  Unsupported options raise instead of silently changing semantics."""
 import os
 import warnings
 
 import torch
 
 from . import hip
-from .dit_layout import smooth_k_asked
+from .dit_layout import smooth_k_asked, smooth_v_asked
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0.0, softmax_scale=None, q_scale=None, causal=False,
@@ -40,8 +41,10 @@ def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0.0, softmax_scale=No
         scale = (softmax_scale if softmax_scale is not None else d ** -0.5) * 1.4426950408889634
         # FLEXAM_SAGE_SMOOTH_K=1 (default 0): K - mean_tokens(K) is quantised instead of K -- the same softmax, see csrc/attn_fp8.inc
         mean = hip.k_mean(k.view(b * lk, n * d), None, None, None, lk) if smooth_k_asked(os.environ) else None
-        bufs = hip.attn_fp8_pack((q.float() * scale).to(torch.bfloat16), k, v, k_shift=mean)
-        return hip.attn_fwd_fp8(bufs, lq).to(out_dtype)
+        # FLEXAM_SAGE_SMOOTH_V=1 (default 0): V - mean_tokens(V) is quantised and the kernel adds the mean back before it rounds its output
+        v_mean = hip.k_mean(v.view(b * lk, n * d), None, None, None, lk) if smooth_v_asked(os.environ) else None
+        bufs = hip.attn_fp8_pack((q.float() * scale).to(torch.bfloat16), k, v, k_shift=mean, v_shift=v_mean)
+        return hip.attn_fwd_fp8(bufs, lq, o_shift=v_mean).to(out_dtype)
     if k_lens is None:
         return hip.attn_fwd(q, k, v, softmax_scale=softmax_scale).to(out_dtype)
     if uniform:

@@ -69,6 +69,9 @@ struct AttnParams {
   // into one s_mul_hi_u32 (exact for g, tiles < 2^16)
   int kv8_chunk_tiles;
   unsigned kv8_chunk_magic;
+  // smooth-V (flexam_attn_fwd_fp8_oshift): fp32 [B][H * 128] added to O / l in fp32 in front of the one rounding to bf16, by the OSHIFT
+  // instances of the two final writers (store_output, attn_merge_kernel); nullptr = none.  Partials never carry it: their weights sum to 1
+  const float* o_shift;
 };
 
 // byte offset of 16-byte chunk `ch` (0..15) of key row `row` in a [64][128] bf16 tile, image (b)
@@ -220,17 +223,25 @@ __device__ __forceinline__ void store_partial(const AttnParams& p, const f32x16 
 // A lane holds 4 of the 8 columns of each 8-column group of its row, its partner (lane ^ 32) the other 4.  One half exchange
 // per dword between the groups of a pair (lower lanes give their part of the odd group, upper lanes their part of the even
 // one) leaves 16 contiguous bytes in every lane: 8 stores of 16 B instead of 16 of 8 B (the tail is store-issue bound).
+// OSHIFT: p.o_shift[b][head * 128 + column] is added to O / l in fp32, loaded here (behind the key loop) in the accumulator's column order.
+template <bool OSHIFT = false>
 __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (&o_acc)[4], float inv_l, int b, int head, int qi, int h) {
   bf16* orow = p.o + (int64_t)b * p.o_bs + (int64_t)min(qi, p.Lq - 1) * p.o_rs + head * HD + 8 * h;
+  const float* srow = OSHIFT ? p.o_shift + ((int64_t)b * p.H + head) * HD + 4 * h : nullptr;
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
     for (int i = 0; i < 4; i += 2) {
       bf16x4 even, odd;
+      f32x4 se = {0.f, 0.f, 0.f, 0.f}, so = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (OSHIFT) {
+        se = *(const f32x4*)(srow + 32 * dt + 8 * i);
+        so = *(const f32x4*)(srow + 32 * dt + 8 * i + 8);
+      }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        even[e] = f2bf(o_acc[dt][4 * i + e] * inv_l);
-        odd[e] = f2bf(o_acc[dt][4 * i + 4 + e] * inv_l);
+        even[e] = f2bf(OSHIFT ? o_acc[dt][4 * i + e] * inv_l + se[e] : o_acc[dt][4 * i + e] * inv_l);
+        odd[e] = f2bf(OSHIFT ? o_acc[dt][4 * i + 4 + e] * inv_l + so[e] : o_acc[dt][4 * i + 4 + e] * inv_l);
       }
       const u32x2 ev = __builtin_bit_cast(u32x2, even), od = __builtin_bit_cast(u32x2, odd);
       unsigned a0 = ev[0], a1 = ev[1], c0 = od[0], c1 = od[1];
@@ -659,7 +670,9 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
 #include "attn_fp8.inc"
 
 // out[b][q][head][:] = sum_s w_s O_s / sum_s w_s l_s with w_s = exp2((m_s - max_s m_s) * scale_log2e) for the rows of the
-// launch's units; one wave per row, two columns per lane
+// launch's units; one wave per row, two columns per lane.  OSHIFT: + p.o_shift[b][head * 128 + column] in fp32 in front of the rounding
+// (once, here: the partials' weights w_s l_s / sum sum to 1)
+template <bool OSHIFT>
 __global__ __launch_bounds__(256) void attn_merge_kernel(AttnParams p) {
   const int64_t rows = (int64_t)p.n_units * QBLK;
   const int lane = threadIdx.x & 63;
@@ -683,8 +696,14 @@ __global__ __launch_bounds__(256) void attn_merge_kernel(AttnParams p) {
     const int head = bh % p.H, b = bh / p.H;
     const float inv = 1.0f / l;
     bf16x2 ov;
-    ov[0] = f2bf(acc[0] * inv);
-    ov[1] = f2bf(acc[1] * inv);
+    if constexpr (OSHIFT) {
+      const f32x2 sh = *(const f32x2*)(p.o_shift + (int64_t)bh * HD + 2 * lane);
+      ov[0] = f2bf(acc[0] * inv + sh[0]);
+      ov[1] = f2bf(acc[1] * inv + sh[1]);
+    } else {
+      ov[0] = f2bf(acc[0] * inv);
+      ov[1] = f2bf(acc[1] * inv);
+    }
     *(bf16x2*)(p.o + (int64_t)b * p.o_bs + (int64_t)q * p.o_rs + head * HD + 2 * lane) = ov;
   }
 }
@@ -701,16 +720,19 @@ struct AttnCall {
   float *ws_o = nullptr, *ws_ml = nullptr;
   const void *q8 = nullptr, *qs = nullptr, *kv8 = nullptr;   // MXFP8 operands (flexam_attn_fp8_pack) instead of q / k / v
   int kv8_chunk_tiles = 0;                     // 0 = one chunk holds all key tiles
+  const float* o_shift = nullptr;              // MXFP8 only (flexam_attn_fwd_fp8_oshift): see AttnParams::o_shift
 };
-// The seven instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
+// The eight instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
 struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
-AttnInstance attn_instance(bool fp8, bool cross, bool prescaled, bool full, bool short_ctx) {
+constexpr int ATTN_INSTANCES = 8;
+AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES, F8 = NSLOT * REC_BYTES;
-  static const AttnInstance table[7] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
+  static const AttnInstance table[ATTN_INSTANCES] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
                                         {attn_fwd_kernel<1, true>, BF, 3}, {attn_fwd_kernel<0, true, true>, BF, 4},
-                                        {attn_fwd_kernel<1, true, false, true>, BF, 5}, {attn8_fwd_kernel<0>, F8, 6}};
-  return table[fp8 ? 6 : full ? 4 : short_ctx ? 5 : (cross ? 1 : 0) + (prescaled ? 2 : 0)];
+                                        {attn_fwd_kernel<1, true, false, true>, BF, 5}, {attn8_fwd_kernel<0>, F8, 6},
+                                        {attn8_oshift_kernel, F8, 7}};      // the MXFP8 kernel that adds AttnParams::o_shift (smooth-V)
+  return table[fp8 ? (oshift ? 7 : 6) : full ? 4 : short_ctx ? 5 : (cross ? 1 : 0) + (prescaled ? 2 : 0)];
 }
 // FLEXAM_ATTN_FULL / _SHORT / _FUSED_TAIL, read per call (A/B in one process): 0 = the general instance / one workgroup per q block / two launches
 bool attn_switch(const char* name) { const char* e = getenv(name); return !(e && atoi(e) == 0); }
@@ -724,7 +746,9 @@ void split_part(AttnParams& p, int unit0, int n_units, int S, int tps) {      //
 }
 void launch_merge(const AttnParams& p, void* stream) {      // one wave per row of the launch's units, grid-stride past 16384 workgroups
   const int64_t g = ((int64_t)p.n_units * QBLK + 3) / 4;
-  hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)(g > 16384 ? 16384 : g)), dim3(256), 0, (hipStream_t)stream, p);
+  const dim3 grid((unsigned)(g > 16384 ? 16384 : g));
+  if (p.o_shift) hipLaunchKernelGGL(attn_merge_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, p);
+  else hipLaunchKernelGGL(attn_merge_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, p);
 }
 
 int attn_run(const AttnCall& c) {
@@ -733,7 +757,8 @@ int attn_run(const AttnCall& c) {
   FX_REQUIRE(c.B > 0 && c.H > 0 && c.Lq > 0 && c.Lk > 0, FLEXAM_E_SHAPE, "attn_fwd: empty problem B=%d H=%d Lq=%d Lk=%d", c.B, c.H, c.Lq, c.Lk);
   FX_REQUIRE(c.q_rs % 8 == 0 && c.k_rs % 8 == 0 && c.v_rs % 8 == 0 && c.o_rs % 8 == 0 && c.q_bs % 8 == 0 && c.k_bs % 8 == 0 && c.v_bs % 8 == 0 && c.o_bs % 8 == 0,
              FLEXAM_E_SHAPE, "attn_fwd: strides must keep 16-byte alignment of head rows");
-  FX_REQUIRE(((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v | (uintptr_t)c.o) % 16 == 0, FLEXAM_E_ARG, "attn_fwd: misaligned pointer");
+  FX_REQUIRE(((uintptr_t)c.q | (uintptr_t)c.k | (uintptr_t)c.v | (uintptr_t)c.o | (uintptr_t)c.o_shift) % 16 == 0, FLEXAM_E_ARG, "attn_fwd: misaligned pointer");
+  FX_REQUIRE(!c.o_shift || (c.q8 && c.partial_slot0 < 0), FLEXAM_E_ARG, "attn_fwd: an output shift goes with the MXFP8 operands and a final output");
   const int tiles_all = (c.Lk + KVBLK - 1) / KVBLK;
   FX_REQUIRE(c.kv_splits >= 1 && c.kv_splits <= tiles_all, FLEXAM_E_ARG, "attn_fwd: %d key splits for %d key tiles", c.kv_splits, tiles_all);
   FX_REQUIRE((c.kv_splits == 1 && c.partial_slot0 < 0) || (c.ws_o && c.ws_ml), FLEXAM_E_ARG, "attn_fwd: split-KV needs both workspaces");
@@ -746,7 +771,7 @@ int attn_run(const AttnCall& c) {
   p.ws_o = c.ws_o; p.ws_ml = c.ws_ml; p.last_key_bias = c.last_key_bias;
   p.partial = 0; p.slot0 = 0; p.n_slots = S; p.whole_units = 0;
   p.q8 = (const unsigned char*)c.q8; p.qs = (const unsigned*)c.qs; p.kv8 = (const unsigned char*)c.kv8; p.lq_pad = p.q_blocks * QBLK;
-  p.kv8_chunk_tiles = c.kv8_chunk_tiles > 0 ? c.kv8_chunk_tiles : tiles_all;
+  p.kv8_chunk_tiles = c.kv8_chunk_tiles > 0 ? c.kv8_chunk_tiles : tiles_all; p.o_shift = c.o_shift;
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
@@ -754,8 +779,8 @@ int attn_run(const AttnCall& c) {
   const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
   const bool short_ctx = !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
   const bool full = !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
-  const AttnInstance inst = attn_instance(fp8, cross, p.prescaled, full, short_ctx);
-  static bool attr_set[FLEXAM_MAX_DEVICES][7] = {};      // per device and kernel instance
+  const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx);
+  static bool attr_set[FLEXAM_MAX_DEVICES][ATTN_INSTANCES] = {};      // per device and kernel instance
   bool& lds_raised = attr_set[flexam_current_device()][inst.slot];
   if (!lds_raised) {
     if (hipFuncSetAttribute((const void*)inst.kern, hipFuncAttributeMaxDynamicSharedMemorySize, inst.smem) != hipSuccess)
@@ -838,38 +863,50 @@ extern "C" int flexam_attn_fwd_partial(const void* q, int64_t q_bs, int64_t q_rs
   return attn_run(c);
 }
 
-// the pack and the fused producer, without (k_shift = nullptr: the instances the plain entry points have always launched) and with smooth-K
+// the pack and the fused producer, without (k_shift = nullptr: the instances the plain entry points have always launched) and with smooth-K;
+// the pack also with smooth-V (v_shift)
 static int attn8_pack_run(const char* who, const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                           int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim, const float* k_shift,
-                          void* stream) {
+                          const float* v_shift, void* stream) {
   FX_REQUIRE(v && q8 && qs && kv8 && ((q == nullptr) == (k == nullptr)), FLEXAM_E_ARG, "attn_fp8_pack: null pointer (q and k: both or neither)");
   FX_REQUIRE(head_dim == HD && B > 0 && H > 0 && L > 0, FLEXAM_E_SHAPE, "attn_fp8_pack: bad sizes (head_dim 128 only)");
   FX_REQUIRE(q_rs % 8 == 0 && k_rs % 8 == 0 && v_rs % 8 == 0 && q_bs % 8 == 0 && k_bs % 8 == 0 && v_bs % 8 == 0, FLEXAM_E_SHAPE,
              "attn_fp8_pack: strides must keep 16-byte alignment of head rows");
-  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8 | (uintptr_t)k_shift) % 16 == 0, FLEXAM_E_ARG,
+  FX_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8 | (uintptr_t)k_shift | (uintptr_t)v_shift) % 16 == 0, FLEXAM_E_ARG,
              "attn_fp8_pack: misaligned pointer");
   Attn8Pack a;
   a.q = (const bf16*)q; a.k = (const bf16*)k; a.v = (const bf16*)v;
   a.q_bs = q_bs; a.q_rs = q_rs; a.k_bs = k_bs; a.k_rs = k_rs; a.v_bs = v_bs; a.v_rs = v_rs;
   a.q8 = (unsigned char*)q8; a.qs = (unsigned char*)qs; a.kv8 = (unsigned char*)kv8;
-  a.H = H; a.L = L; a.lq_pad = (L + QBLK - 1) / QBLK * QBLK; a.tiles = (L + KVBLK - 1) / KVBLK; a.k_shift = k_shift;
+  a.H = H; a.L = L; a.lq_pad = (L + QBLK - 1) / QBLK * QBLK; a.tiles = (L + KVBLK - 1) / KVBLK; a.k_shift = k_shift; a.v_shift = v_shift;
   const dim3 grid(a.lq_pad / KVBLK, H, B);
-  if (k_shift) hipLaunchKernelGGL(attn8_pack_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(attn8_pack_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, a);
+#define ATTN8_PACK_LAUNCH(K, V) hipLaunchKernelGGL((attn8_pack_kernel<K, V>), grid, dim3(256), 0, (hipStream_t)stream, a)
+  if (v_shift) { if (k_shift) ATTN8_PACK_LAUNCH(true, true); else ATTN8_PACK_LAUNCH(false, true); }
+  else if (k_shift) ATTN8_PACK_LAUNCH(true, false);
+  else ATTN8_PACK_LAUNCH(false, false);
+#undef ATTN8_PACK_LAUNCH
   return flexam_check_launch(who);
 }
 
 extern "C" int flexam_attn_fp8_pack(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                                     int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
                                     void* stream) {
-  return attn8_pack_run("flexam_attn_fp8_pack", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, nullptr, stream);
+  return attn8_pack_run("flexam_attn_fp8_pack", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, nullptr, nullptr, stream);
 }
 
 extern "C" int flexam_attn_fp8_pack_shift(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                                           int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
                                           const float* k_shift, void* stream) {
   FX_REQUIRE(k_shift && k, FLEXAM_E_ARG, "attn_fp8_pack_shift: null pointer (the shift needs its k)");
-  return attn8_pack_run("flexam_attn_fp8_pack_shift", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, k_shift, stream);
+  return attn8_pack_run("flexam_attn_fp8_pack_shift", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, k_shift, nullptr, stream);
+}
+
+extern "C" int flexam_attn_fp8_pack_shift_kv(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                             int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
+                                             const float* k_shift, const float* v_shift, void* stream) {
+  FX_REQUIRE(!k_shift || k, FLEXAM_E_ARG, "attn_fp8_pack_shift_kv: null pointer (the K shift needs its k)");
+  return attn8_pack_run("flexam_attn_fp8_pack_shift_kv", q, q_bs, q_rs, k, k_bs, k_rs, v, v_bs, v_rs, q8, qs, kv8, B, H, L, head_dim, k_shift, v_shift,
+                        stream);
 }
 
 static int rmsnorm_rope_mx_run(const char* who, const void* q, int64_t ldq, const float* wq, const void* k, int64_t ldk, const float* wk, void* q8,
@@ -944,6 +981,18 @@ extern "C" int flexam_attn_fwd_fp8(const void* q8, const void* qs, const void* k
   c.q8 = q8; c.qs = qs; c.kv8 = kv8; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
   c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = FLEXAM_ATTN_PRESCALED; c.stream = stream;
   c.kv_splits = kv_splits; c.split_from_unit = split_from_unit; c.ws_o = ws_o; c.ws_ml = ws_ml;
+  return attn_run(c);
+}
+
+extern "C" int flexam_attn_fwd_fp8_oshift(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
+                                          int head_dim, int kv_splits, int split_from_unit, float* ws_o, float* ws_ml, const float* o_shift,
+                                          void* stream) {
+  FX_REQUIRE(q8 && qs && kv8 && o_shift, FLEXAM_E_ARG, "attn_fwd_fp8_oshift: null pointer");
+  FX_REQUIRE(((uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG, "attn_fwd_fp8_oshift: misaligned pointer");
+  AttnCall c;
+  c.q8 = q8; c.qs = qs; c.kv8 = kv8; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = FLEXAM_ATTN_PRESCALED; c.stream = stream;
+  c.kv_splits = kv_splits; c.split_from_unit = split_from_unit; c.ws_o = ws_o; c.ws_ml = ws_ml; c.o_shift = o_shift;
   return attn_run(c);
 }
 

@@ -39,8 +39,11 @@ __device__ __forceinline__ i32x8 join8(u32x4 lo, u32x4 hi) {
   return (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
 
-template <int KIND>
-__global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) {
+// The kernel's body, inlined into its two __global__ wrappers below (KIND: the profiler symbol, as attn_fwd_kernel's).  OSHIFT: the
+// epilogue adds p.o_shift (smooth-V) to O / l in fp32 in front of the rounding to bf16 -- loaded behind the key loop, nothing of it inside.
+// p by value, as the kernel had it: by reference hipcc allocates the loop differently (186 instead of 188 VGPRs, another schedule).
+template <int KIND, bool OSHIFT>
+__device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // ring of 4 records
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -309,8 +312,13 @@ __global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) {
     store_partial<true>(p, o_acc, osc, ref, l_tot, split, ul, wave, r, h, q0 + r);      // reference in exp2 units (the merge runs in its prescaled form)
     return;
   }
-  store_output(p, o_acc, osc / l_tot, b, head, q0 + r, h);
+  store_output<OSHIFT>(p, o_acc, osc / l_tot, b, head, q0 + r, h);
 }
+
+template <int KIND>
+__global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) { attn8_fwd_body<KIND, false>(p); }
+// the same kernel with the output shift: a symbol of its own (flexam_attn_fwd_fp8_oshift)
+__global__ __launch_bounds__(NT, 2) void attn8_oshift_kernel(AttnParams p) { attn8_fwd_body<0, true>(p); }
 
 // ---- the pack kernel: q, k (after RMSNorm + RoPE; q carrying softmax_scale * log2 e) and v, bf16 [B, L, H, 128] -> MXFP8 operands.
 // One workgroup per (64-token tile, head, batch).  K and Q: thread = (token row, 32-channel block); V: thread = (channel, 32-key half
@@ -322,7 +330,8 @@ struct Attn8Pack {
   unsigned char* qs;      // [B][H][lq_pad][4] E8M0 bytes (read as one dword per row by the attention kernel)
   unsigned char* kv8;
   int H, L, lq_pad, tiles;
-  const float* k_shift;   // SHIFT instance only (flexam_attn_fp8_pack_shift): fp32 [B][H * 128], subtracted from K before it is quantised
+  const float* k_shift;   // SHIFT instances only (flexam_attn_fp8_pack_shift): fp32 [B][H * 128], subtracted from K before it is quantised
+  const float* v_shift;   // VSHIFT instances only (flexam_attn_fp8_pack_shift_kv): fp32 [B][H * 128], subtracted from V before it is quantised
 };
 
 // smallest power of two 2^e with amax * 2^-e <= 448 (the largest e4m3 number): returns the E8M0 byte e + 127 and 2^-e
@@ -334,7 +343,7 @@ __device__ __forceinline__ unsigned mx_scale(float amax, float& inv) {
   return (unsigned)e;
 }
 
-template <bool SHIFT>
+template <bool SHIFT, bool VSHIFT = false>
 __global__ __launch_bounds__(256) void attn8_pack_kernel(Attn8Pack a) {
   __shared__ __attribute__((aligned(16))) bf16 vt[64 * 128];
   const int tid = threadIdx.x, tile = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -417,6 +426,15 @@ __global__ __launch_bounds__(256) void attn8_pack_kernel(Attn8Pack a) {
     for (int hh = 0; hh < 2; ++hh)
 #pragma unroll
       for (int e = 0; e < 16; ++e) x[16 * hh + e] = bf2f(vt[(32 * bb + (e & 3) + 8 * (e >> 2) + 4 * hh) * 128 + d]);
+    if constexpr (VSHIFT) {                                // smooth-V: v - shift in fp32, one rounding; keys past L stay zero, not -shift
+      const float sh = a.v_shift[bh * HD + d];
+      const int key0 = tile * 64 + 32 * bb;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          if (key0 + (e & 3) + 8 * (e >> 2) + 4 * hh < a.L) x[16 * hh + e] -= sh;
+    }
     float amax = 0.f;
 #pragma unroll
     for (int j = 0; j < 32; ++j) amax = fmaxf(amax, fabsf(x[j]));

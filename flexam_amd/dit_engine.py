@@ -26,7 +26,7 @@ from typing import List, Optional
 import torch
 
 from . import hip
-from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, smooth_k_asked
+from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, smooth_k_asked, smooth_v_asked
 from .dit_sp import HeadAllToAll, KVGather, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
@@ -70,6 +70,7 @@ def _proj_fp8(h: torch.Tensor, pk: dict, wname: str, bias, epilogue: int = 0) ->
 class DiTEngine:
     _sage_warned = False
     _smooth_k_warned = False
+    _smooth_v_warned = False
 
     def __init__(self, model):
         self.model = model
@@ -98,7 +99,9 @@ class DiTEngine:
         self._ws = {}
         self._attn8 = {}                            # MXFP8 operand buffers of the quantised self-attention (_attn8_buffers)
         self._kmean = {}                            # smooth-K: K's token mean and the scratch of its parts (_k_mean_buffers)
+        self._vmean = {}                            # smooth-V: the same pair for V's token mean
         self._smooth_k = self.sage_smooth_taken = False
+        self._smooth_v = self.sage_smooth_v_taken = False
         self._ws_gen = 0                            # bumped whenever the activation buffers are dropped: recorded launch plans name their addresses
         self._angles = None
         self.cond = None
@@ -350,10 +353,11 @@ class DiTEngine:
             cache[(nb, lc, heads)] = hip.attn_fp8_buffers(nb, heads, lc, self.device)      # (block 0 may run one sample: its own set, not a re-allocation per step)
         return cache[(nb, lc, heads)]
 
-    def _k_mean_buffers(self, nb, lc):
-        """(mean fp32 [nb, dim], scratch fp32 [nb, parts, dim]) of hip.k_mean under FLEXAM_SAGE_SMOOTH_K, cached as _attn8_buffers caches
-        the operands: one set per (samples, heads), block 0's one-sample run under share0 its own."""
-        cache = self._kmean
+    def _k_mean_buffers(self, nb, lc, of_v=False):
+        """(mean fp32 [nb, dim], scratch fp32 [nb, parts, dim]) of hip.k_mean under FLEXAM_SAGE_SMOOTH_K (of_v: FLEXAM_SAGE_SMOOTH_V, a
+        pair of its own: V's mean lives until the attention has added it back), cached as _attn8_buffers caches the operands: one set
+        per (samples, heads), block 0's one-sample run under share0 its own."""
+        cache = self._vmean if of_v else self._kmean
         if (nb, lc, self.nh) not in cache:
             if any(k[1:] != (lc, self.nh) for k in cache):
                 cache.clear()
@@ -401,6 +405,15 @@ class DiTEngine:
             import warnings
             warnings.warn("flexam_amd: FLEXAM_SAGE_SMOOTH_K=1 is ignored under sequence parallelism: K is quantised as it is",
                           RuntimeWarning, stacklevel=3)
+        # FLEXAM_SAGE_SMOOTH_V=1 (default 0): V - mean_tokens(V) is quantised and the mean added back to the attention's output in fp32.
+        # Kept like smooth-K and independent of it.  One rank only: under the record gather each rank's own mean would not be exact
+        asked = smooth_v_asked(env)
+        self._smooth_v = bool(m.sage and m.sp == 1 and asked)
+        if asked and m.sage and m.sp > 1 and not DiTEngine._smooth_v_warned:       # said once per process
+            DiTEngine._smooth_v_warned = True
+            import warnings
+            warnings.warn("flexam_amd: FLEXAM_SAGE_SMOOTH_V=1 is ignored under sequence parallelism: V is quantised as it is",
+                          RuntimeWarning, stacklevel=3)
         return m
 
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
@@ -440,7 +453,7 @@ class DiTEngine:
             if m.sp > 1:
                 xr[b].copy_(full[m.tok0:m.tok0 + lc])
         self.share0_taken, self.sage_taken = m.share0, m.sage          # what this forward DID (bench.py labels its line from them)
-        self.sage_smooth_taken = self._smooth_k
+        self.sage_smooth_taken, self.sage_smooth_v_taken = self._smooth_k, self._smooth_v
         if not m.share0:
             for b in range(bx, B):
                 xr[b].copy_(xr[0])
@@ -513,7 +526,7 @@ class DiTEngine:
         address they carry.  Not with TeaCache (data-dependent skipping), per-layer tables or blocks called as modules (_Mode.use_plan)."""
         cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
         key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
-               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), self._smooth_k)
+               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), self._smooth_v, self._smooth_k)
         plans = cd.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -573,24 +586,31 @@ class DiTEngine:
         the MXFP8 operands of the quantised attention (csrc/attn_fp8.inc): at the 5B model's 24 heads (sage_fused) the RMSNorm + RoPE
         launch writes Q and K as operands directly and V is packed on its own; otherwise q and k are normed in bf16 and all three packed.
         Smooth-K (FLEXAM_SAGE_SMOOTH_K, _mode): one more pass over k, the token mean of the normed and rotated K (hip.k_mean: computed
-        from the raw k in the fused form, which never writes that K), is what the producer subtracts before it quantises K."""
+        from the raw k in the fused form, which never writes that K), is what the producer subtracts before it quantises K.
+        Smooth-V (FLEXAM_SAGE_SMOOTH_V): the token mean of the V columns, taken as given, is what both pack forms subtract from V; it is
+        returned (else None) for the attention to add back (hip.attn_fwd_fp8's o_shift)."""
         d, rows, cd = self.dim, nb * m.lc, self.cond
         q, k = ws["qkv"][:rows, 0:d], ws["qkv"][:rows, d:2 * d]
         q4, k4, v4, _ = self._heads(m, ws)
         smooth = bufs is not None and self._smooth_k
         mean, scratch = self._k_mean_buffers(nb, m.lc) if smooth else (None, None)
+        v_mean = None
+        if bufs is not None and self._smooth_v:
+            v_mean, v_scratch = self._k_mean_buffers(nb, m.lc, of_v=True)
+            hip.k_mean(ws["qkv"][:rows, 2 * d:3 * d], None, None, None, m.lc, out=v_mean, scratch=v_scratch)
         if bufs is not None and m.sage_fused:
             if smooth:
                 hip.k_mean(k, p["nk"], cd["cos"], cd["sin"], m.lc, m.tok0, eps=self.eps, head_dim=self.hd, out=mean, scratch=scratch)
             hip.rmsnorm_rope_mx(q, p["nq"], k, p["nk"], bufs, cd["cos"], cd["sin"], m.lc, m.tok0, eps=self.eps, k_shift=mean)
-            hip.attn_fp8_pack(None, None, v4[:nb], bufs)
-            return
+            hip.attn_fp8_pack(None, None, v4[:nb], bufs, v_shift=v_mean)
+            return v_mean
         hip.rmsnorm_rope(q, p["nq"], k, p["nk"], eps=self.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=m.lc,
                          token_offset=m.tok0, head_dim=self.hd)
         if smooth:
             hip.k_mean(k, None, None, None, m.lc, out=mean, scratch=scratch)
         if bufs is not None:
-            hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs, k_shift=mean)
+            hip.attn_fp8_pack(q4[:nb], k4[:nb], v4[:nb], bufs, k_shift=mean, v_shift=v_mean)
+        return v_mean
 
     def _self_attention(self, i, p, T, m, ws, ex=None):
         """LN + modulate -> q|k|v -> self-attention in this forward's layout (one rank, all-to-all over heads or K|V all-gather) ->
@@ -623,8 +643,8 @@ class DiTEngine:
         q4, k4, v4, ao4 = self._heads(m, ws)
         if m.sage:
             bufs = self._attn8_buffers(nb, m.lc)
-            self._norm_rope_qk(p, m, ws, nb, bufs)
-            hip.attn_fwd_fp8(bufs, m.lc, out=ao4[:nb])
+            v_mean = self._norm_rope_qk(p, m, ws, nb, bufs)
+            hip.attn_fwd_fp8(bufs, m.lc, out=ao4[:nb], o_shift=v_mean)
         else:
             self._norm_rope_qk(p, m, ws, nb)
             hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)

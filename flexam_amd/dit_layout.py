@@ -97,6 +97,12 @@ def smooth_k_asked(env) -> bool:
     return env.get("FLEXAM_SAGE_SMOOTH_K", "0") == "1"
 
 
+def smooth_v_asked(env) -> bool:
+    """FLEXAM_SAGE_SMOOTH_V=1 (default 0): quantise V - mean_tokens(V) in the MXFP8 self-attention and add the mean back to its output
+    in fp32.  Independent of smooth-K and kept like it: beside the mode in DiTEngine._mode (`sage and sp == 1` only), in the plan key."""
+    return env.get("FLEXAM_SAGE_SMOOTH_V", "0") == "1"
+
+
 def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, parallel: Parallel, B, L, dens_same,
                  bx, R, rows_per_batch, only_row, rows_shared, teacache: bool) -> _Mode:
     """The mode of one forward.  env: the environment mapping; fused .. parallel: the engine (all blocks native, layers, heads, head

@@ -588,11 +588,13 @@ def _check_fp8_bufs(bufs, B, H, L, device, who):
                                f"on {t.device}, want {shape} {dt}")
 
 
-def _k_shift(who, k_shift, B, C, device):
-    """The smooth-K shift of the shifted producers: contiguous fp32 [B, C] on the operands' device (see flexam_hip.h)."""
-    if tuple(k_shift.shape) != (B, C) or k_shift.dtype != F32 or not k_shift.is_contiguous() or k_shift.device != torch.device(device):
-        raise RuntimeError(f"{who}: k_shift must be contiguous float32 [B={B}, {C}] on {device}, got {tuple(k_shift.shape)} {k_shift.dtype} "
-                           f"on {k_shift.device}")
+def _k_shift(who, k_shift, B, C, device, name="k_shift"):
+    """The smooth-K shift of the shifted producers (and, under their names, smooth-V's v_shift and o_shift): contiguous fp32 [B, C] on
+    the operands' device (see flexam_hip.h)."""
+    if (not torch.is_tensor(k_shift) or tuple(k_shift.shape) != (B, C) or k_shift.dtype != F32 or not k_shift.is_contiguous()
+            or k_shift.device != torch.device(device)):
+        got = f"{tuple(k_shift.shape)} {k_shift.dtype} on {k_shift.device}" if torch.is_tensor(k_shift) else type(k_shift).__name__
+        raise RuntimeError(f"{who}: {name} must be contiguous float32 [B={B}, {C}] on {device}, got {got}")
     return _ptr(k_shift, F32)
 
 
@@ -635,9 +637,11 @@ def k_mean(k, wk, rope_cos, rope_sin, tokens_per_batch, token_offset=0, eps=1e-6
     return out
 
 
-def attn_fp8_pack(q, k, v, bufs=None, k_shift=None):
+def attn_fp8_pack(q, k, v, bufs=None, k_shift=None, v_shift=None):
     """q, k, v [B, L, H, 128] bf16 (q prescaled by softmax_scale * log2 e) -> the MXFP8 operand buffers of attn_fwd_fp8.  k_shift
-    (smooth-K, fp32 [B, H * 128]): K is quantised from float(k) - k_shift (flexam_attn_fp8_pack_shift)."""
+    (smooth-K, fp32 [B, H * 128]): K is quantised from float(k) - k_shift (flexam_attn_fp8_pack_shift).  v_shift (smooth-V, fp32
+    [B, H * 128]): V is quantised from float(v) - v_shift, also in the V-only call (flexam_attn_fp8_pack_shift_kv); attn_fwd_fp8 then
+    takes the same tensor as o_shift."""
     B, L, H, D = v.shape
     if any(t is not None and t.shape != v.shape for t in (q, k)):
         raise RuntimeError(f"attn_fp8_pack: q, k, v must be [B, L, H, {ATTN_HEAD_DIM}], all of one shape")
@@ -650,12 +654,15 @@ def attn_fp8_pack(q, k, v, bufs=None, k_shift=None):
     q8, qs, kv8 = bufs
     qk = (lambda t: (t.stride(0), t.stride(1))) if q is not None else (lambda t: (0, 0))
     args = (_ptr(q, BF16), *qk(q), _ptr(k, BF16), *qk(k), _ptr(v, BF16), v.stride(0), v.stride(1), _raw(q8), _raw(qs), _raw(kv8), B, H, L, D)
-    if k_shift is None:
-        _call("flexam_attn_fp8_pack", *args)
+    if k_shift is not None and k is None:
+        raise RuntimeError("attn_fp8_pack: k_shift needs its k")
+    ks = _k_shift("attn_fp8_pack", k_shift, B, H * D, v.device) if k_shift is not None else None
+    if v_shift is not None:
+        _call("flexam_attn_fp8_pack_shift_kv", *args, ks, _k_shift("attn_fp8_pack", v_shift, B, H * D, v.device, "v_shift"))
+    elif k_shift is not None:
+        _call("flexam_attn_fp8_pack_shift", *args, ks)
     else:
-        if k is None:
-            raise RuntimeError("attn_fp8_pack: k_shift needs its k")
-        _call("flexam_attn_fp8_pack_shift", *args, _k_shift("attn_fp8_pack", k_shift, B, H * D, v.device))
+        _call("flexam_attn_fp8_pack", *args)
     return bufs
 
 
@@ -687,8 +694,9 @@ def _fp8_split_words(device, kv_splits, split_from_unit, batch_heads, lq, lk):
     return S, from_unit, _ptr(ws_o, F32), _ptr(ws_ml, F32)
 
 
-def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None):
-    """Self-attention from packed MXFP8 operands (attn_fp8_pack) -> out [B, L, H, 128] bf16."""
+def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None, o_shift=None):
+    """Self-attention from packed MXFP8 operands (attn_fp8_pack) -> out [B, L, H, 128] bf16.  o_shift (smooth-V, fp32 [B, H * 128]: the
+    v_shift the operands were packed with) is added to the output in fp32 before its one rounding (flexam_attn_fwd_fp8_oshift)."""
     q8, qs, kv8 = bufs
     B, H, D = q8.shape[0], q8.shape[1], ATTN_HEAD_DIM
     _check_fp8_bufs(bufs, B, H, L, q8.device, "attn_fwd_fp8")
@@ -697,8 +705,12 @@ def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None):
     _packed_heads("attn_fwd_fp8", out)
     if tuple(out.shape) != (B, L, H, D):
         raise RuntimeError(f"attn_fwd_fp8: out must be [B={B}, L={L}, H={H}, {D}] with heads packed along the row, got {tuple(out.shape)}")
-    _call("flexam_attn_fwd_fp8", _raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D,
-          *_fp8_split_words(q8.device, kv_splits, split_from_unit, B * H, L, L))
+    args = (_raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D,
+            *_fp8_split_words(q8.device, kv_splits, split_from_unit, B * H, L, L))
+    if o_shift is None:
+        _call("flexam_attn_fwd_fp8", *args)
+    else:
+        _call("flexam_attn_fwd_fp8_oshift", *args, _k_shift("attn_fwd_fp8", o_shift, B, H * D, q8.device, "o_shift"))
     return out
 
 

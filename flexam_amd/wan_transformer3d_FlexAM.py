@@ -191,7 +191,7 @@ class _SelfAttn(_Attn):
         (angle table, or the reference's complex exp(i angle) table)."""
         from . import hip
         from .dist import current_sp_context
-        from .dit_layout import smooth_k_asked
+        from .dit_layout import smooth_k_asked, smooth_v_asked
         b, l, c = x.shape
         nh, hd = self.num_heads, self.head_dim
         sp = current_sp_context()
@@ -217,9 +217,11 @@ class _SelfAttn(_Attn):
         if n_keys < l:
             ao = hip.attn_fwd(q4, k4[:, :n_keys], v4[:, :n_keys], prescaled=True)
         elif os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION" and not torch.is_grad_enabled() and hd == 128:
-            # the reference's attention() reads the switch per call (ATT.py:195-203); FLEXAM_SAGE_SMOOTH_K=1: K - mean_tokens(K) is quantised
+            # the reference's attention() reads the switch per call (ATT.py:195-203); FLEXAM_SAGE_SMOOTH_K=1: K - mean_tokens(K) is quantised;
+            # FLEXAM_SAGE_SMOOTH_V=1: V - mean_tokens(V) is, and the kernel adds the mean back in fp32
             mean = hip.k_mean(qkv[:, c:2 * c], None, None, None, l) if smooth_k_asked(os.environ) else None
-            ao = hip.attn_fwd_fp8(hip.attn_fp8_pack(q4, k4, v4, k_shift=mean), l)
+            v_mean = hip.k_mean(qkv[:, 2 * c:3 * c], None, None, None, l) if smooth_v_asked(os.environ) else None
+            ao = hip.attn_fwd_fp8(hip.attn_fp8_pack(q4, k4, v4, k_shift=mean, v_shift=v_mean), l, o_shift=v_mean)
         else:
             ao = hip.attn_fwd(q4, k4, v4, prescaled=True)
         return hip.gemm(ao.view(b * l, c), pk["wo"], pk["bo"]).view(b, l, c)

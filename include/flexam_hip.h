@@ -210,6 +210,25 @@ int flexam_k_mean(const void* k, int64_t ldk, const float* wk, int64_t M, int C,
                   int64_t tokens_per_batch, int64_t token_offset, int head_dim, int parts, float* partial, float* mean, void* stream);
 int flexam_attn_fwd_fp8(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
                         int head_dim, int kv_splits, int split_from_unit, float* ws_o, float* ws_ml, void* stream);
+/* Smooth-V, SageAttention's `smooth_v`: the rows of softmax sum to 1, so softmax(S).(V - 1 c^T) + c^T = softmax(S).V for ANY vector c per
+ * (batch, head).  V is quantised with one E8M0 scale per channel and 32-key half tile and e4m3's error is relative to the element, so a
+ * channel offset all keys share is paid for in every product -- and multiplied by the e4m3 rounding of P as well (the plain output is
+ * sum p~ (v - c) / l + c sum p~ / l with sum p~ / l != 1).  With c = the token mean of V (flexam_k_mean in its as-given form, wk = NULL,
+ * on the V columns) both are gone.  Independent of smooth-K; the two compose.
+ * flexam_attn_fp8_pack_shift_kv: flexam_attn_fp8_pack with K quantised from float(k) - k_shift[b][h * 128 + c] (as flexam_attn_fp8_pack_shift)
+ * and V from float(v) - v_shift[b][h * 128 + c], one fp32 subtraction each in front of the block amax (fp32 [B][H * 128], taken as given).
+ * Either shift may be NULL (that operand is packed as it is); k_shift needs q and k, v_shift also serves the V-only call (q = k = NULL).
+ * Keys past L stay zero (codes 0, scale byte 1), not -shift; Q is flexam_attn_fp8_pack's, byte for byte.
+ * flexam_attn_fwd_fp8_oshift: flexam_attn_fwd_fp8 (kv_splits, split_from_unit, ws_o and ws_ml as there) with o_shift[b][h * 128 + c]
+ * (fp32 [B][H * 128], not NULL) added to O / l in fp32 BEFORE the one rounding to bf16, in both final writers: the attention kernel's own
+ * epilogue (an instance under its own symbol; the shift is loaded behind the key loop) and, for the units split over key ranges, the
+ * merge.  The partial results never carry it: their weights sum to 1, the merge adds it once. */
+int flexam_attn_fp8_pack_shift_kv(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                  int64_t v_bs, int64_t v_rs, void* q8, void* qs, void* kv8, int B, int H, int L, int head_dim,
+                                  const float* k_shift, const float* v_shift, void* stream);
+int flexam_attn_fwd_fp8_oshift(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
+                               int head_dim, int kv_splits, int split_from_unit, float* ws_o, float* ws_ml, const float* o_shift,
+                               void* stream);
 /* The same kernel with Lq != Lk and the key records in CHUNKS of `chunk_tiles` 64-key tiles: kv8 = [n_chunks][B][H][chunk_tiles] records,
  * n_chunks = ceil(ceil(Lk / 64) / chunk_tiles) -- the rank-major result of all-gathering every rank's own records under sequence
  * parallelism (each rank's token chunk a multiple of 64 tokens: MXFP8 K|V travel instead of bf16 rows, 288 instead of 512 bytes per key

@@ -1,5 +1,6 @@
-"""Dev tool: what the smooth-K pass costs per block at the bench shape (CFG pair, L = 11648, 24 heads; k a column view of the [M, 9216]
-q|k|v buffer, as the engine calls it).  Times hip.k_mean in both forms and the fused producer with and without a shift, with device
+"""Dev tool: what the smooth-K and smooth-V passes cost per block at the bench shape (CFG pair, L = 11648, 24 heads; k and v column views of
+the [M, 9216] q|k|v buffer, as the engine calls them).  Times hip.k_mean in both forms and the fused producer with and without a shift;
+for smooth-V the mean of the V columns, the V-only pack with and without v_shift and the attention with and without o_shift; with device
 events over `--iters` back-to-back calls after a warm-up, and prints the mean kernel's GB/s: the bytes are those the algorithm needs
 (K once, the parts written and read once, the mean).  usage: k_mean_bench.py [--iters=200] [--parts=512,256,1024]"""
 import os
@@ -54,3 +55,16 @@ for parts in parts_list:
 us0 = timed(lambda: H.rmsnorm_rope_mx(q, wq, k, wk, bufs, cos, sin, L))
 us1 = timed(lambda: H.rmsnorm_rope_mx(q, wq, k, wk, bufs, cos, sin, L, k_shift=mean))
 print(f"rmsnorm_rope_mx: {us0:.1f} us per call; with k_shift (two launches): {us1:.1f} us")
+# smooth-V: the mean of the V columns (as given), the V-only pack the fused producer is followed by, the attention that adds the mean back
+v, v4 = qkv[:, 2 * C:], qkv.view(B, L, 3, heads, D)[:, :, 2]
+v_mean, v_scratch = torch.empty(B, C, device="cuda"), torch.empty(B, H.k_mean_parts(L), C, device="cuda")
+us = timed(lambda: H.k_mean(v, None, None, None, L, out=v_mean, scratch=v_scratch))
+print(f"k_mean of the V columns (as given, parts={v_scratch.shape[1]}): {us:.1f} us per call (both launches)")
+us0 = timed(lambda: H.attn_fp8_pack(None, None, v4, bufs))
+us1 = timed(lambda: H.attn_fp8_pack(None, None, v4, bufs, v_shift=v_mean))
+print(f"attn_fp8_pack, V only: {us0:.1f} us per call; with v_shift: {us1:.1f} us")
+out = torch.empty(B, L, heads, D, dtype=torch.bfloat16, device="cuda")
+H.rmsnorm_rope_mx(q, wq, k, wk, bufs, cos, sin, L)
+us0 = timed(lambda: H.attn_fwd_fp8(bufs, L, out=out), group=4)
+us1 = timed(lambda: H.attn_fwd_fp8(bufs, L, out=out, o_shift=v_mean), group=4)
+print(f"attn_fwd_fp8: {us0:.1f} us per call; with o_shift: {us1:.1f} us")
