@@ -5,7 +5,13 @@ The reference dispatches on VIDEOX_ATTENTION_TYPE to flash-attn / SageAttention 
 Here FLASH_ATTENTION and every other value map to the bf16 HIP kernel; SAGE_ATTENTION -- the reference's quantised attention --
 maps to the MXFP8 kernel (csrc/attn_fp8.inc: e4m3 Q, K, P and V with E8M0 block scales, fp32 softmax) for self-attention shapes
 (Lq == Lk, no key lengths) and to the bf16 kernel otherwise; with FLEXAM_SAGE_SMOOTH_K=1 it quantises K - mean_tokens(K) (smooth-K), with
-FLEXAM_SAGE_SMOOTH_V=1 V - mean_tokens(V), the mean added back to the output in fp32 (smooth-V).  Unsupported options raise instead of silently changing semantics."""
+FLEXAM_SAGE_SMOOTH_V=1 V - mean_tokens(V), the mean added back to the output in fp32 (smooth-V).  Unsupported options raise instead of silently changing semantics.
+
+`causal` and `window_size` are flash-attn's (attention_utils.py:43-171 hands them to flash_attn_varlen_func): window_size = (left, right),
+a negative side unbounded, query i sees key j iff j >= i - left and j <= i + right; causal=True sets right = 0.  They are served by the
+windowed bf16 kernel (hip.attn_fwd_window) for Lq == Lk with q_lens / k_lens absent or all equal to that length.  Under SAGE_ATTENTION
+a mask also runs that bf16 kernel: the MXFP8 kernel has no mask -- and the reference's own `sageattn` call forwards is_causal only and
+drops window_size (attention_utils.py:195-203), which this seam does not imitate."""
 import os
 import warnings
 
@@ -17,14 +23,23 @@ from .dit_layout import smooth_k_asked, smooth_v_asked
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0.0, softmax_scale=None, q_scale=None, causal=False,
               window_size=(-1, -1), deterministic=False, dtype=torch.bfloat16, fa_version=None, attention_type=None, attn_mask=None):
-    if causal or attn_mask is not None or dropout_p != 0.0 or tuple(window_size) != (-1, -1):
-        raise NotImplementedError("flexam_amd.attention: causal / mask / dropout / window are not used on the FlexAM path")
+    if attn_mask is not None or dropout_p != 0.0:
+        raise NotImplementedError("flexam_amd.attention: attn_mask / dropout are not used on the FlexAM path")
+    window = hip.attn_window(window_size, causal)
     if q_scale is not None:
         q = q * q_scale
     b, lq, n, d = q.shape
     lk = k.shape[1]
     out_dtype = q.dtype
     q, k, v = (u.to(torch.bfloat16).contiguous() for u in (q, k, v))
+    if window != (-1, -1):
+        # flash-attn aligns the mask of Lq != Lk (and of every sample's q_lens[i] != k_lens[i]) to the bottom-right corner, torch SDPA's
+        # is_causal to the top-left one: the reference's answer depends on the backend it finds, so only the case both agree on is served
+        lens = [int(x) for u in (q_lens, k_lens) if u is not None for x in u]
+        if lq != lk or any(x != lq for x in lens):
+            raise NotImplementedError("flexam_amd.attention: causal / window_size with Lq != Lk or with q_lens / k_lens other than the full "
+                                      "length is not served: flash-attn aligns such a mask bottom-right, SDPA top-left")
+        return hip.attn_fwd_window(q, k, v, window, softmax_scale=softmax_scale).to(out_dtype)
     uniform = True
     if k_lens is not None:
         kl = [int(x) for x in k_lens]

@@ -67,8 +67,11 @@ struct AttnParams {
   // key tile g lives in chunk g / kv8_chunk_tiles (flexam_attn_fwd_fp8_chunked: the rank-major result of a sequence-parallel all-gather of
   // every rank's records; one chunk = all tiles for the plain call); kv8_chunk_magic = ceil(2^32 / kv8_chunk_tiles) turns the division
   // into one s_mul_hi_u32 (exact for g, tiles < 2^16)
-  int kv8_chunk_tiles;
-  unsigned kv8_chunk_magic;
+  // (attn_window_kernel, which has no MXFP8 operands, reads the two words as its window: the struct, and with it the kernarg loads of
+  //  every other instance, stay as they are.)  Sliding window, Lq == Lk: row i sees key j iff (win_left < 0 or j >= i - win_left) and
+  //  (win_right < 0 or j <= i + win_right)
+  union { int kv8_chunk_tiles; int win_left; };
+  union { unsigned kv8_chunk_magic; int win_right; };
   // smooth-V (flexam_attn_fwd_fp8_oshift): fp32 [B][H * 128] added to O / l in fp32 in front of the one rounding to bf16, by the OSHIFT
   // instances of the two final writers (store_output, attn_merge_kernel); nullptr = none.  Partials never carry it: their weights sum to 1
   const float* o_shift;
@@ -266,8 +269,17 @@ __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (
 // (q blocks of one (batch, head), then of the next); the K/V tiles of a head stay in the ring while its q blocks last -- one LDS-DMA
 // prologue and barrier per head change instead of per q block, none inside (the tiles are read-only), so the waves run through
 // their rows of the blocks on their own.
-template <int KIND, bool PRE, bool FULL = false, bool SHORT = false>
-__global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
+// WIN (attn_window_kernel; the general form, whole units, Lq == Lk): flash-attn's sliding window.  A work unit walks the key tiles
+// [first, last] that hold a key one of its 256 rows sees (hip.attn_window_tiles states the same rule) instead of all of them.  Tiles in
+// which every row sees every key (`interior`) run the general step as it is; in the others -- the ragged last tile among them -- the
+// one uniform branch the general step has in front of part A applies mask_half and the window mask, a per-lane range compare like
+// mask_shift (a lane holds 32 scores of ONE row).  Rows of a wave may see no key at all in the first tiles of the unit (the unit's range
+// is the union over its rows): a row's reference stays unset until its first finite score, and the rescale factors are guarded against
+// inf - inf.  Units of a window without a left bound grow with the q block: the q blocks of a head are walked backwards, longest first.
+// (The one-block step of FULL for runs of interior tiles, next to the general step for the edges, was built and not kept: two step
+//  bodies in one loop cost hipcc 70 (scale in kernel) to 330 (PRE) spilled VGPRs, and a loop for each does not fit the instruction cache.)
+template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN>
+__device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p by value, as attn8_fwd_body takes it and for its reason)
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [4 K tiles][4 V tiles], each a ring
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -314,8 +326,22 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   // ---- LDS-DMA staging: piece id = tid + 512*i (i < 2) lands at LDS byte id*16 of the tile, i.e. row id/16,
   //      slot id%16; it must carry chunk (slot ^ swizzle(row)) of that key row
   const int tiles_all = (p.Lk + KVBLK - 1) / KVBLK;
-  const int t0 = split * tps;                                      // first key tile of this split (0 without split-KV)
-  const int ntiles = min(tps, tiles_all - t0);       // tiles are indexed locally below; t0 + t is the global tile
+  // WIN: the unit's key tiles [w_t0, w_t0 + w_n) and, of them, the interior tiles [ti_lo, ti_hi] (global indices) every row sees whole
+  int w_t0 = 0, w_n = 0, ti_lo = 0, ti_hi = 0;
+  if constexpr (WIN) {
+    int qb = unit % p.q_blocks;
+    if (p.win_left < 0) qb = p.q_blocks - 1 - qb;
+    const int qa = qb * QBLK, qz = min(qa + QBLK, p.Lq) - 1;      // first and last row of the unit
+    const int k_first = p.win_left < 0 ? 0 : max(0, qa - p.win_left);
+    const int k_last = p.win_right < 0 ? p.Lk - 1 : min(p.Lk - 1, qz + p.win_right);
+    w_t0 = k_first / KVBLK;
+    w_n = k_last / KVBLK - w_t0 + 1;
+    ti_lo = p.win_left < 0 ? 0 : (max(0, qz - p.win_left) + KVBLK - 1) / KVBLK;      // its first key is the last row's first or later
+    const int top_key = qa + p.win_right - (KVBLK - 1);                              // its last key is the first row's last or sooner
+    ti_hi = min(p.win_right < 0 ? tiles_all : top_key >= 0 ? top_key / KVBLK : -1, p.Lk / KVBLK - 1);      // (whole tiles only)
+  }
+  const int t0 = WIN ? w_t0 : split * tps;                         // first key tile of this split (0 without split-KV)
+  const int ntiles = WIN ? w_n : min(tps, tiles_all - t0);       // tiles are indexed locally below; t0 + t is the global tile
   const unsigned k_step = (unsigned)(KVBLK * p.k_rs * 2), v_step = (unsigned)(KVBLK * p.v_rs * 2);
   unsigned k_go[2], v_go[2];
 #pragma unroll
@@ -363,7 +389,8 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     for (int dt = 0; dt < 4; ++dt) vaddr[half][dt] = smem + V_RING + voff[half][dt];
   // ---- the work units of this workgroup (one, unless SHORT)
   for (int u = unit; u < unit_end; ++u) {
-  const int qbi = u % p.q_blocks, bh = u / p.q_blocks;
+  const int qbu = u % p.q_blocks, bh = u / p.q_blocks;
+  const int qbi = WIN && p.win_left < 0 ? p.q_blocks - 1 - qbu : qbu;      // (WIN without a left bound: longest units first)
   head = bh % p.H; b = bh / p.H;
   qbase = p.q + (int64_t)b * p.q_bs + head * HD;
   kbase = (const char*)(p.k + (int64_t)b * p.k_bs + head * HD);
@@ -435,6 +462,17 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
       }
     }
   };
+  // WIN: keys outside the window of this lane's row -> -inf.  Element e is key 32 gg + 4 h + (e & 3) + 8 (e >> 2) of global half gg: seen iff
+  // that lies in [row - left, row + right]: one per-lane value, the bounds' other terms are uniform.  Called in the tiles that are not interior only.
+  const int w_row = q0 + r - 4 * h;
+  auto mask_window = [&](int g, f32x16& sacc) {
+    const int base = (2 * t0 + g) * 32;
+    const int lo = w_row - (p.win_left < 0 ? (1 << 30) : p.win_left + base), hi = w_row + (p.win_right < 0 ? (1 << 30) : p.win_right - base);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sacc[e] = (e & 3) + 8 * (e >> 2) >= lo && (e & 3) + 8 * (e >> 2) <= hi ? sacc[e] : -INFINITY;
+  };
+  // WIN, PRE: what a lane's maximum must exceed for the reference to move: 2^THR once the row has met a finite score, anything before
+  float gate = -INFINITY;
   f32x16 o_acc[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -521,8 +559,16 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   // (Tried and not kept: 1..8 scores of every half exponentiated one part later, in part A of the next step.  It paid with a key-mask
   // branch in every step, profiles/r4g_*; with the one-block step none deferred is best, profiles/r4ab_*.)
   auto stepA = [&](int g, f32x16& s_cur, f32x16& s_nxt, auto mask_c) __attribute__((always_inline)) {
+    if constexpr (WIN) {
+      const int tg = t0 + (g >> 1);
+      if (tg < ti_lo || tg > ti_hi) {      // ONE uniform branch, as mask_half is in the general instances: interior tiles run unmasked
+        mask_half(g, s_cur);               // (the ragged last tile is not interior)
+        mask_window(g, s_cur);
+      }
+    } else {
     if constexpr (FULL && decltype(mask_c)::value) mask_shift(g, s_cur);
     mask_half(g, s_cur);             // keys past Lk -> -inf (uniform branch, only taken in the last tile)
+    }
     qk_mma(IC<0>{}, kf_pre, s_nxt);
     const float m0 = vmax8(s_cur[0], s_cur[1], s_cur[2], s_cur[3], s_cur[4], s_cur[5], s_cur[6], s_cur[7]);
     const float m1 = vmax8(s_cur[8], s_cur[9], s_cur[10], s_cur[11], s_cur[12], s_cur[13], s_cur[14], s_cur[15]);
@@ -532,11 +578,19 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     if constexpr (PRE) {
       // ---- deferred rescale (always taken for half 0, which sets the reference to the first row maximum): O, l, the pending
       // P(g-1), the scores of this half and the already started chain of the next half all move to the new reference
-      const bool first = !FIRST_IN_PROLOGUE && g == 0;       // FULL: the first reference is set in the prologue
-      if (first || __any(mloc > RESCALE_THR_LOG2)) {            // relative to ref
+      const bool first = !WIN && !FIRST_IN_PROLOGUE && g == 0;       // FULL: the first reference is set in the prologue
+      if (WIN ? __any(mloc > gate) : first || __any(mloc > RESCALE_THR_LOG2)) {            // relative to ref
         const float mx = pair_max(mloc);
-        const float delta = first ? mx : fmaxf(mx, 0.f);
-        const float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
+        float delta = first ? mx : fmaxf(mx, 0.f);
+        float alpha = first ? 1.f : __builtin_amdgcn_exp2f(-delta);
+        if constexpr (WIN) {
+          // a row that has met no finite score yet (O = l = P = 0, reference 0) takes its first maximum as the reference, as `first` does
+          // for every row of half 0; it stays unset while that maximum is -inf
+          const bool started = gate > -INFINITY, live = mx > -INFINITY;
+          delta = started ? delta : live ? mx : 0.f;
+          alpha = started ? alpha : 1.f;
+          gate = started || live ? RESCALE_THR_LOG2 : -INFINITY;
+        }
         ref += delta;
         l_run *= alpha;
 #pragma unroll
@@ -559,7 +613,8 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
       if (__any((mloc - m_run) * c > RESCALE_THR_LOG2)) {
         const float mx = pair_max(mloc);
         const float m_new = fmaxf(m_run, mx);
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * c);
+        // (WIN: a row all of whose scores so far are masked keeps m = -inf; -inf - -inf is not a factor)
+        const float alpha = WIN && m_new == -INFINITY ? 1.f : __builtin_amdgcn_exp2f((m_run - m_new) * c);
         l_run *= alpha;
         m_run = m_new;
 #pragma unroll
@@ -580,7 +635,7 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
     qk_part(IC<((g8 + 1) & 7)>{}, IC<4>{}, s_nxt);      // (its four K fragments read at the end of part A instead: -0.2 %, profiles/r4g)
     pv_half(IC<((g8 + 7) & 7)>{});
     qk_read(IC<((g8 + 2) & 7)>{}, IC<0>{}, kf_pre);          // for the next step's part A
-    const float mc = PRE ? 0.f : m_run * c;
+    const float mc = PRE ? 0.f : WIN && m_run == -INFINITY ? 0.f : m_run * c;      // (WIN: such a row holds -inf scores only: exp2(-inf) = 0)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const float pv = PRE ? __builtin_amdgcn_exp2f(s_cur[e]) : __builtin_amdgcn_exp2f(__builtin_fmaf(s_cur[e], c, -mc));
@@ -666,6 +721,11 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) {
   store_output(p, o_acc, 1.0f / l_tot, b, head, q0 + r, h);
   }   // q blocks of this workgroup
 }
+template <int KIND, bool PRE, bool FULL = false, bool SHORT = false>
+__global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) { attn_fwd_body<KIND, PRE, FULL, SHORT, false>(p); }
+// The windowed instances (a name of their own: the profiler and tools/kernel_resources.py tell them from the six above)
+template <bool PRE>
+__global__ __launch_bounds__(NT, 2) void attn_window_kernel(AttnParams p) { attn_fwd_body<0, PRE, false, false, true>(p); }
 
 #include "attn_fp8.inc"
 
@@ -721,17 +781,20 @@ struct AttnCall {
   const void *q8 = nullptr, *qs = nullptr, *kv8 = nullptr;   // MXFP8 operands (flexam_attn_fp8_pack) instead of q / k / v
   int kv8_chunk_tiles = 0;                     // 0 = one chunk holds all key tiles
   const float* o_shift = nullptr;              // MXFP8 only (flexam_attn_fwd_fp8_oshift): see AttnParams::o_shift
+  int win_left = -1, win_right = -1;           // flexam_attn_fwd_window: see AttnParams::win_left; a negative side is unbounded
 };
-// The eight instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
+// The ten instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
 struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
-constexpr int ATTN_INSTANCES = 8;
-AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx) {
+constexpr int ATTN_INSTANCES = 10;
+AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx, bool window) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES, F8 = NSLOT * REC_BYTES;
   static const AttnInstance table[ATTN_INSTANCES] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
                                         {attn_fwd_kernel<1, true>, BF, 3}, {attn_fwd_kernel<0, true, true>, BF, 4},
                                         {attn_fwd_kernel<1, true, false, true>, BF, 5}, {attn8_fwd_kernel<0>, F8, 6},
-                                        {attn8_oshift_kernel, F8, 7}};      // the MXFP8 kernel that adds AttnParams::o_shift (smooth-V)
+                                        {attn8_oshift_kernel, F8, 7},      // the MXFP8 kernel that adds AttnParams::o_shift (smooth-V)
+                                        {attn_window_kernel<false>, BF, 8}, {attn_window_kernel<true>, BF, 9}};      // sliding window (bf16)
+  if (window) return table[prescaled ? 9 : 8];
   return table[fp8 ? (oshift ? 7 : 6) : full ? 4 : short_ctx ? 5 : (cross ? 1 : 0) + (prescaled ? 2 : 0)];
 }
 // FLEXAM_ATTN_FULL / _SHORT / _FUSED_TAIL, read per call (A/B in one process): 0 = the general instance / one workgroup per q block / two launches
@@ -772,14 +835,20 @@ int attn_run(const AttnCall& c) {
   p.partial = 0; p.slot0 = 0; p.n_slots = S; p.whole_units = 0;
   p.q8 = (const unsigned char*)c.q8; p.qs = (const unsigned*)c.qs; p.kv8 = (const unsigned char*)c.kv8; p.lq_pad = p.q_blocks * QBLK;
   p.kv8_chunk_tiles = c.kv8_chunk_tiles > 0 ? c.kv8_chunk_tiles : tiles_all; p.o_shift = c.o_shift;
+  // a side that reaches past the sequence from every row is no bound; no bound at all is the ordinary call, launch for launch
+  const int win_left = c.win_left < 0 || c.win_left >= c.Lk - 1 ? -1 : c.win_left, win_right = c.win_right < 0 || c.win_right >= c.Lk - 1 ? -1 : c.win_right;
+  const bool window = win_left >= 0 || win_right >= 0;
+  FX_REQUIRE(!window || (c.Lq == c.Lk && !c.q8 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
+             "attn_fwd: a window goes with bf16 operands of one length and whole work units");
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
+  if (window) { p.win_left = win_left; p.win_right = win_right; }      // (in the words of the two MXFP8 chunk fields above: see AttnParams)
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
   const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
-  const bool short_ctx = !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
-  const bool full = !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
-  const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx);
+  const bool short_ctx = !window && !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
+  const bool full = !window && !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
+  const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window);
   static bool attr_set[FLEXAM_MAX_DEVICES][ATTN_INSTANCES] = {};      // per device and kernel instance
   bool& lds_raised = attr_set[flexam_current_device()][inst.slot];
   if (!lds_raised) {
@@ -828,6 +897,16 @@ extern "C" int flexam_attn_fwd(const void* q, int64_t q_bs, int64_t q_rs, const 
   AttnCall c;
   c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
   c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  return attn_run(c);
+}
+
+extern "C" int flexam_attn_fwd_window(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
+                                      const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
+                                      int L, int head_dim, float softmax_scale, int window_left, int window_right, void* stream) {
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  c.win_left = window_left; c.win_right = window_right;
   return attn_run(c);
 }
 

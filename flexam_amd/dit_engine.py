@@ -71,6 +71,7 @@ class DiTEngine:
     _sage_warned = False
     _smooth_k_warned = False
     _smooth_v_warned = False
+    _sage_window_warned = False
 
     def __init__(self, model):
         self.model = model
@@ -81,6 +82,9 @@ class DiTEngine:
         self.patch = tuple(c["patch_size"])
         self.out_dim, self.in_dim = c["out_dim"], c["in_dim"]
         self.text_len, self.freq_dim = c["text_len"], c["freq_dim"]
+        # flash-attn's (left, right) window of the self-attention in tokens, (-1, -1) = none (the model's window_size, as the reference's
+        # WanSelfAttention hands it to its kernel); kept beside the mode like smooth-K / smooth-V, and part of a launch plan's key
+        self.window = hip.attn_window(c["window_size"])
         if self.hd != hip.ATTN_HEAD_DIM:
             raise RuntimeError(f"flexam_amd: head_dim {self.hd} unsupported by the HIP attention kernel ({hip.ATTN_HEAD_DIM} only)")
         if self.patch != (1, 2, 2):
@@ -384,6 +388,10 @@ class DiTEngine:
         """The mode of one forward (see _Mode).  Every environment switch a forward reads is read here, once per forward: tests and
         benchlib flip them between forwards."""
         cd, env = self.cond, os.environ
+        window = getattr(self, "window", (-1, -1))         # (tests/test_smooth_k_mode_cpu.py resolves modes on a bare namespace)
+        if window != (-1, -1) and self.sp_size > 1:
+            raise NotImplementedError("flexam_amd: window_size under sequence parallelism is not served: a rank's queries and the keys it "
+                                      "gathers carry global token indices, which the windowed kernel does not take")
         m = resolve_mode(env, fused=self.fused, nl=self.nl, nh=self.nh, hd=self.hd, dim=self.dim, table_limit=self.table_limit, fp8=self.fp8,
                          sp=self.sp_size, rank=self.sp_rank,
                          parallel=(self.sp_mode, self.sp_overlap_level, self.sp_pieces, self.sp_fused_qkv),
@@ -414,6 +422,14 @@ class DiTEngine:
             import warnings
             warnings.warn("flexam_amd: FLEXAM_SAGE_SMOOTH_V=1 is ignored under sequence parallelism: V is quantised as it is",
                           RuntimeWarning, stacklevel=3)
+        if window != (-1, -1) and m.sage:                  # the MXFP8 kernel has no mask: the windowed bf16 kernel runs
+            m = m._replace(sage=False, sage_gather=False, sage_fused=False)
+            self._smooth_k = self._smooth_v = False
+            if not DiTEngine._sage_window_warned:          # said once per process
+                DiTEngine._sage_window_warned = True
+                import warnings
+                warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored with window_size: self-attention runs the windowed "
+                              "bf16 kernel", RuntimeWarning, stacklevel=3)
         return m
 
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
@@ -526,7 +542,7 @@ class DiTEngine:
         address they carry.  Not with TeaCache (data-dependent skipping), per-layer tables or blocks called as modules (_Mode.use_plan)."""
         cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
         key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
-               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), self._smooth_v, self._smooth_k)
+               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), getattr(self, "window", (-1, -1)), self._smooth_v, self._smooth_k)
         plans = cd.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -647,7 +663,10 @@ class DiTEngine:
             hip.attn_fwd_fp8(bufs, m.lc, out=ao4[:nb], o_shift=v_mean)
         else:
             self._norm_rope_qk(p, m, ws, nb)
-            hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)
+            if self.window != (-1, -1):
+                hip.attn_fwd_window(q4[:nb], k4[:nb], v4[:nb], self.window, out=ao4[:nb], prescaled=True)
+            else:
+                hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)
         self._out_proj(i, p, "wo", "bo", ws["ao"][:mb], ws, mb, m.fp8_oproj, **gate)
         if nb < m.B:
             xr = ws["x"].view(m.B, m.lc, d)

@@ -536,6 +536,42 @@ def attn_fwd(q, k, v, out=None, softmax_scale=None, kv_splits=None, split_from_u
     return out
 
 
+def attn_window(window, causal=False):
+    """(left, right) of flash-attn's mask as two ints, a negative side written -1; causal sets right = 0 as flash-attn does."""
+    left, right = (int(w) for w in window)
+    return (left if left >= 0 else -1), (0 if causal else right if right >= 0 else -1)
+
+
+def attn_window_tiles(L: int, window):
+    """Per block of ATTN_Q_BLOCK query rows the (first, last) key tile the windowed kernel visits: the tiles that hold a key some row of
+    the block sees.  window = (left, right), a negative side unbounded: row i sees key j iff j >= i - left and j <= i + right.  The rows'
+    intervals overlap from row to row, so their union is one range of keys: from the first row's first key to the last row's last."""
+    left, right = attn_window(window)
+    out = []
+    for q0 in range(0, L, ATTN_Q_BLOCK):
+        q1 = min(q0 + ATTN_Q_BLOCK, L) - 1
+        first = 0 if left < 0 else max(0, q0 - left)
+        last = L - 1 if right < 0 else min(L - 1, q1 + right)
+        out.append((first // ATTN_KV_TILE, last // ATTN_KV_TILE))
+    return out
+
+
+def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False):
+    """attn_fwd under flash-attn's sliding-window mask (see flexam_hip.h): q, k, v [B, L, H, 128] bf16 with the layouts of attn_fwd and
+    ONE length L; window = (left, right), a negative side unbounded, (-1, -1) the ordinary call.  Whole work units only (no split-KV)."""
+    B, L, H, D = q.shape
+    if k.shape[1] != L or v.shape[1] != L:
+        raise RuntimeError(f"attn_fwd_window: queries and keys share one length (Lq = {L}, Lk = {k.shape[1]})")
+    _packed_heads("attn_fwd_window", q, k, v)
+    if out is None:
+        out = torch.empty(B, L, H, D, device=q.device, dtype=BF16)
+    left, right = attn_window(window)
+    _call("flexam_attn_fwd_window", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D, _softmax_scale(softmax_scale, prescaled, D),
+          left, right)
+    return out
+
+
 def attn_partial_workspace(B, H, Lq, n_slots, device):
     return _partials(n_slots, attn_units(B * H, Lq), device)
 

@@ -156,7 +156,12 @@ class _Attn(nn.Module):
 
 class _SelfAttn(_Attn):
     """WanSelfAttention (wan_transformer3d_FlexAM.py:205-262) on the HIP kernels: fused q|k|v GEMM, full-width RMSNorm +
-    3-axis RoPE in one pass, flash attention, output projection."""
+    3-axis RoPE in one pass, flash attention, output projection.  window_size: flash-attn's (left, right) in tokens, which the reference
+    hands to its kernel (wan_transformer3d_FlexAM.py:251-256); (-1, -1) = full attention."""
+
+    def __init__(self, dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1)):
+        super().__init__(dim, num_heads, eps)
+        self.window_size = tuple(int(w) for w in window_size)
 
     def packed(self):
         sig = self._sig()
@@ -195,7 +200,11 @@ class _SelfAttn(_Attn):
         b, l, c = x.shape
         nh, hd = self.num_heads, self.head_dim
         sp = current_sp_context()
+        window = hip.attn_window(self.window_size)
         if sp is not None and sp["size"] > 1:
+            if window != (-1, -1):
+                raise NotImplementedError("flexam_amd: window_size under sequence parallelism is not served (a rank's queries are a chunk of "
+                                          "the sequence: the window would have to follow their global indices)")
             return self._forward_chunk(x, seq_lens, sp)
         # A caller that hands over a PADDED sequence (FX.py:918-925: zero tokens behind seq_lens[b] real ones, the same count for every
         # sample) gets flash-attention's semantics: the pads are no keys (k_lens, FX.py:251-256 -> ATT.py:87-95); their own rows are
@@ -214,7 +223,12 @@ class _SelfAttn(_Attn):
                          tokens_per_batch=l, token_offset=0, head_dim=hd)
         q3 = qkv.view(b, l, 3 * c)
         q4, k4, v4 = (q3[:, :, i * c:(i + 1) * c].unflatten(2, (nh, hd)) for i in range(3))
-        if n_keys < l:
+        if window != (-1, -1):
+            if n_keys < l:
+                raise NotImplementedError("flexam_amd: window_size with seq_lens shorter than the sequence is not served: flash-attn aligns "
+                                          "the mask of Lq != Lk bottom-right, SDPA top-left")
+            ao = hip.attn_fwd_window(q4, k4, v4, window, prescaled=True)      # (SAGE_ATTENTION too: the MXFP8 kernel has no mask)
+        elif n_keys < l:
             ao = hip.attn_fwd(q4, k4[:, :n_keys], v4[:, :n_keys], prescaled=True)
         elif os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION" and not torch.is_grad_enabled() and hd == 128:
             # the reference's attention() reads the switch per call (ATT.py:195-203); FLEXAM_SAGE_SMOOTH_K=1: K - mean_tokens(K) is quantised;
@@ -323,10 +337,10 @@ class _Block(nn.Module):
     wan_transformer3d_FlexAM.py:807-815): same signature, it calls `self.self_attn` / `self.cross_attn` as modules so a
     re-bound attention forward takes effect, and the engine routes a step through it whenever a block is not pristine."""
 
-    def __init__(self, dim: int, ffn_dim: int, num_heads: int = None, eps: float = 1e-6):
+    def __init__(self, dim: int, ffn_dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1)):
         super().__init__()
         self.dim, self.ffn_dim, self.num_heads, self.eps = dim, ffn_dim, num_heads, eps
-        self.self_attn, self.cross_attn = _SelfAttn(dim, num_heads, eps), _CrossAttn(dim, num_heads, eps)
+        self.self_attn, self.cross_attn = _SelfAttn(dim, num_heads, eps, window_size), _CrossAttn(dim, num_heads, eps)      # (cross-attention: no window, as in the reference)
         self.norm3 = _Norm(dim, bias=True, eps=eps)
         self.ffn = nn.Sequential(_holder(ffn_dim, dim), nn.GELU(approximate="tanh"), _holder(dim, ffn_dim))
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
@@ -435,17 +449,16 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         cfg.pop("self")
         cfg.pop("__class__", None)
         cfg["patch_size"] = tuple(patch_size)
+        cfg["window_size"] = tuple(int(w) for w in window_size)
         self.config = ModelConfig(cfg)
         if add_control_adapter:
             raise NotImplementedError("control_adapter (camera branch) is not part of the FlexAM 5B path (SURVEY section 2)")
         if not (qk_norm and cross_attn_norm):
             raise NotImplementedError("FlexAM 5B uses qk_norm and cross_attn_norm; other variants are out of scope")
-        if tuple(window_size) != (-1, -1):
-            raise NotImplementedError("windowed attention is not used by FlexAM")
         if cross_attn_type not in (None, "cross_attn"):
             raise NotImplementedError(f"cross_attn_type {cross_attn_type}: only the text cross-attention of Wan2.2 is implemented")
         for k in ("model_type", "patch_size", "text_len", "in_dim", "dim", "ffn_dim", "freq_dim", "text_dim", "out_dim", "num_heads",
-                  "num_layers", "eps"):
+                  "num_layers", "eps", "window_size"):
             setattr(self, k, self.config[k])
         pt, ph, pw = self.patch_size
         self.patch_embedding = nn.Conv3d(in_dim, dim, kernel_size=self.patch_size, stride=self.patch_size)
@@ -454,7 +467,7 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         self.time_projection = nn.Sequential(nn.SiLU(), _holder(dim * 6, dim))
         self.density_embedding = nn.Sequential(_holder(dim, freq_dim), nn.SiLU(), _holder(dim, dim))
         self.density_projection = nn.Sequential(nn.SiLU(), _holder(dim * 2, dim))
-        self.blocks = nn.ModuleList([_Block(dim, ffn_dim, num_heads, eps) for _ in range(num_layers)])
+        self.blocks = nn.ModuleList([_Block(dim, ffn_dim, num_heads, eps, self.window_size) for _ in range(num_layers)])
         self.head = _Head(dim, pt * ph * pw * out_dim, eps)
         self.d = dim // num_heads
         self.ref_conv = nn.Conv2d(in_dim_ref_conv, dim, kernel_size=(ph, pw), stride=(ph, pw)) if add_ref_conv else None

@@ -139,7 +139,17 @@ int flexam_attn_fwd(const void* q, int64_t q_bs, int64_t q_rs, const void* k, in
 int flexam_attn_fwd_lastkey(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                             int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int Lk,
                             int head_dim, float softmax_scale, float last_key_multiplicity, void* stream);
-/* Same, with the work units u = (batch*H + head)*ceil(Lq/256) + q_block at and after `split_from_unit` cut into kv_splits key
+/* flexam_attn_fwd over ONE length L (Lq = Lk) under flash-attn's sliding-window mask, which the reference hands to its kernel
+ * (attention_utils.py:43-171: flash_attn_varlen_func(..., causal=, window_size=)): query i sees key j iff
+ * (window_left < 0 or j >= i - window_left) and (window_right < 0 or j <= i + window_right); a negative side is unbounded, causal is
+ * window_right = 0, and (-1, -1) -- or a window no shorter than the sequence on both sides -- is flexam_attn_fwd itself.  Every row sees
+ * at least itself.  A work unit visits only the key tiles that hold a key one of its 256 rows sees, and masks only those of them that
+ * hold a key one of its rows does not see; whole units only (no split-KV).  softmax_scale as flexam_attn_fwd takes it,
+ * FLEXAM_ATTN_PRESCALED included. */
+int flexam_attn_fwd_window(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                           int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L, int head_dim,
+                           float softmax_scale, int window_left, int window_right, void* stream);
+/* flexam_attn_fwd with the work units u =(batch*H + head)*ceil(Lq/256) + q_block at and after `split_from_unit` cut into kv_splits key
  * ranges each (flash-decoding style partial softmaxes + a merge launch), the units before it in one pass: with
  * split_from_unit = floor(units/256)*256 only the last, partial round of the 256 CUs is split; 0 splits everything (ranks of a
  * sequence-parallel run hold few query rows).  ws_o: fp32 [kv_splits, n, 256, 128], ws_ml: fp32 [kv_splits, n, 256, 2] scratch
