@@ -63,7 +63,9 @@ struct AttnParams {
   const unsigned char* q8;   // [B][H][lq_pad][128] e4m3
   const unsigned* qs;        // [B][H][lq_pad] four E8M0 bytes per row
   const unsigned char* kv8;  // [B][H][ceil(Lk / 64)] records of REC_BYTES -- or, in chunks of kv8_chunk_tiles key tiles, [chunk][B][H][kv8_chunk_tiles]
-  int lq_pad;
+  // (attn_window_kernel reads this word as its sink, the way it reads the two chunk words below as its window: the first win_sink keys
+  //  are visible to EVERY row, whatever win_right says -- the model is not causal.  Row i sees key j iff j < win_sink or j is in its window)
+  union { int lq_pad; int win_sink; };
   // key tile g lives in chunk g / kv8_chunk_tiles (flexam_attn_fwd_fp8_chunked: the rank-major result of a sequence-parallel all-gather of
   // every rank's records; one chunk = all tiles for the plain call); kv8_chunk_magic = ceil(2^32 / kv8_chunk_tiles) turns the division
   // into one s_mul_hi_u32 (exact for g, tiles < 2^16)
@@ -276,6 +278,12 @@ __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (
 // mask_shift (a lane holds 32 scores of ONE row).  Rows of a wave may see no key at all in the first tiles of the unit (the unit's range
 // is the union over its rows): a row's reference stays unset until its first finite score, and the rescale factors are guarded against
 // inf - inf.  Units of a window without a left bound grow with the q block: the q blocks of a head are walked backwards, longest first.
+// Sink (win_sink > 0, flexam_attn_fwd_window_sink): the first win_sink keys are visible to every row whatever the window says, the right
+// side included -- the model is not causal.  The unit then walks the sink tiles and the window tiles (see global_tile below); a tile wholly
+// below the sink is interior, the tile that holds key win_sink - 1 takes the per-lane mask `key < win_sink or in the window`.  Behind the
+// sink tiles a row HAS started, and the first window tiles of the unit may again hold no key it sees: such a half tile is all -inf for the
+// row, its maximum moves neither reference (PRE: delta = max(-inf, 0) = 0, alpha = 1; else m_new = m_run, alpha = exp2(0)) and its
+// exp2(-inf) terms add exactly 0 -- the same guards, no new case.
 // (The one-block step of FULL for runs of interior tiles, next to the general step for the edges, was built and not kept: two step
 //  bodies in one loop cost hipcc 70 (scale in kernel) to 330 (PRE) spilled VGPRs, and a loop for each does not fit the instruction cache.)
 template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN>
@@ -326,22 +334,32 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   // ---- LDS-DMA staging: piece id = tid + 512*i (i < 2) lands at LDS byte id*16 of the tile, i.e. row id/16,
   //      slot id%16; it must carry chunk (slot ^ swizzle(row)) of that key row
   const int tiles_all = (p.Lk + KVBLK - 1) / KVBLK;
-  // WIN: the unit's key tiles [w_t0, w_t0 + w_n) and, of them, the interior tiles [ti_lo, ti_hi] (global indices) every row sees whole
-  int w_t0 = 0, w_n = 0, ti_lo = 0, ti_hi = 0;
+  // WIN: the unit's w_n key tiles and, of them, the window's interior tiles [ti_lo, ti_hi] (local indices) every row sees whole.
+  // With a sink (the first win_sink keys, visible to every row) the walk is the union of the sink tiles [0, s_n) and the window tiles: ONE
+  // run when they touch or overlap, else two runs with `gap` tiles between them that no row sees.  Tiles stay indexed locally (loop, ring,
+  // 4-unroll); the global tile of local tile t is t below s_n and t + gap from there on (hip.attn_window_sink_tiles states the same rule).
+  // Without a sink s_n = 0 and gap is the window's first tile.  s_full: the tiles wholly below win_sink, interior for every row.
+  int w_n = 0, ti_lo = 0, ti_hi = 0, s_n = 0, s_full = 0, gap = 0;
   if constexpr (WIN) {
     int qb = unit % p.q_blocks;
     if (p.win_left < 0) qb = p.q_blocks - 1 - qb;
     const int qa = qb * QBLK, qz = min(qa + QBLK, p.Lq) - 1;      // first and last row of the unit
     const int k_first = p.win_left < 0 ? 0 : max(0, qa - p.win_left);
     const int k_last = p.win_right < 0 ? p.Lk - 1 : min(p.Lk - 1, qz + p.win_right);
-    w_t0 = k_first / KVBLK;
-    w_n = k_last / KVBLK - w_t0 + 1;
+    s_n = (min(p.win_sink, p.Lk) + KVBLK - 1) / KVBLK;
+    s_full = p.win_sink / KVBLK;
+    gap = max(0, k_first / KVBLK - s_n);
+    w_n = max(k_last / KVBLK, s_n - 1) + 1 - gap;
     ti_lo = p.win_left < 0 ? 0 : (max(0, qz - p.win_left) + KVBLK - 1) / KVBLK;      // its first key is the last row's first or later
     const int top_key = qa + p.win_right - (KVBLK - 1);                              // its last key is the first row's last or sooner
     ti_hi = min(p.win_right < 0 ? tiles_all : top_key >= 0 ? top_key / KVBLK : -1, p.Lk / KVBLK - 1);      // (whole tiles only)
+    // as local indices, for the test in front of part A: the window's interior tiles lie at or behind its first tile, so behind the gap
+    ti_lo -= gap;
+    ti_hi -= gap;
   }
-  const int t0 = WIN ? w_t0 : split * tps;                         // first key tile of this split (0 without split-KV)
-  const int ntiles = WIN ? w_n : min(tps, tiles_all - t0);       // tiles are indexed locally below; t0 + t is the global tile
+  const int t0 = WIN ? 0 : split * tps;                            // first key tile of this split (0 without split-KV)
+  const int ntiles = WIN ? w_n : min(tps, tiles_all - t0);       // tiles are indexed locally below; global_tile(t) is the global tile
+  auto global_tile = [&](int t) { return WIN ? (t < s_n ? t : t + gap) : t0 + t; };      // (WIN: one wave-uniform select)
   const unsigned k_step = (unsigned)(KVBLK * p.k_rs * 2), v_step = (unsigned)(KVBLK * p.v_rs * 2);
   unsigned k_go[2], v_go[2];
 #pragma unroll
@@ -354,7 +372,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   const unsigned lds0 = (unsigned)(size_t)LDS_PTR(smem);
   auto issue_tile = [&](int t, int parts = 3, int tslot = -1) {      // parts: 1 = K, 2 = V; tslot: ring position (default t)
     const unsigned slot = lds0 + (unsigned)(((tslot < 0 ? t : tslot) & (NSLOT - 1)) * KV_TILE_BYTES + wave * 1024);   // wave-uniform; K ring, V ring = + V_RING
-    const int tg = t0 + t;
+    const int tg = global_tile(t);
     if (FULL || (tg + 1) * KVBLK <= p.Lk) {
       // FULL: the last tile is the window [Lk - 64, Lk) (scalar select, no branch)
       const unsigned row0 = FULL && tg == tiles_all - 1 ? (unsigned)(p.Lk - KVBLK) : (unsigned)tg * KVBLK;
@@ -451,7 +469,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   };
   auto mask_half = [&](int g, f32x16& sacc) {      // g: local half index; keys are global
     if constexpr (FULL) return;
-    const int gg = 2 * t0 + g;
+    const int gg = WIN ? 2 * global_tile(g >> 1) + (g & 1) : 2 * t0 + g;
     // past the end of the keys, or of this split's range -- or the half tile that holds a weighted last key
     if ((gg + 1) * 32 > p.Lk || g >= 2 * ntiles || (p.last_key_bias != 0.f && (gg + 1) * 32 == p.Lk)) {
 #pragma unroll
@@ -464,12 +482,19 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   };
   // WIN: keys outside the window of this lane's row -> -inf.  Element e is key 32 gg + 4 h + (e & 3) + 8 (e >> 2) of global half gg: seen iff
   // that lies in [row - left, row + right]: one per-lane value, the bounds' other terms are uniform.  Called in the tiles that are not interior only.
+  // The sink: or that key lies below win_sink (`sk`: uniform but for the lane half; never true without a sink).
+  // (the three bounds less `base` are kept per lane: as uniform values next to s_n, gap and s_full they cost the loop 40 SGPR lane reloads)
   const int w_row = q0 + r - 4 * h;
+  const int w_lo = w_row - (p.win_left < 0 ? (1 << 30) : p.win_left), w_hi = w_row + (p.win_right < 0 ? (1 << 30) : p.win_right), w_sk = p.win_sink - 4 * h;
   auto mask_window = [&](int g, f32x16& sacc) {
-    const int base = (2 * t0 + g) * 32;
-    const int lo = w_row - (p.win_left < 0 ? (1 << 30) : p.win_left + base), hi = w_row + (p.win_right < 0 ? (1 << 30) : p.win_right - base);
+    const int base = (2 * global_tile(g >> 1) + (g & 1)) * 32;
+    const int lo = w_lo - base, hi = w_hi - base, sk = w_sk - base;
+    // the lane's visible in-half positions as one bit mask (positions 0 .. 27 occur): [0, sk) or [lo, hi].  As three compares per element
+    // hipcc turns the `or` into an exec-mask branch per element (+2700 instructions in the kernel)
+    const unsigned below_sk = (1u << min(max(sk, 0), 28)) - 1u, below_lo = (1u << min(max(lo, 0), 28)) - 1u, to_hi = (1u << min(max(hi + 1, 0), 28)) - 1u;
+    const unsigned seen = below_sk | (to_hi & ~below_lo);
 #pragma unroll
-    for (int e = 0; e < 16; ++e) sacc[e] = (e & 3) + 8 * (e >> 2) >= lo && (e & 3) + 8 * (e >> 2) <= hi ? sacc[e] : -INFINITY;
+    for (int e = 0; e < 16; ++e) sacc[e] = seen & (1u << ((e & 3) + 8 * (e >> 2))) ? sacc[e] : -INFINITY;
   };
   // WIN, PRE: what a lane's maximum must exceed for the reference to move: 2^THR once the row has met a finite score, anything before
   float gate = -INFINITY;
@@ -560,8 +585,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   // branch in every step, profiles/r4g_*; with the one-block step none deferred is best, profiles/r4ab_*.)
   auto stepA = [&](int g, f32x16& s_cur, f32x16& s_nxt, auto mask_c) __attribute__((always_inline)) {
     if constexpr (WIN) {
-      const int tg = t0 + (g >> 1);
-      if (tg < ti_lo || tg > ti_hi) {      // ONE uniform branch, as mask_half is in the general instances: interior tiles run unmasked
+      const int tl = g >> 1;               // (local: a tile below s_full is its own global index)
+      // ONE uniform branch, as mask_half is in the general instances: interior tiles -- of the window, or wholly below the sink -- run unmasked
+      if (tl >= s_full && (tl < ti_lo || tl > ti_hi)) {
         mask_half(g, s_cur);               // (the ragged last tile is not interior)
         mask_window(g, s_cur);
       }
@@ -782,6 +808,7 @@ struct AttnCall {
   int kv8_chunk_tiles = 0;                     // 0 = one chunk holds all key tiles
   const float* o_shift = nullptr;              // MXFP8 only (flexam_attn_fwd_fp8_oshift): see AttnParams::o_shift
   int win_left = -1, win_right = -1;           // flexam_attn_fwd_window: see AttnParams::win_left; a negative side is unbounded
+  int win_sink = 0;                            // flexam_attn_fwd_window_sink: see AttnParams::win_sink
 };
 // The ten instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
@@ -837,12 +864,15 @@ int attn_run(const AttnCall& c) {
   p.kv8_chunk_tiles = c.kv8_chunk_tiles > 0 ? c.kv8_chunk_tiles : tiles_all; p.o_shift = c.o_shift;
   // a side that reaches past the sequence from every row is no bound; no bound at all is the ordinary call, launch for launch
   const int win_left = c.win_left < 0 || c.win_left >= c.Lk - 1 ? -1 : c.win_left, win_right = c.win_right < 0 || c.win_right >= c.Lk - 1 ? -1 : c.win_right;
-  const bool window = win_left >= 0 || win_right >= 0;
+  FX_REQUIRE(c.win_sink >= 0, FLEXAM_E_ARG, "attn_fwd: negative sink %d", c.win_sink);
+  // a sink that holds every key leaves no mask; one under a window without a left bound (nothing lies to the left of it) adds no key
+  const bool window = (win_left >= 0 || win_right >= 0) && c.win_sink < c.Lk;
+  const int win_sink = win_left < 0 ? 0 : c.win_sink;
   FX_REQUIRE(!window || (c.Lq == c.Lk && !c.q8 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
              "attn_fwd: a window goes with bf16 operands of one length and whole work units");
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
-  if (window) { p.win_left = win_left; p.win_right = win_right; }      // (in the words of the two MXFP8 chunk fields above: see AttnParams)
+  if (window) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; }      // (in the words of three MXFP8 fields above: see AttnParams)
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
   const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
@@ -907,6 +937,16 @@ extern "C" int flexam_attn_fwd_window(const void* q, int64_t q_bs, int64_t q_rs,
   c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
   c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
   c.win_left = window_left; c.win_right = window_right;
+  return attn_run(c);
+}
+
+extern "C" int flexam_attn_fwd_window_sink(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
+                                           const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
+                                           int L, int head_dim, float softmax_scale, int window_left, int window_right, int sink, void* stream) {
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  c.win_left = window_left; c.win_right = window_right; c.win_sink = sink;
   return attn_run(c);
 }
 

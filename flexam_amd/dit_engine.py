@@ -85,6 +85,8 @@ class DiTEngine:
         # flash-attn's (left, right) window of the self-attention in tokens, (-1, -1) = none (the model's window_size, as the reference's
         # WanSelfAttention hands it to its kernel); kept beside the mode like smooth-K / smooth-V, and part of a launch plan's key
         self.window = hip.attn_window(c["window_size"])
+        # under a window: the first window_sink tokens stay visible to every query (the model's window_sink); in the plan's key too
+        self.window_sink = int(c["window_sink"])
         if self.hd != hip.ATTN_HEAD_DIM:
             raise RuntimeError(f"flexam_amd: head_dim {self.hd} unsupported by the HIP attention kernel ({hip.ATTN_HEAD_DIM} only)")
         if self.patch != (1, 2, 2):
@@ -542,7 +544,8 @@ class DiTEngine:
         address they carry.  Not with TeaCache (data-dependent skipping), per-layer tables or blocks called as modules (_Mode.use_plan)."""
         cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
         key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
-               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), getattr(self, "window", (-1, -1)), self._smooth_v, self._smooth_k)
+               torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), getattr(self, "window", (-1, -1)), getattr(self, "window_sink", 0),
+               self._smooth_v, self._smooth_k)
         plans = cd.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -664,7 +667,7 @@ class DiTEngine:
         else:
             self._norm_rope_qk(p, m, ws, nb)
             if self.window != (-1, -1):
-                hip.attn_fwd_window(q4[:nb], k4[:nb], v4[:nb], self.window, out=ao4[:nb], prescaled=True)
+                hip.attn_fwd_window(q4[:nb], k4[:nb], v4[:nb], self.window, out=ao4[:nb], prescaled=True, sink=self.window_sink)
             else:
                 hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)
         self._out_proj(i, p, "wo", "bo", ws["ao"][:mb], ws, mb, m.fp8_oproj, **gate)

@@ -556,9 +556,29 @@ def attn_window_tiles(L: int, window):
     return out
 
 
-def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False):
+def attn_window_sink_tiles(L: int, window, sink: int):
+    """attn_window_tiles with the first `sink` keys visible to every row (row i sees key j iff j < sink or j is in its window): per block
+    of ATTN_Q_BLOCK query rows the list of (first, last) key-tile runs the windowed kernel walks -- the sink tiles [0, (sink - 1) // 64]
+    and the window tiles of attn_window_tiles, as ONE run where they touch or overlap and as two runs with a gap otherwise."""
+    if sink < 0:
+        raise ValueError(f"attn_window_sink_tiles: negative sink {sink}")
+    n_sink = -(-min(sink, L) // ATTN_KV_TILE)                  # the sink tiles are [0, n_sink)
+    out = []
+    for first, last in attn_window_tiles(L, window):
+        if n_sink == 0:
+            out.append([(first, last)])
+        elif n_sink >= first:
+            out.append([(0, max(last, n_sink - 1))])
+        else:
+            out.append([(0, n_sink - 1), (first, last)])
+    return out
+
+
+def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0):
     """attn_fwd under flash-attn's sliding-window mask (see flexam_hip.h): q, k, v [B, L, H, 128] bf16 with the layouts of attn_fwd and
-    ONE length L; window = (left, right), a negative side unbounded, (-1, -1) the ordinary call.  Whole work units only (no split-KV)."""
+    ONE length L; window = (left, right), a negative side unbounded, (-1, -1) the ordinary call.  Whole work units only (no split-KV).
+    sink > 0: the first `sink` keys stay visible to every row whatever the window says (flexam_attn_fwd_window_sink); sink = 0 is the
+    call this function has always made."""
     B, L, H, D = q.shape
     if k.shape[1] != L or v.shape[1] != L:
         raise RuntimeError(f"attn_fwd_window: queries and keys share one length (Lq = {L}, Lk = {k.shape[1]})")
@@ -566,9 +586,13 @@ def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=Fal
     if out is None:
         out = torch.empty(B, L, H, D, device=q.device, dtype=BF16)
     left, right = attn_window(window)
-    _call("flexam_attn_fwd_window", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
-          v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D, _softmax_scale(softmax_scale, prescaled, D),
-          left, right)
+    sink = int(sink)
+    args = (_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16), v.stride(0), v.stride(1),
+            _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D, _softmax_scale(softmax_scale, prescaled, D), left, right)
+    if sink == 0:
+        _call("flexam_attn_fwd_window", *args)
+    else:
+        _call("flexam_attn_fwd_window_sink", *args, sink)
     return out
 
 

@@ -157,11 +157,13 @@ class _Attn(nn.Module):
 class _SelfAttn(_Attn):
     """WanSelfAttention (wan_transformer3d_FlexAM.py:205-262) on the HIP kernels: fused q|k|v GEMM, full-width RMSNorm +
     3-axis RoPE in one pass, flash attention, output projection.  window_size: flash-attn's (left, right) in tokens, which the reference
-    hands to its kernel (wan_transformer3d_FlexAM.py:251-256); (-1, -1) = full attention."""
+    hands to its kernel (wan_transformer3d_FlexAM.py:251-256); (-1, -1) = full attention.  window_sink: under a window, the first
+    window_sink tokens (the reference image leads the frame-major sequence) stay visible to every query; without a window it does nothing."""
 
-    def __init__(self, dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1)):
+    def __init__(self, dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1), window_sink=0):
         super().__init__(dim, num_heads, eps)
         self.window_size = tuple(int(w) for w in window_size)
+        self.window_sink = int(window_sink)
 
     def packed(self):
         sig = self._sig()
@@ -227,7 +229,7 @@ class _SelfAttn(_Attn):
             if n_keys < l:
                 raise NotImplementedError("flexam_amd: window_size with seq_lens shorter than the sequence is not served: flash-attn aligns "
                                           "the mask of Lq != Lk bottom-right, SDPA top-left")
-            ao = hip.attn_fwd_window(q4, k4, v4, window, prescaled=True)      # (SAGE_ATTENTION too: the MXFP8 kernel has no mask)
+            ao = hip.attn_fwd_window(q4, k4, v4, window, prescaled=True, sink=self.window_sink)      # (SAGE_ATTENTION too: the MXFP8 kernel has no mask)
         elif n_keys < l:
             ao = hip.attn_fwd(q4, k4[:, :n_keys], v4[:, :n_keys], prescaled=True)
         elif os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION" and not torch.is_grad_enabled() and hd == 128:
@@ -337,10 +339,10 @@ class _Block(nn.Module):
     wan_transformer3d_FlexAM.py:807-815): same signature, it calls `self.self_attn` / `self.cross_attn` as modules so a
     re-bound attention forward takes effect, and the engine routes a step through it whenever a block is not pristine."""
 
-    def __init__(self, dim: int, ffn_dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1)):
+    def __init__(self, dim: int, ffn_dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1), window_sink=0):
         super().__init__()
         self.dim, self.ffn_dim, self.num_heads, self.eps = dim, ffn_dim, num_heads, eps
-        self.self_attn, self.cross_attn = _SelfAttn(dim, num_heads, eps, window_size), _CrossAttn(dim, num_heads, eps)      # (cross-attention: no window, as in the reference)
+        self.self_attn, self.cross_attn = _SelfAttn(dim, num_heads, eps, window_size, window_sink), _CrossAttn(dim, num_heads, eps)      # (cross-attention: no window, as in the reference)
         self.norm3 = _Norm(dim, bias=True, eps=eps)
         self.ffn = nn.Sequential(_holder(ffn_dim, dim), nn.GELU(approximate="tanh"), _holder(dim, ffn_dim))
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
@@ -443,13 +445,18 @@ class WanTransformer3DModel_FlexAM(nn.Module):
                  text_dim=4096, out_dim=16, num_heads=16, num_layers=32, window_size=(-1, -1), qk_norm=True, cross_attn_norm=True,
                  eps=1e-6, in_channels=16, hidden_size=2048, add_control_adapter=False, in_dim_control_adapter=24,
                  downscale_factor_control_adapter=8, add_ref_conv=False, in_dim_ref_conv=16, cross_attn_type=None,
-                 add_cnn_block=False, in_dim_cnn_block=96, out_dim_cnn_block=16):
+                 add_cnn_block=False, in_dim_cnn_block=96, out_dim_cnn_block=16, window_sink=0):
         super().__init__()
         cfg = dict(locals())
         cfg.pop("self")
         cfg.pop("__class__", None)
         cfg["patch_size"] = tuple(patch_size)
         cfg["window_size"] = tuple(int(w) for w in window_size)
+        # not the reference's: under window_size the first window_sink tokens (the reference image, which leads the frame-major sequence)
+        # stay visible to every query of the self-attention; 0 = the plain window, and without a window it does nothing
+        cfg["window_sink"] = int(window_sink)
+        if cfg["window_sink"] < 0:
+            raise ValueError(f"window_sink {window_sink}: a count of leading tokens, 0 or more")
         self.config = ModelConfig(cfg)
         if add_control_adapter:
             raise NotImplementedError("control_adapter (camera branch) is not part of the FlexAM 5B path (SURVEY section 2)")
@@ -458,7 +465,7 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         if cross_attn_type not in (None, "cross_attn"):
             raise NotImplementedError(f"cross_attn_type {cross_attn_type}: only the text cross-attention of Wan2.2 is implemented")
         for k in ("model_type", "patch_size", "text_len", "in_dim", "dim", "ffn_dim", "freq_dim", "text_dim", "out_dim", "num_heads",
-                  "num_layers", "eps", "window_size"):
+                  "num_layers", "eps", "window_size", "window_sink"):
             setattr(self, k, self.config[k])
         pt, ph, pw = self.patch_size
         self.patch_embedding = nn.Conv3d(in_dim, dim, kernel_size=self.patch_size, stride=self.patch_size)
@@ -467,7 +474,7 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         self.time_projection = nn.Sequential(nn.SiLU(), _holder(dim * 6, dim))
         self.density_embedding = nn.Sequential(_holder(dim, freq_dim), nn.SiLU(), _holder(dim, dim))
         self.density_projection = nn.Sequential(nn.SiLU(), _holder(dim * 2, dim))
-        self.blocks = nn.ModuleList([_Block(dim, ffn_dim, num_heads, eps, self.window_size) for _ in range(num_layers)])
+        self.blocks = nn.ModuleList([_Block(dim, ffn_dim, num_heads, eps, self.window_size, self.window_sink) for _ in range(num_layers)])
         self.head = _Head(dim, pt * ph * pw * out_dim, eps)
         self.d = dim // num_heads
         self.ref_conv = nn.Conv2d(in_dim_ref_conv, dim, kernel_size=(ph, pw), stride=(ph, pw)) if add_ref_conv else None

@@ -149,6 +149,17 @@ int flexam_attn_fwd_lastkey(const void* q, int64_t q_bs, int64_t q_rs, const voi
 int flexam_attn_fwd_window(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                            int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L, int head_dim,
                            float softmax_scale, int window_left, int window_right, void* stream);
+/* flexam_attn_fwd_window with the first `sink` keys visible to every query (the "attention sink" of StreamingLLM; here the
+ * reference-image tokens that lead the frame-major sequence): query i sees key j iff
+ *   j < sink  or  ((window_left < 0 or j >= i - window_left) and (window_right < 0 or j <= i + window_right)).
+ * The sink is visible to every row whatever window_right says: the model is not causal.  A work unit visits the sink tiles
+ * [0, (sink - 1) / 64] and its window tiles, as one run where they touch and as two runs otherwise; a tile wholly below the sink is
+ * not masked.  Normalisations, each the very launch named: sink = 0, or window_left < 0 (nothing lies to the left of the window), is
+ * flexam_attn_fwd_window(window_left, window_right); sink >= L, or a window that is no bound on either side, is flexam_attn_fwd itself.
+ * sink < 0 is FLEXAM_E_ARG. */
+int flexam_attn_fwd_window_sink(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L, int head_dim,
+                                float softmax_scale, int window_left, int window_right, int sink, void* stream);
 /* flexam_attn_fwd with the work units u =(batch*H + head)*ceil(Lq/256) + q_block at and after `split_from_unit` cut into kv_splits key
  * ranges each (flash-decoding style partial softmaxes + a merge launch), the units before it in one pass: with
  * split_from_unit = floor(units/256)*256 only the last, partial round of the 256 CUs is split; 0 splits everything (ranks of a
