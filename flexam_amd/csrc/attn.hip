@@ -61,7 +61,10 @@ struct AttnParams {
   float last_key_bias;  // added to the score of key Lk - 1 in exp2 units (log2 of its multiplicity), 0 = none: see flexam_attn_fwd_lastkey
   // MXFP8 operands (attn_fp8.inc; q8 != nullptr selects that kernel): written by flexam_attn_fp8_pack
   const unsigned char* q8;   // [B][H][lq_pad][128] e4m3
-  const unsigned* qs;        // [B][H][lq_pad] four E8M0 bytes per row
+  // (attn_window_frames_kernel, which has no MXFP8 operands, reads the low word of this pointer as win_frame = T > 0
+  //  (flexam_attn_fwd_window_frames): win_left / win_right count frames of T tokens from token 0, see below.  attn_window_kernel, whose
+  //  window counts tokens, does not read it: attn_run leaves it 0 there, the null qs)
+  union { const unsigned* qs; int win_frame; };        // [B][H][lq_pad] four E8M0 bytes per row
   const unsigned char* kv8;  // [B][H][ceil(Lk / 64)] records of REC_BYTES -- or, in chunks of kv8_chunk_tiles key tiles, [chunk][B][H][kv8_chunk_tiles]
   // (attn_window_kernel reads this word as its sink, the way it reads the two chunk words below as its window: the first win_sink keys
   //  are visible to EVERY row, whatever win_right says -- the model is not causal.  Row i sees key j iff j < win_sink or j is in its window)
@@ -71,7 +74,8 @@ struct AttnParams {
   // into one s_mul_hi_u32 (exact for g, tiles < 2^16)
   // (attn_window_kernel, which has no MXFP8 operands, reads the two words as its window: the struct, and with it the kernarg loads of
   //  every other instance, stay as they are.)  Sliding window, Lq == Lk: row i sees key j iff (win_left < 0 or j >= i - win_left) and
-  //  (win_right < 0 or j <= i + win_right)
+  //  (win_right < 0 or j <= i + win_right); with win_frame = T > 0 the same two words count frames: j / T >= i / T - win_left and
+  //  j / T <= i / T + win_right, i.e. row i sees the keys [(i / T - win_left) T, (i / T + win_right + 1) T - 1] -- whole frames
   union { int kv8_chunk_tiles; int win_left; };
   union { unsigned kv8_chunk_magic; int win_right; };
   // smooth-V (flexam_attn_fwd_fp8_oshift): fp32 [B][H * 128] added to O / l in fp32 in front of the one rounding to bf16, by the OSHIFT
@@ -284,9 +288,15 @@ __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (
 // sink tiles a row HAS started, and the first window tiles of the unit may again hold no key it sees: such a half tile is all -inf for the
 // row, its maximum moves neither reference (PRE: delta = max(-inf, 0) = 0, alpha = 1; else m_new = m_run, alpha = exp2(0)) and its
 // exp2(-inf) terms add exactly 0 -- the same guards, no new case.
+// FRAMES (attn_window_frames_kernel; win_frame = T > 0, flexam_attn_fwd_window_frames): the window counts frames of T tokens from token 0 and row i sees the frames
+// i / T - win_left .. i / T + win_right whole.  A row's keys are still ONE range [lo(i), hi(i)] and both ends are non-decreasing in i, which
+// is all the walk, the interior test and the per-lane mask rest on: only the derivation of the bounds differs (one division by T per unit
+// for the scalar bounds, one per row for the lane's), at kernel entry; the tile loop is the token window's.  Where T is a multiple of 64
+// every frame boundary is a tile boundary: all window tiles are interior and the per-lane mask runs for the sink's edge and the ragged
+// last tile only.
 // (The one-block step of FULL for runs of interior tiles, next to the general step for the edges, was built and not kept: two step
 //  bodies in one loop cost hipcc 70 (scale in kernel) to 330 (PRE) spilled VGPRs, and a loop for each does not fit the instruction cache.)
-template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN>
+template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN, bool FRAMES = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p by value, as attn8_fwd_body takes it and for its reason)
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [4 K tiles][4 V tiles], each a ring
   const int tid = threadIdx.x;
@@ -344,14 +354,23 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
     int qb = unit % p.q_blocks;
     if (p.win_left < 0) qb = p.q_blocks - 1 - qb;
     const int qa = qb * QBLK, qz = min(qa + QBLK, p.Lq) - 1;      // first and last row of the unit
-    const int k_first = p.win_left < 0 ? 0 : max(0, qa - p.win_left);
-    const int k_last = p.win_right < 0 ? p.Lk - 1 : min(p.Lk - 1, qz + p.win_right);
+    // the key ranges [lo, hi] of the first (_a) and the last (_z) row before clipping (an unbounded side's are not used): in tokens, or
+    // FRAMES in whole frames of win_frame = T tokens counted from token 0 (fa, fz: the two rows' frames).  Non-decreasing in the row
+    // either way
+    int fa = 0, fz = 0;
+    if constexpr (FRAMES) { fa = (int)((unsigned)qa / (unsigned)p.win_frame); fz = (int)((unsigned)qz / (unsigned)p.win_frame); }
+    const int lo_a = FRAMES ? (fa - p.win_left) * p.win_frame : qa - p.win_left;
+    const int hi_z = FRAMES ? (fz + p.win_right + 1) * p.win_frame - 1 : qz + p.win_right;
+    const int k_first = p.win_left < 0 ? 0 : max(0, lo_a);
+    const int k_last = p.win_right < 0 ? p.Lk - 1 : min(p.Lk - 1, hi_z);
     s_n = (min(p.win_sink, p.Lk) + KVBLK - 1) / KVBLK;
     s_full = p.win_sink / KVBLK;
     gap = max(0, k_first / KVBLK - s_n);
     w_n = max(k_last / KVBLK, s_n - 1) + 1 - gap;
-    ti_lo = p.win_left < 0 ? 0 : (max(0, qz - p.win_left) + KVBLK - 1) / KVBLK;      // its first key is the last row's first or later
-    const int top_key = qa + p.win_right - (KVBLK - 1);                              // its last key is the first row's last or sooner
+    const int lo_z = FRAMES ? (fz - p.win_left) * p.win_frame : qz - p.win_left;
+    ti_lo = p.win_left < 0 ? 0 : (max(0, lo_z) + KVBLK - 1) / KVBLK;      // its first key is the last row's first or later
+    const int hi_a = FRAMES ? (fa + p.win_right + 1) * p.win_frame - 1 : qa + p.win_right;
+    const int top_key = hi_a - (KVBLK - 1);                               // its last key is the first row's last or sooner
     ti_hi = min(p.win_right < 0 ? tiles_all : top_key >= 0 ? top_key / KVBLK : -1, p.Lk / KVBLK - 1);      // (whole tiles only)
     // as local indices, for the test in front of part A: the window's interior tiles lie at or behind its first tile, so behind the gap
     ti_lo -= gap;
@@ -484,8 +503,16 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   // that lies in [row - left, row + right]: one per-lane value, the bounds' other terms are uniform.  Called in the tiles that are not interior only.
   // The sink: or that key lies below win_sink (`sk`: uniform but for the lane half; never true without a sink).
   // (the three bounds less `base` are kept per lane: as uniform values next to s_n, gap and s_full they cost the loop 40 SGPR lane reloads)
+  // FRAMES: the range is that of the row's frame, [(f - left) T, (f + right + 1) T - 1] with f = row / T: one division
+  // per row here, nothing in the tile loop.
   const int w_row = q0 + r - 4 * h;
-  const int w_lo = w_row - (p.win_left < 0 ? (1 << 30) : p.win_left), w_hi = w_row + (p.win_right < 0 ? (1 << 30) : p.win_right), w_sk = p.win_sink - 4 * h;
+  int w_lo = w_row - (p.win_left < 0 ? (1 << 30) : p.win_left), w_hi = w_row + (p.win_right < 0 ? (1 << 30) : p.win_right);
+  if constexpr (FRAMES) {
+    const int w_f = (int)((unsigned)(q0 + r) / (unsigned)p.win_frame);
+    if (p.win_left >= 0) w_lo = (w_f - p.win_left) * p.win_frame - 4 * h;
+    if (p.win_right >= 0) w_hi = (w_f + p.win_right + 1) * p.win_frame - 1 - 4 * h;
+  }
+  const int w_sk = p.win_sink - 4 * h;
   auto mask_window = [&](int g, f32x16& sacc) {
     const int base = (2 * global_tile(g >> 1) + (g & 1)) * 32;
     const int lo = w_lo - base, hi = w_hi - base, sk = w_sk - base;
@@ -752,6 +779,11 @@ __global__ __launch_bounds__(NT, 2) void attn_fwd_kernel(AttnParams p) { attn_fw
 // The windowed instances (a name of their own: the profiler and tools/kernel_resources.py tell them from the six above)
 template <bool PRE>
 __global__ __launch_bounds__(NT, 2) void attn_window_kernel(AttnParams p) { attn_fwd_body<0, PRE, false, false, true>(p); }
+// ... and the same two with the window counted in frames (AttnParams::win_frame > 0).  Instances of their own, not a run-time branch on
+// win_frame in the two above: the branch sits at kernel entry only, but with it hipcc schedules the whole kernel anew, and the token-window
+// launches measured 0.2 - 1.8 % slower than the parent build's (tools/attn_window_bench.py --frames --base); so those two stay as they were
+template <bool PRE>
+__global__ __launch_bounds__(NT, 2) void attn_window_frames_kernel(AttnParams p) { attn_fwd_body<0, PRE, false, false, true, true>(p); }
 
 #include "attn_fp8.inc"
 
@@ -809,18 +841,24 @@ struct AttnCall {
   const float* o_shift = nullptr;              // MXFP8 only (flexam_attn_fwd_fp8_oshift): see AttnParams::o_shift
   int win_left = -1, win_right = -1;           // flexam_attn_fwd_window: see AttnParams::win_left; a negative side is unbounded
   int win_sink = 0;                            // flexam_attn_fwd_window_sink: see AttnParams::win_sink
+  bool win_by_frames = false;                  // flexam_attn_fwd_window_frames: win_left / win_right count frames of win_frame tokens
+  int win_frame = 0;                           // see AttnParams::win_frame; read under win_by_frames only
 };
-// The ten instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
+// The twelve instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
 struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
-constexpr int ATTN_INSTANCES = 10;
-AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx, bool window) {
+constexpr int ATTN_INSTANCES = 12;
+// the two attn_window_frames_kernel instances (slots 10 and 11).  Defined at the end of this file, so that they are emitted behind every
+// other kernel of it: a listing of this file then differs from one without them by the two kernels alone (tools/isa_diff.py)
+AttnInstance attn_frames_instance(bool prescaled);
+AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx, bool window, bool frames) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES, F8 = NSLOT * REC_BYTES;
-  static const AttnInstance table[ATTN_INSTANCES] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
+  static const AttnInstance table[10] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
                                         {attn_fwd_kernel<1, true>, BF, 3}, {attn_fwd_kernel<0, true, true>, BF, 4},
                                         {attn_fwd_kernel<1, true, false, true>, BF, 5}, {attn8_fwd_kernel<0>, F8, 6},
                                         {attn8_oshift_kernel, F8, 7},      // the MXFP8 kernel that adds AttnParams::o_shift (smooth-V)
                                         {attn_window_kernel<false>, BF, 8}, {attn_window_kernel<true>, BF, 9}};      // sliding window (bf16)
+  if (window && frames) return attn_frames_instance(prescaled);
   if (window) return table[prescaled ? 9 : 8];
   return table[fp8 ? (oshift ? 7 : 6) : full ? 4 : short_ctx ? 5 : (cross ? 1 : 0) + (prescaled ? 2 : 0)];
 }
@@ -863,7 +901,10 @@ int attn_run(const AttnCall& c) {
   p.q8 = (const unsigned char*)c.q8; p.qs = (const unsigned*)c.qs; p.kv8 = (const unsigned char*)c.kv8; p.lq_pad = p.q_blocks * QBLK;
   p.kv8_chunk_tiles = c.kv8_chunk_tiles > 0 ? c.kv8_chunk_tiles : tiles_all; p.o_shift = c.o_shift;
   // a side that reaches past the sequence from every row is no bound; no bound at all is the ordinary call, launch for launch
-  const int win_left = c.win_left < 0 || c.win_left >= c.Lk - 1 ? -1 : c.win_left, win_right = c.win_right < 0 || c.win_right >= c.Lk - 1 ? -1 : c.win_right;
+  // (in frames: the last frame is ceil(Lk / T) - 1, and frame_tokens >= Lk is one frame that holds every key)
+  FX_REQUIRE(!c.win_by_frames || c.win_frame > 0, FLEXAM_E_ARG, "attn_fwd: frame_tokens %d (1 or more)", c.win_frame);
+  const int win_reach = c.win_by_frames ? (int)(((int64_t)c.Lk + c.win_frame - 1) / c.win_frame) - 1 : c.Lk - 1;
+  const int win_left = c.win_left < 0 || c.win_left >= win_reach ? -1 : c.win_left, win_right = c.win_right < 0 || c.win_right >= win_reach ? -1 : c.win_right;
   FX_REQUIRE(c.win_sink >= 0, FLEXAM_E_ARG, "attn_fwd: negative sink %d", c.win_sink);
   // a sink that holds every key leaves no mask; one under a window without a left bound (nothing lies to the left of it) adds no key
   const bool window = (win_left >= 0 || win_right >= 0) && c.win_sink < c.Lk;
@@ -872,13 +913,15 @@ int attn_run(const AttnCall& c) {
              "attn_fwd: a window goes with bf16 operands of one length and whole work units");
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
-  if (window) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; }      // (in the words of three MXFP8 fields above: see AttnParams)
+  // (in the words of four MXFP8 fields above: see AttnParams.  A token window leaves win_frame 0, the low word of the null qs, and runs
+  //  the instances that do not read it)
+  if (window) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; if (c.win_by_frames) p.win_frame = c.win_frame; }
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
   const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
   const bool short_ctx = !window && !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
   const bool full = !window && !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
-  const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window);
+  const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window, window && c.win_by_frames);
   static bool attr_set[FLEXAM_MAX_DEVICES][ATTN_INSTANCES] = {};      // per device and kernel instance
   bool& lds_raised = attr_set[flexam_current_device()][inst.slot];
   if (!lds_raised) {
@@ -947,6 +990,17 @@ extern "C" int flexam_attn_fwd_window_sink(const void* q, int64_t q_bs, int64_t 
   c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
   c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
   c.win_left = window_left; c.win_right = window_right; c.win_sink = sink;
+  return attn_run(c);
+}
+
+extern "C" int flexam_attn_fwd_window_frames(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
+                                             const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
+                                             int L, int head_dim, float softmax_scale, int frames_left, int frames_right, int frame_tokens,
+                                             int sink, void* stream) {
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  c.win_left = frames_left; c.win_right = frames_right; c.win_sink = sink; c.win_by_frames = true; c.win_frame = frame_tokens;
   return attn_run(c);
 }
 
@@ -1140,3 +1194,11 @@ extern "C" int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int
   launch_merge(p, stream);
   return flexam_check_launch("flexam_attn_merge");
 }
+
+namespace {
+AttnInstance attn_frames_instance(bool prescaled) {      // (declared next to attn_instance: why it stands here)
+  constexpr int BF = NSLOT * 2 * KV_TILE_BYTES;
+  if (prescaled) return {attn_window_frames_kernel<true>, BF, 11};
+  return {attn_window_frames_kernel<false>, BF, 10};
+}
+}  // namespace

@@ -87,6 +87,9 @@ class DiTEngine:
         self.window = hip.attn_window(c["window_size"])
         # under a window: the first window_sink tokens stay visible to every query (the model's window_sink); in the plan's key too
         self.window_sink = int(c["window_sink"])
+        # the window counted in frames of the clip's token grid instead (the model's window_frames; never together with window_size): served
+        # by the same windowed kernel, refused and warned about like a token window; with the frame's tokens part of a launch plan's key
+        self.window_frames = hip.attn_window(c["window_frames"])
         if self.hd != hip.ATTN_HEAD_DIM:
             raise RuntimeError(f"flexam_amd: head_dim {self.hd} unsupported by the HIP attention kernel ({hip.ATTN_HEAD_DIM} only)")
         if self.patch != (1, 2, 2):
@@ -391,9 +394,11 @@ class DiTEngine:
         benchlib flip them between forwards."""
         cd, env = self.cond, os.environ
         window = getattr(self, "window", (-1, -1))         # (tests/test_smooth_k_mode_cpu.py resolves modes on a bare namespace)
-        if window != (-1, -1) and self.sp_size > 1:
-            raise NotImplementedError("flexam_amd: window_size under sequence parallelism is not served: a rank's queries and the keys it "
-                                      "gathers carry global token indices, which the windowed kernel does not take")
+        frames = getattr(self, "window_frames", (-1, -1))
+        if (window != (-1, -1) or frames != (-1, -1)) and self.sp_size > 1:
+            raise NotImplementedError(f"flexam_amd: {'window_size' if frames == (-1, -1) else 'window_frames'} under sequence parallelism is not "
+                                      "served: a rank's queries and the keys it gathers carry global token indices, which the windowed "
+                                      "kernel does not take")
         m = resolve_mode(env, fused=self.fused, nl=self.nl, nh=self.nh, hd=self.hd, dim=self.dim, table_limit=self.table_limit, fp8=self.fp8,
                          sp=self.sp_size, rank=self.sp_rank,
                          parallel=(self.sp_mode, self.sp_overlap_level, self.sp_pieces, self.sp_fused_qkv),
@@ -424,14 +429,14 @@ class DiTEngine:
             import warnings
             warnings.warn("flexam_amd: FLEXAM_SAGE_SMOOTH_V=1 is ignored under sequence parallelism: V is quantised as it is",
                           RuntimeWarning, stacklevel=3)
-        if window != (-1, -1) and m.sage:                  # the MXFP8 kernel has no mask: the windowed bf16 kernel runs
+        if (window != (-1, -1) or frames != (-1, -1)) and m.sage:      # the MXFP8 kernel has no mask: the windowed bf16 kernel runs
             m = m._replace(sage=False, sage_gather=False, sage_fused=False)
             self._smooth_k = self._smooth_v = False
             if not DiTEngine._sage_window_warned:          # said once per process
                 DiTEngine._sage_window_warned = True
                 import warnings
-                warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored with window_size: self-attention runs the windowed "
-                              "bf16 kernel", RuntimeWarning, stacklevel=3)
+                warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored with window_size / window_frames: self-attention "
+                              "runs the windowed bf16 kernel", RuntimeWarning, stacklevel=3)
         return m
 
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
@@ -535,6 +540,14 @@ class DiTEngine:
         self._head(m, ws)
         return ws["head"].view(B, lc, -1)
 
+    def _window_frames(self):
+        """((a, b), T) of the self-attention's frame window for this clip, T = the tokens of one frame of its grid; ((-1, -1), 0) without one."""
+        frames = getattr(self, "window_frames", (-1, -1))
+        if frames == (-1, -1):
+            return frames, 0
+        from .wan_transformer3d_FlexAM import frame_tokens
+        return frames, frame_tokens(self.cond["grid"], self.cond["L"])
+
     def _record_or_replay(self, m, ws, e0, dens0):
         """The blocks and the head through a launch plan: they issue the same ~420 launches on the same buffers every step (only buffer
         CONTENTS change), so the first step records them (hip.record: executed and appended to command lists) and every later step
@@ -545,7 +558,7 @@ class DiTEngine:
         cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
         key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
                torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), getattr(self, "window", (-1, -1)), getattr(self, "window_sink", 0),
-               self._smooth_v, self._smooth_k)
+               DiTEngine._window_frames(self), self._smooth_v, self._smooth_k)      # (unbound: the mode tests hand a bare namespace)
         plans = cd.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -668,6 +681,9 @@ class DiTEngine:
             self._norm_rope_qk(p, m, ws, nb)
             if self.window != (-1, -1):
                 hip.attn_fwd_window(q4[:nb], k4[:nb], v4[:nb], self.window, out=ao4[:nb], prescaled=True, sink=self.window_sink)
+            elif self.window_frames != (-1, -1):
+                frames, T = self._window_frames()
+                hip.attn_fwd_window(q4[:nb], k4[:nb], v4[:nb], frames, out=ao4[:nb], prescaled=True, sink=self.window_sink, frame_tokens=T)
             else:
                 hip.attn_fwd(q4[:nb], k4[:nb], v4[:nb], out=ao4[:nb], prescaled=True)
         self._out_proj(i, p, "wo", "bo", ws["ao"][:mb], ws, mb, m.fp8_oproj, **gate)

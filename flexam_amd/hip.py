@@ -574,11 +574,40 @@ def attn_window_sink_tiles(L: int, window, sink: int):
     return out
 
 
-def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0):
+def attn_window_frames_tiles(L: int, window_frames, frame_tokens: int, sink: int = 0):
+    """attn_window_sink_tiles for a window counted in frames of `frame_tokens` = T tokens from token 0 (flexam_attn_fwd_window_frames):
+    row i sees key j iff j < sink or (a < 0 or j // T >= i // T - a) and (b < 0 or j // T <= i // T + b), window_frames = (a, b).  Per
+    block of ATTN_Q_BLOCK query rows the list of (first, last) key-tile runs the windowed kernel walks.  A row's keys are the range
+    [(i // T - a) T, (i // T + b + 1) T - 1] clipped to [0, L) and both ends are non-decreasing in i, so a block's window keys run from
+    its first row's first key to its last row's last; the sink tiles join them as in attn_window_sink_tiles -- but for a < 0, where the
+    entry point drops the sink (nothing lies to the left of such a window) and so does this.  GPU-free."""
+    a, b = attn_window(window_frames)
+    T, sink = int(frame_tokens), int(sink)
+    if T <= 0:
+        raise ValueError(f"attn_window_frames_tiles: frame_tokens {frame_tokens} (1 or more)")
+    if sink < 0:
+        raise ValueError(f"attn_window_frames_tiles: negative sink {sink}")
+    n_sink = -(-min(sink, L) // ATTN_KV_TILE) if a >= 0 else 0            # (nothing lies to the left of a window without a left bound)
+    out = []
+    for q0 in range(0, L, ATTN_Q_BLOCK):
+        q1 = min(q0 + ATTN_Q_BLOCK, L) - 1
+        first = (0 if a < 0 else max(0, (q0 // T - a) * T)) // ATTN_KV_TILE
+        last = (L - 1 if b < 0 else min(L - 1, (q1 // T + b + 1) * T - 1)) // ATTN_KV_TILE
+        if n_sink == 0:
+            out.append([(first, last)])
+        elif n_sink >= first:
+            out.append([(0, max(last, n_sink - 1))])
+        else:
+            out.append([(0, n_sink - 1), (first, last)])
+    return out
+
+
+def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0, frame_tokens=0):
     """attn_fwd under flash-attn's sliding-window mask (see flexam_hip.h): q, k, v [B, L, H, 128] bf16 with the layouts of attn_fwd and
     ONE length L; window = (left, right), a negative side unbounded, (-1, -1) the ordinary call.  Whole work units only (no split-KV).
     sink > 0: the first `sink` keys stay visible to every row whatever the window says (flexam_attn_fwd_window_sink); sink = 0 is the
-    call this function has always made."""
+    call this function has always made.  frame_tokens = T > 0: `window` = (a, b) counts frames of T tokens from token 0, row i sees the
+    frames i // T - a .. i // T + b whole (flexam_attn_fwd_window_frames); frame_tokens = 0 changes no call."""
     B, L, H, D = q.shape
     if k.shape[1] != L or v.shape[1] != L:
         raise RuntimeError(f"attn_fwd_window: queries and keys share one length (Lq = {L}, Lk = {k.shape[1]})")
@@ -589,7 +618,9 @@ def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=Fal
     sink = int(sink)
     args = (_ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16), v.stride(0), v.stride(1),
             _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D, _softmax_scale(softmax_scale, prescaled, D), left, right)
-    if sink == 0:
+    if int(frame_tokens) != 0:
+        _call("flexam_attn_fwd_window_frames", *args, int(frame_tokens), sink)
+    elif sink == 0:
         _call("flexam_attn_fwd_window", *args)
     else:
         _call("flexam_attn_fwd_window_sink", *args, sink)

@@ -154,16 +154,33 @@ class _Attn(nn.Module):
         return t2d.view(b, l, -1)[:, :, :nh * hd].unflatten(2, (nh, hd)) if t2d.shape[1] == nh * hd else None
 
 
+def frame_tokens(grid_sizes, seq_len: int) -> int:
+    """Tokens per frame of a token grid [F + 1, h_tok, w_tok] (one grid per sample, all alike): h_tok * w_tok, what window_frames counts
+    in.  The sequence is frame-major with the reference image's tokens as frame 0, so its length must be a whole number of frames."""
+    g = grid_sizes.tolist() if torch.is_tensor(grid_sizes) else list(grid_sizes)
+    g = g if isinstance(g[0], (list, tuple)) else [g]
+    if any(tuple(u) != tuple(g[0]) for u in g):
+        raise NotImplementedError("flexam_amd: all samples of a batch share one token grid on the FlexAM path")
+    T = int(g[0][1]) * int(g[0][2])
+    if T <= 0 or seq_len % T:
+        raise NotImplementedError(f"flexam_amd: window_frames needs a sequence of whole frames: {seq_len} tokens are no multiple of the "
+                                  f"{T} tokens of a frame (leading reference tokens must be exactly one frame's worth)")
+    return T
+
+
 class _SelfAttn(_Attn):
     """WanSelfAttention (wan_transformer3d_FlexAM.py:205-262) on the HIP kernels: fused q|k|v GEMM, full-width RMSNorm +
     3-axis RoPE in one pass, flash attention, output projection.  window_size: flash-attn's (left, right) in tokens, which the reference
     hands to its kernel (wan_transformer3d_FlexAM.py:251-256); (-1, -1) = full attention.  window_sink: under a window, the first
-    window_sink tokens (the reference image leads the frame-major sequence) stay visible to every query; without a window it does nothing."""
+    window_sink tokens (the reference image leads the frame-major sequence) stay visible to every query; without a window it does nothing.
+    window_frames: (a, b), the window counted in frames of the token grid (h_tok * w_tok tokens each, taken from grid_sizes per forward;
+    the reference image is frame 0): a query sees the frames f - a .. f + b whole, a negative side unbounded; not with window_size."""
 
-    def __init__(self, dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1), window_sink=0):
+    def __init__(self, dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1), window_sink=0, window_frames=(-1, -1)):
         super().__init__(dim, num_heads, eps)
         self.window_size = tuple(int(w) for w in window_size)
         self.window_sink = int(window_sink)
+        self.window_frames = tuple(int(w) for w in window_frames)
 
     def packed(self):
         sig = self._sig()
@@ -202,11 +219,12 @@ class _SelfAttn(_Attn):
         b, l, c = x.shape
         nh, hd = self.num_heads, self.head_dim
         sp = current_sp_context()
-        window = hip.attn_window(self.window_size)
+        window, frames = hip.attn_window(self.window_size), hip.attn_window(self.window_frames)
         if sp is not None and sp["size"] > 1:
-            if window != (-1, -1):
-                raise NotImplementedError("flexam_amd: window_size under sequence parallelism is not served (a rank's queries are a chunk of "
-                                          "the sequence: the window would have to follow their global indices)")
+            if window != (-1, -1) or frames != (-1, -1):
+                raise NotImplementedError(f"flexam_amd: {'window_size' if frames == (-1, -1) else 'window_frames'} under sequence parallelism is "
+                                          "not served (a rank's queries are a chunk of the sequence: the window would have to follow their "
+                                          "global indices)")
             return self._forward_chunk(x, seq_lens, sp)
         # A caller that hands over a PADDED sequence (FX.py:918-925: zero tokens behind seq_lens[b] real ones, the same count for every
         # sample) gets flash-attention's semantics: the pads are no keys (k_lens, FX.py:251-256 -> ATT.py:87-95); their own rows are
@@ -217,6 +235,11 @@ class _SelfAttn(_Attn):
             if any(v != lens[0] for v in lens) or lens[0] > l or lens[0] < 1:
                 raise NotImplementedError("flexam_amd: ragged seq_lens inside one batch do not occur on the FlexAM path (one clip per call)")
             n_keys = lens[0]
+        if frames != (-1, -1):                                 # refused before any launch: what the frame window does not serve
+            if n_keys < l:
+                raise NotImplementedError("flexam_amd: window_frames with seq_lens shorter than the sequence is not served: the mask of "
+                                          "Lq != Lk is refused as window_size's is")
+            frame_t = frame_tokens(grid_sizes, l)
         pk = self.packed()
         h = x.reshape(b * l, c).to(BF16).contiguous()
         qkv = _proj_fp8(h, pk, "wqkv", pk["bqkv"]) if self._fp8 else hip.gemm(h, pk["wqkv"], pk["bqkv"])
@@ -230,6 +253,8 @@ class _SelfAttn(_Attn):
                 raise NotImplementedError("flexam_amd: window_size with seq_lens shorter than the sequence is not served: flash-attn aligns "
                                           "the mask of Lq != Lk bottom-right, SDPA top-left")
             ao = hip.attn_fwd_window(q4, k4, v4, window, prescaled=True, sink=self.window_sink)      # (SAGE_ATTENTION too: the MXFP8 kernel has no mask)
+        elif frames != (-1, -1):
+            ao = hip.attn_fwd_window(q4, k4, v4, frames, prescaled=True, sink=self.window_sink, frame_tokens=frame_t)
         elif n_keys < l:
             ao = hip.attn_fwd(q4, k4[:, :n_keys], v4[:, :n_keys], prescaled=True)
         elif os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION" and not torch.is_grad_enabled() and hd == 128:
@@ -339,10 +364,10 @@ class _Block(nn.Module):
     wan_transformer3d_FlexAM.py:807-815): same signature, it calls `self.self_attn` / `self.cross_attn` as modules so a
     re-bound attention forward takes effect, and the engine routes a step through it whenever a block is not pristine."""
 
-    def __init__(self, dim: int, ffn_dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1), window_sink=0):
+    def __init__(self, dim: int, ffn_dim: int, num_heads: int = None, eps: float = 1e-6, window_size=(-1, -1), window_sink=0, window_frames=(-1, -1)):
         super().__init__()
         self.dim, self.ffn_dim, self.num_heads, self.eps = dim, ffn_dim, num_heads, eps
-        self.self_attn, self.cross_attn = _SelfAttn(dim, num_heads, eps, window_size, window_sink), _CrossAttn(dim, num_heads, eps)      # (cross-attention: no window, as in the reference)
+        self.self_attn, self.cross_attn = _SelfAttn(dim, num_heads, eps, window_size, window_sink, window_frames), _CrossAttn(dim, num_heads, eps)      # (cross-attention: no window, as in the reference)
         self.norm3 = _Norm(dim, bias=True, eps=eps)
         self.ffn = nn.Sequential(_holder(ffn_dim, dim), nn.GELU(approximate="tanh"), _holder(dim, ffn_dim))
         self.modulation = nn.Parameter(torch.randn(1, 6, dim) / dim ** 0.5)
@@ -445,7 +470,7 @@ class WanTransformer3DModel_FlexAM(nn.Module):
                  text_dim=4096, out_dim=16, num_heads=16, num_layers=32, window_size=(-1, -1), qk_norm=True, cross_attn_norm=True,
                  eps=1e-6, in_channels=16, hidden_size=2048, add_control_adapter=False, in_dim_control_adapter=24,
                  downscale_factor_control_adapter=8, add_ref_conv=False, in_dim_ref_conv=16, cross_attn_type=None,
-                 add_cnn_block=False, in_dim_cnn_block=96, out_dim_cnn_block=16, window_sink=0):
+                 add_cnn_block=False, in_dim_cnn_block=96, out_dim_cnn_block=16, window_sink=0, window_frames=(-1, -1)):
         super().__init__()
         cfg = dict(locals())
         cfg.pop("self")
@@ -457,6 +482,14 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         cfg["window_sink"] = int(window_sink)
         if cfg["window_sink"] < 0:
             raise ValueError(f"window_sink {window_sink}: a count of leading tokens, 0 or more")
+        # not the reference's either: the window counted in frames of the token grid, (a, b) = the frames f - a .. f + b whole, a negative
+        # side unbounded ((-1, 0) frame-block-causal, (0, 0) per frame); the tokens of a frame come from each forward's grid_sizes.
+        # window_sink applies under it as under window_size; the two windows exclude each other
+        cfg["window_frames"] = tuple(-1 if int(w) < 0 else int(w) for w in window_frames)
+        if len(cfg["window_frames"]) != 2:
+            raise ValueError(f"window_frames {window_frames}: (frames before, frames after)")
+        if cfg["window_frames"] != (-1, -1) and tuple(-1 if w < 0 else w for w in cfg["window_size"]) != (-1, -1):
+            raise ValueError(f"window_size {tuple(window_size)} and window_frames {tuple(window_frames)}: one window, in tokens or in frames")
         self.config = ModelConfig(cfg)
         if add_control_adapter:
             raise NotImplementedError("control_adapter (camera branch) is not part of the FlexAM 5B path (SURVEY section 2)")
@@ -465,7 +498,7 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         if cross_attn_type not in (None, "cross_attn"):
             raise NotImplementedError(f"cross_attn_type {cross_attn_type}: only the text cross-attention of Wan2.2 is implemented")
         for k in ("model_type", "patch_size", "text_len", "in_dim", "dim", "ffn_dim", "freq_dim", "text_dim", "out_dim", "num_heads",
-                  "num_layers", "eps", "window_size", "window_sink"):
+                  "num_layers", "eps", "window_size", "window_sink", "window_frames"):
             setattr(self, k, self.config[k])
         pt, ph, pw = self.patch_size
         self.patch_embedding = nn.Conv3d(in_dim, dim, kernel_size=self.patch_size, stride=self.patch_size)
@@ -474,7 +507,7 @@ class WanTransformer3DModel_FlexAM(nn.Module):
         self.time_projection = nn.Sequential(nn.SiLU(), _holder(dim * 6, dim))
         self.density_embedding = nn.Sequential(_holder(dim, freq_dim), nn.SiLU(), _holder(dim, dim))
         self.density_projection = nn.Sequential(nn.SiLU(), _holder(dim * 2, dim))
-        self.blocks = nn.ModuleList([_Block(dim, ffn_dim, num_heads, eps, self.window_size, self.window_sink) for _ in range(num_layers)])
+        self.blocks = nn.ModuleList([_Block(dim, ffn_dim, num_heads, eps, self.window_size, self.window_sink, self.window_frames) for _ in range(num_layers)])
         self.head = _Head(dim, pt * ph * pw * out_dim, eps)
         self.d = dim // num_heads
         self.ref_conv = nn.Conv2d(in_dim_ref_conv, dim, kernel_size=(ph, pw), stride=(ph, pw)) if add_ref_conv else None

@@ -160,6 +160,19 @@ int flexam_attn_fwd_window(const void* q, int64_t q_bs, int64_t q_rs, const void
 int flexam_attn_fwd_window_sink(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                                 int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L, int head_dim,
                                 float softmax_scale, int window_left, int window_right, int sink, void* stream);
+/* flexam_attn_fwd_window_sink with the window counted in frames of `frame_tokens` = T tokens instead of tokens (the masks video
+ * transformers are trained with: the sequence is frame-major, the reference image's tokens are frame 0 and the latent frames follow,
+ * the grid [F + 1, h, w] RoPE uses, T = h * w).  Frames are counted from token 0, frame(t) = t / T; query i sees key j iff
+ *   j < sink  or  ((frames_left < 0 or j / T >= i / T - frames_left) and (frames_right < 0 or j / T <= i / T + frames_right)),
+ * i.e. the keys [(i / T - frames_left) T, (i / T + frames_right + 1) T - 1] clipped to [0, L): whole frames, its own among them, so no
+ * row is empty.  (-1, 0) is frame-block-causal, (0, 0) per-frame attention.  L need not be a multiple of T (a ragged last frame).  A
+ * work unit visits the tiles that hold a key one of its rows sees, and the sink tiles, as flexam_attn_fwd_window_sink does; where T is
+ * a multiple of 64 every frame boundary is a tile boundary and no window tile is masked.  Normalisations, each the very launch named:
+ * both sides negative (or reaching the first and the last frame from every row), frame_tokens >= L, or sink >= L, is flexam_attn_fwd
+ * itself; frames_left < 0 drops the sink (nothing lies to the left of such a window).  frame_tokens <= 0 and sink < 0 are FLEXAM_E_ARG. */
+int flexam_attn_fwd_window_frames(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                  int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L, int head_dim,
+                                  float softmax_scale, int frames_left, int frames_right, int frame_tokens, int sink, void* stream);
 /* flexam_attn_fwd with the work units u =(batch*H + head)*ceil(Lq/256) + q_block at and after `split_from_unit` cut into kv_splits key
  * ranges each (flash-decoding style partial softmaxes + a merge launch), the units before it in one pass: with
  * split_from_unit = floor(units/256)*256 only the last, partial round of the 256 CUs is split; 0 splits everything (ranks of a

@@ -1,6 +1,7 @@
 """Dev tool: what a sliding window saves per self-attention launch at the bench shape (B = 2, H = 24, L = 11648 = 26 frames of 448
 tokens, pre-scaled q) -> profiles/attn_window_bench.json; with --sink, what keeping the first keys visible costs on top of it
--> profiles/attn_window_sink_bench.json.
+-> profiles/attn_window_sink_bench.json; with --frames, the window counted in frames (hip.attn_fwd_window(..., frame_tokens=448))
+-> profiles/attn_window_frames_bench.json.
 
 Arms: full attention through hip.attn_fwd (the yardstick: the launch the engine makes without a window, tail split and merge included)
 against hip.attn_fwd_window with windows of +-k latent frames ((448 k, 448 k), k = 2, 5, 12) and causal.  All arms run in ONE process on
@@ -18,8 +19,15 @@ in-tree, base again, the order rotating -- and checks that both give the same by
 itself (its two arms' medians), `new_over_base` the in-tree median over the pooled base median, `slower_beyond_margin` says whether it
 exceeds 1 + margin.
 
+--frames[=2,5,12] [--sink=0,448]: the arms are the full call and the frame windows +-k frames of the list, frame-block-causal (-1, 0) and
+per-frame (0, 0), each with every sink of the list (tile shares from hip.attn_window_frames_tiles), and beside every +-k arm the token
+window of the same span, (448 k, 448 k) with the same sink: the frame form visits more tiles and masks none of them at this shape (448
+tokens are 7 key tiles), `faster_per_visited_tile` records which of the two takes less time per tile it visits.  With --base the same
+call times the token-window launches (frame_tokens = 0, every sink of the list) of the in-tree library against that build, as above.
+
 usage: attn_window_bench.py [--iters=10] [--rounds=7] [--out=profiles/attn_window_bench.json]
-       attn_window_bench.py --sink=0,448,896 [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sink_bench.json]"""
+       attn_window_bench.py --sink=0,448,896 [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sink_bench.json]
+       attn_window_bench.py --frames[=2,5,12] [--sink=0,448] [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_frames_bench.json]"""
 import json
 import os
 import statistics
@@ -30,74 +38,95 @@ sys.path.insert(0, root)
 import torch  # noqa: E402
 from flexam_amd import hip as H  # noqa: E402
 
-opt = {a.split("=")[0][2:]: a.split("=")[1] for a in sys.argv[1:] if a.startswith("--")}
+opt = {a.split("=")[0][2:]: a.partition("=")[2] for a in sys.argv[1:] if a.startswith("--")}
 iters, rounds = int(opt.get("iters", 10)), int(opt.get("rounds", 7))
-sinks = [int(s) for s in opt["sink"].split(",")] if "sink" in opt else None
-out_path = os.path.join(root, opt.get("out", "profiles/attn_window_bench.json" if sinks is None else "profiles/attn_window_sink_bench.json"))
+frames = [int(n) for n in (opt["frames"] or "2,5,12").split(",")] if "frames" in opt else None
+sinks = [int(s) for s in opt["sink"].split(",")] if "sink" in opt else [0, 448] if frames is not None else None
+out_path = os.path.join(root, opt.get("out", "profiles/attn_window_frames_bench.json" if frames is not None else
+                                      "profiles/attn_window_bench.json" if sinks is None else "profiles/attn_window_sink_bench.json"))
 B, heads, L, D = 2, 24, 11648, 128
 FRAME = 448
 g = torch.Generator().manual_seed(0)
 q, k, v = ((torch.randn(B, L, heads, D, generator=g) * s).to(torch.bfloat16).cuda() for s in (0.35, 1.0, 1.0))      # q in exp2 units: logits of std ~4
 o = torch.empty_like(q)
 
-WINDOWS = [(f"window_{n}_frames", (FRAME * n, FRAME * n)) for n in (2, 5, 12)]
-if sinks is None:
-    ARMS = [("full", None, 0)] + [(name, w, 0) for name, w in WINDOWS] + [("causal", (-1, 0), 0)]
+WINDOWS = [(f"window_{n}_frames", (FRAME * n, FRAME * n)) for n in (frames or (2, 5, 12))]
+# an arm: (name, window, sink, frame_tokens); frame_tokens = 0: the window counts tokens
+if frames is not None:
+    FRAME_WINDOWS = [(f"frames_{n}_{n}", (n, n)) for n in frames] + [("frames_block_causal", (-1, 0)), ("frames_per_frame", (0, 0))]
+    ARMS = [("full", None, 0, 0)] + [(f"{name}_sink_{s}", w, s, FRAME) for name, w in FRAME_WINDOWS for s in sinks]
+    ARMS += [(f"tokens_{n}_{n}_sink_{s}", (FRAME * n, FRAME * n), s, 0) for n in frames for s in sinks]      # the token window of the same span
+elif sinks is None:
+    ARMS = [("full", None, 0, 0)] + [(name, w, 0, 0) for name, w in WINDOWS] + [("causal", (-1, 0), 0, 0)]
 else:
-    ARMS = [("full", None, 0)] + [(f"{name}_sink_{s}", w, s) for name, w in WINDOWS for s in sinks]
+    ARMS = [("full", None, 0, 0)] + [(f"{name}_sink_{s}", w, s, 0) for name, w in WINDOWS for s in sinks]
 
 
-def launch(window, sink=0, out=o):
+def launch(window, sink=0, frame_tokens=0, out=o):
     if window is None:
         H.attn_fwd(q, k, v, out=out, prescaled=True)
+    elif frame_tokens:
+        H.attn_fwd_window(q, k, v, window, out=out, prescaled=True, sink=sink, frame_tokens=frame_tokens)
     elif sink:
         H.attn_fwd_window(q, k, v, window, out=out, prescaled=True, sink=sink)
     else:
         H.attn_fwd_window(q, k, v, window, out=out, prescaled=True)
 
 
-def share(window, sink=0):
-    runs = H.attn_window_sink_tiles(L, window if window is not None else (-1, -1), sink)
+def share(window, sink=0, frame_tokens=0):
+    window = window if window is not None else (-1, -1)
+    runs = H.attn_window_frames_tiles(L, window, frame_tokens, sink) if frame_tokens else H.attn_window_sink_tiles(L, window, sink)
     return sum(b - a + 1 for r in runs for a, b in r) / (H.attn_units(1, L) * H.attn_kv_tiles(L))
 
 
-def timed(window, sink=0):
+def timed(window, sink=0, frame_tokens=0):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(iters):
-        launch(window, sink)
+        launch(window, sink, frame_tokens)
     b.record()
     torch.cuda.synchronize()
     return a.elapsed_time(b) / iters
 
 
-for _, w, s in ARMS:                               # warm-up: every instance once (LDS attribute, code load), then the clock
-    launch(w, s)
+for _, w, s, ft in ARMS:                           # warm-up: every instance once (LDS attribute, code load), then the clock
+    launch(w, s, ft)
 for _ in range(3):
     launch(None)
 torch.cuda.synchronize()
-ms = {name: [] for name, _, _ in ARMS}
+ms = {name: [] for name, _, _, _ in ARMS}
 for _ in range(rounds):
-    for name, w, s in ARMS:
-        ms[name].append(timed(w, s))
+    for name, w, s, ft in ARMS:
+        ms[name].append(timed(w, s, ft))
 full = statistics.median(ms["full"])
 arms, ok = {}, True
-for name, w, s in ARMS:
-    t, sh = statistics.median(ms[name]), share(w, s)
+for name, w, s, ft in ARMS:
+    t, sh = statistics.median(ms[name]), share(w, s, ft)
     arms[name] = dict(window=list(w) if w else None, ms=round(t, 4), ms_min=round(min(ms[name]), 4), ms_max=round(max(ms[name]), 4),
                       tile_share=round(sh, 4), time_ratio=round(t / full, 4), time_per_tile_ratio=round(t / full / sh, 3))
     if sinks is not None and w is not None:
         arms[name]["sink"] = s
+    if frames is not None and w is not None:
+        arms[name]["frame_tokens"] = ft
     if w is not None and sh <= 0.5 and not t < full:
         ok = False
     print(f"{name:28s} {t:8.3f} ms (min {min(ms[name]):.3f}, max {max(ms[name]):.3f})  tiles {sh:6.4f}  time {t / full:6.3f}  per tile {t / full / sh:5.2f}")
+if frames is not None:                             # beside each +-k frame arm: the token window of the same span
+    for n in frames:
+        for s in sinks:
+            fr, tk = arms[f"frames_{n}_{n}_sink_{s}"], arms[f"tokens_{n}_{n}_sink_{s}"]
+            fr["token_window_same_span"] = f"tokens_{n}_{n}_sink_{s}"
+            fr["time_over_token_window"] = round(fr["ms"] / tk["ms"], 4)
+            fr["faster_per_visited_tile"] = "frames" if fr["ms"] / fr["tile_share"] < tk["ms"] / tk["tile_share"] else "tokens"
+            print(f"+-{n} frames, sink {s}: frames / tokens time {fr['ms'] / tk['ms']:6.3f}, per visited tile {fr['time_per_tile_ratio']:5.3f} / "
+                  f"{tk['time_per_tile_ratio']:5.3f} of the full call's: {fr['faster_per_visited_tile']} faster per tile")
 rec = dict(shape=dict(B=B, H=heads, L=L, head_dim=D, prescaled=True), iters=iters, rounds=rounds, device=torch.cuda.get_device_name(0),
            method="one process, arms alternating per round, device events around `iters` back-to-back launches, median over the rounds",
            arms=arms, condition="every window that visits at most half the tiles is faster than the full call of the same run",
            condition_met=ok)
 
-if sinks is not None and "base" in opt:
-    # sink = 0 against a parent build: base, in-tree, base again per window and round, rotating; hip._lib switches the build
+if sinks is not None and opt.get("base"):
+    # sink = 0 (--frames: the token windows) against a parent build: base, in-tree, base again per window and round, rotating; hip._lib switches the build
     import ctypes
 
     def build_of(path):
@@ -112,37 +141,40 @@ if sinks is not None and "base" in opt:
     base_lib, new_lib = build_of(os.path.abspath(opt["base"])), H.load_library(H.LIB_PATH)
     libs = {"base_a": base_lib, "new": new_lib, "base_b": base_lib}
     outs = {tag: torch.empty_like(q) for tag in ("base_a", "new")}
+    # the launches both builds have: sink = 0 (--sink), or the token windows (frame_tokens = 0) with every sink of the list (--frames)
+    AB = [(name, w, 0) for name, w in WINDOWS] if frames is None else [(f"{name}_sink_{s}", w, s) for name, w in WINDOWS for s in sinks]
     for tag in outs:                               # warm-up of both builds, and the bytes they give
         H._lib = libs[tag]
-        for _, w in WINDOWS:
-            launch(w, 0, outs[tag])
+        for _, w, s in AB:
+            launch(w, s, 0, outs[tag])
     torch.cuda.synchronize()
-    ab = {name: {tag: [] for tag in libs} for name, _ in WINDOWS}
+    ab = {name: {tag: [] for tag in libs} for name, _, _ in AB}
     same = {}
-    for name, w in WINDOWS:
+    for name, w, s in AB:
         for tag in outs:
             H._lib = libs[tag]
-            launch(w, 0, outs[tag])
+            launch(w, s, 0, outs[tag])
         torch.cuda.synchronize()
         same[name] = bool(torch.equal(outs["base_a"], outs["new"]))
     order = list(libs)
     for r in range(rounds):
-        for name, w in WINDOWS:
+        for name, w, s in AB:
             for tag in order[r % 3:] + order[:r % 3]:
                 H._lib = libs[tag]
-                ab[name][tag].append(timed(w, 0))
+                ab[name][tag].append(timed(w, s))
     H._lib = new_lib
-    rec["sink_0_against_base"] = dict(method="sink = 0 launches (hip.attn_fwd_window) of the base build and of the in-tree build in this process: per window "
-                                             "and round base, in-tree, base again in rotating order; margin = the base build against itself",
-                                      windows={})
-    for name, w in WINDOWS:
+    key = "sink_0_against_base" if frames is None else "token_windows_against_base"
+    rec[key] = dict(method=("sink = 0 launches" if frames is None else "token-window launches (frame_tokens = 0)") + " (hip.attn_fwd_window) of the base build "
+                    "and of the in-tree build in this process: per window and round base, in-tree, base again in rotating order; margin = the base "
+                    "build against itself", windows={})
+    for name, w, s in AB:
         a, n, b = (statistics.median(ab[name][tag]) for tag in libs)
         base = statistics.median(ab[name]["base_a"] + ab[name]["base_b"])
         margin = abs(a - b) / base
-        rec["sink_0_against_base"]["windows"][name] = dict(window=list(w), base_a_ms=round(a, 4), base_b_ms=round(b, 4), new_ms=round(n, 4),
-                                                           margin=round(margin, 4), new_over_base=round(n / base, 4),
-                                                           slower_beyond_margin=bool(n / base > 1 + margin), same_bytes=same[name])
-        print(f"sink 0, {name:18s} base {a:7.3f} / {b:7.3f} ms  in-tree {n:7.3f} ms  new / base {n / base:6.4f}  margin {margin:6.4f}  same bytes {same[name]}")
+        rec[key]["windows"][name] = dict(window=list(w), sink=s, base_a_ms=round(a, 4), base_b_ms=round(b, 4), new_ms=round(n, 4),
+                                         margin=round(margin, 4), new_over_base=round(n / base, 4),
+                                         slower_beyond_margin=bool(n / base > 1 + margin), same_bytes=same[name])
+        print(f"sink {s}, {name:26s} base {a:7.3f} / {b:7.3f} ms  in-tree {n:7.3f} ms  new / base {n / base:6.4f}  margin {margin:6.4f}  same bytes {same[name]}")
 
 with open(out_path, "w") as f:
     json.dump(rec, f, indent=1)
