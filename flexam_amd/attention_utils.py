@@ -10,7 +10,8 @@ FLEXAM_SAGE_SMOOTH_V=1 V - mean_tokens(V), the mean added back to the output in 
 `causal` and `window_size` are flash-attn's (attention_utils.py:43-171 hands them to flash_attn_varlen_func): window_size = (left, right),
 a negative side unbounded, query i sees key j iff j >= i - left and j <= i + right; causal=True sets right = 0.  They are served by the
 windowed bf16 kernel (hip.attn_fwd_window) for Lq == Lk with q_lens / k_lens absent or all equal to that length.  Under SAGE_ATTENTION
-a mask also runs that bf16 kernel: the MXFP8 kernel has no mask -- and the reference's own `sageattn` call forwards is_causal only and
+a mask also runs that bf16 kernel unless FLEXAM_SAGE_WINDOW=1 (default 0, opt-in: quality on a real checkpoint is not measured), which
+runs the windowed MXFP8 kernel (hip.attn_fwd_fp8 with a window) -- the reference's own `sageattn` call forwards is_causal only and
 drops window_size (attention_utils.py:195-203), which this seam does not imitate."""
 import os
 import warnings
@@ -18,7 +19,7 @@ import warnings
 import torch
 
 from . import hip
-from .dit_layout import smooth_k_asked, smooth_v_asked
+from .dit_layout import sage_window_asked, smooth_k_asked, smooth_v_asked
 
 
 def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0.0, softmax_scale=None, q_scale=None, causal=False,
@@ -39,6 +40,14 @@ def attention(q, k, v, q_lens=None, k_lens=None, dropout_p=0.0, softmax_scale=No
         if lq != lk or any(x != lq for x in lens):
             raise NotImplementedError("flexam_amd.attention: causal / window_size with Lq != Lk or with q_lens / k_lens other than the full "
                                       "length is not served: flash-attn aligns such a mask bottom-right, SDPA top-left")
+        # FLEXAM_SAGE_WINDOW=1 (default 0) under SAGE_ATTENTION: the windowed MXFP8 launch, packed as the unmasked SAGE call below packs
+        sage = (attention_type if attention_type is not None else os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION")) == "SAGE_ATTENTION"
+        if sage and sage_window_asked(os.environ) and not torch.is_grad_enabled() and d == hip.ATTN_HEAD_DIM:
+            scale = (softmax_scale if softmax_scale is not None else d ** -0.5) * 1.4426950408889634
+            mean = hip.k_mean(k.view(b * lk, n * d), None, None, None, lk) if smooth_k_asked(os.environ) else None
+            v_mean = hip.k_mean(v.view(b * lk, n * d), None, None, None, lk) if smooth_v_asked(os.environ) else None
+            bufs = hip.attn_fp8_pack((q.float() * scale).to(torch.bfloat16), k, v, k_shift=mean, v_shift=v_mean)
+            return hip.attn_fwd_fp8(bufs, lq, o_shift=v_mean, window=window).to(out_dtype)
         return hip.attn_fwd_window(q, k, v, window, softmax_scale=softmax_scale).to(out_dtype)
     uniform = True
     if k_lens is not None:

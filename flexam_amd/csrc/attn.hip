@@ -848,6 +848,9 @@ struct AttnCall {
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
 struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
 constexpr int ATTN_INSTANCES = 12;
+// the two windowed MXFP8 kernels take their mask as a second argument; defined at the end of this file, as the two below
+struct Attn8WindowInstance { void (*kern)(AttnParams, Attn8Window); int slot; };      // slot in win_attr_set (attn_run)
+Attn8WindowInstance attn8_window_instance(bool oshift);
 // the two attn_window_frames_kernel instances (slots 10 and 11).  Defined at the end of this file, so that they are emitted behind every
 // other kernel of it: a listing of this file then differs from one without them by the two kernels alone (tools/isa_diff.py)
 AttnInstance attn_frames_instance(bool prescaled);
@@ -909,16 +912,34 @@ int attn_run(const AttnCall& c) {
   // a sink that holds every key leaves no mask; one under a window without a left bound (nothing lies to the left of it) adds no key
   const bool window = (win_left >= 0 || win_right >= 0) && c.win_sink < c.Lk;
   const int win_sink = win_left < 0 ? 0 : c.win_sink;
-  FX_REQUIRE(!window || (c.Lq == c.Lk && !c.q8 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
-             "attn_fwd: a window goes with bf16 operands of one length and whole work units");
+  FX_REQUIRE(!window || (c.Lq == c.Lk && c.kv8_chunk_tiles == 0 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
+             "attn_fwd: a window goes with operands of one length (MXFP8: one chunk) and whole work units");
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
   // (in the words of four MXFP8 fields above: see AttnParams.  A token window leaves win_frame 0, the low word of the null qs, and runs
   //  the instances that do not read it)
-  if (window) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; if (c.win_by_frames) p.win_frame = c.win_frame; }
+  const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
+  if (window && !fp8) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; if (c.win_by_frames) p.win_frame = c.win_frame; }
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
-  const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
+  if (window && fp8) {
+    // the windowed MXFP8 kernels read the four MXFP8 words of AttnParams AND a window: theirs is an argument of its own (Attn8Window).
+    // One workgroup per unit, every unit whole
+    const Attn8Window w = {win_left, win_right, win_sink, c.win_by_frames ? c.win_frame : 0};
+    const Attn8WindowInstance wi = attn8_window_instance(c.o_shift != nullptr);
+    constexpr int F8 = NSLOT * REC_BYTES;
+    static bool win_attr_set[FLEXAM_MAX_DEVICES][2] = {};
+    bool& raised = win_attr_set[flexam_current_device()][wi.slot];
+    if (!raised) {
+      if (hipFuncSetAttribute((const void*)wi.kern, hipFuncAttributeMaxDynamicSharedMemorySize, F8) != hipSuccess)
+        return flexam_fail(FLEXAM_E_LAUNCH, "attn_fwd: cannot raise dynamic LDS to %d bytes", F8);
+      raised = true;
+    }
+    const int n = c.B * c.H * p.q_blocks;
+    p.unit0 = 0; p.n_units = n; p.kv_splits = 1; p.tiles_per_split = tiles_all;
+    hipLaunchKernelGGL(wi.kern, dim3(n), dim3(NT), F8, (hipStream_t)c.stream, p, w);
+    return flexam_check_launch("flexam_attn_fwd_fp8_window");
+  }
   const bool short_ctx = !window && !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
   const bool full = !window && !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
   const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window, window && c.win_by_frames);
@@ -1182,6 +1203,19 @@ extern "C" int flexam_attn_fwd_fp8_chunked(const void* q8, const void* qs, const
   return attn_run(c);
 }
 
+extern "C" int flexam_attn_fwd_fp8_window(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
+                                          int head_dim, int window_left, int window_right, int sink, int frame_tokens, const float* o_shift,
+                                          void* stream) {
+  FX_REQUIRE(q8 && qs && kv8, FLEXAM_E_ARG, "attn_fwd_fp8_window: null pointer");
+  FX_REQUIRE(((uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG, "attn_fwd_fp8_window: misaligned pointer");
+  FX_REQUIRE(frame_tokens >= 0, FLEXAM_E_ARG, "attn_fwd_fp8_window: frame_tokens %d (0 = a token window)", frame_tokens);
+  AttnCall c;
+  c.q8 = q8; c.qs = qs; c.kv8 = kv8; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = FLEXAM_ATTN_PRESCALED; c.stream = stream; c.o_shift = o_shift;
+  c.win_left = window_left; c.win_right = window_right; c.win_sink = sink; c.win_by_frames = frame_tokens > 0; c.win_frame = frame_tokens;
+  return attn_run(c);
+}
+
 extern "C" int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int head_dim, float softmax_scale,
                                  int n_slots, const float* ws_o, const float* ws_ml, void* stream) {
   FX_REQUIRE(o && ws_o && ws_ml, FLEXAM_E_ARG, "attn_merge: null pointer");
@@ -1200,5 +1234,9 @@ AttnInstance attn_frames_instance(bool prescaled) {      // (declared next to at
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES;
   if (prescaled) return {attn_window_frames_kernel<true>, BF, 11};
   return {attn_window_frames_kernel<false>, BF, 10};
+}
+Attn8WindowInstance attn8_window_instance(bool oshift) {      // (the windowed MXFP8 kernels, see attn_fp8.inc: why it stands here)
+  if (oshift) return {attn8_window_oshift_kernel<0>, 1};
+  return {attn8_window_kernel<0>, 0};
 }
 }  // namespace

@@ -39,11 +39,27 @@ __device__ __forceinline__ i32x8 join8(u32x4 lo, u32x4 hi) {
   return (i32x8){(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3], (int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
 }
 
-// The kernel's body, inlined into its two __global__ wrappers below (KIND: the profiler symbol, as attn_fwd_kernel's).  OSHIFT: the
+// The mask of the windowed instances (attn8_window_kernel, attn8_window_oshift_kernel; flexam_attn_fwd_fp8_window), a kernel argument of
+// their own: in AttnParams the window words of the bf16 kernel ARE the MXFP8 words (qs, lq_pad, the two chunk words), which this kernel
+// reads, and a longer AttnParams would move the kernarg loads of every other instance.  Lq == Lk = L; row i sees key j iff j < sink or
+// lo(i) <= j <= hi(i), with lo = i - left, hi = i + right in tokens (frame = 0), or lo = (i / T - left) T, hi = (i / T + right + 1) T - 1
+// with frame = T > 0; a negative side is unbounded.  The rule of the bf16 kernel's WIN / FRAMES instances (attn.hip).
+struct Attn8Window { int left, right, sink, frame; };
+
+// The kernel's body, inlined into its __global__ wrappers below (KIND: the profiler symbol, as attn_fwd_kernel's).  OSHIFT: the
 // epilogue adds p.o_shift (smooth-V) to O / l in fp32 in front of the rounding to bf16 -- loaded behind the key loop, nothing of it inside.
 // p by value, as the kernel had it: by reference hipcc allocates the loop differently (186 instead of 188 VGPRs, another schedule).
-template <int KIND, bool OSHIFT>
-__device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
+// WIN (whole units only): the unit walks the sink tiles and the key tiles that hold a key one of its 256 rows sees, as the bf16 kernel's
+// WIN instance does and by its arithmetic (local tile indices in the loop and the ring; issue_tile maps them to global tiles).  Tiles in
+// which every row sees every key run the step as it is; in the others -- the ragged last tile among them -- ONE uniform branch in front of
+// the row maxima sets the scores of the keys the lane's row does not see to -inf (mask_window; keys past L lie past every row's hi).
+// A row's reference cannot come from half tile 0, in which the row may see no key: it stays 0 and the row `unstarted` (gate = -inf: any
+// finite score passes the test of the rescale branch) until the first half tile in which it sees one, whose maximum sets the first
+// reference the way the prologue does for every row of the other instances -- O = l = 0 until then, so nothing is rescaled, and rd
+// counts from there.  A half tile in which a row sees nothing is all -inf: its maximum moves no reference (-inf passes no test; the
+// factors are selected, never computed from it) and its exponentials are exactly 0.  Every row sees its own key: l > 0 at the end.
+template <int KIND, bool OSHIFT, bool WIN = false>
+__device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Window w = {}) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // ring of 4 records
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -52,7 +68,8 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
 
   int split = 0, ul, unit, tps = p.tiles_per_split, partial = p.partial;
   if (!unit_of_workgroup(p, split, ul, unit, tps, partial)) return;
-  const int qb = unit % p.q_blocks;
+  int qb = unit % p.q_blocks;
+  if constexpr (WIN) qb = w.left < 0 ? p.q_blocks - 1 - qb : qb;      // units of a window without a left bound grow with the q block: longest first
   const int bh = unit / p.q_blocks;
   const int head = bh % p.H, b = bh / p.H;
 
@@ -81,8 +98,32 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
   const char* vsaddr = smem + REC_VS + 2 * r_ + h_;
 
   const int tiles_all = (p.Lk + KVBLK - 1) / KVBLK;
-  const int t0 = split * tps;
-  const int ntiles = min(tps, tiles_all - t0);
+  // WIN: the unit's w_n tiles = the sink tiles [0, s_n), then (behind `gap` tiles no row sees) the window's; [ti_lo, ti_hi] (local) are the
+  // window tiles every row sees whole, s_full the tiles wholly below the sink.  attn_fwd_body's arithmetic, word for word (restated, not
+  // shared: the bf16 windowed instances keep the parent's machine code, and FRAMES is a template argument there, w.frame > 0 a test here)
+  int w_n = 0, ti_lo = 0, ti_hi = 0, s_n = 0, s_full = 0, gap = 0;
+  if constexpr (WIN) {
+    const int qa = qb * QBLK, qz = min(qa + QBLK, p.Lq) - 1;      // first and last row of the unit
+    int fa = 0, fz = 0;
+    if (w.frame > 0) { fa = (int)((unsigned)qa / (unsigned)w.frame); fz = (int)((unsigned)qz / (unsigned)w.frame); }
+    const int lo_a = w.frame > 0 ? (fa - w.left) * w.frame : qa - w.left;
+    const int hi_z = w.frame > 0 ? (fz + w.right + 1) * w.frame - 1 : qz + w.right;
+    const int k_first = w.left < 0 ? 0 : max(0, lo_a);
+    const int k_last = w.right < 0 ? p.Lk - 1 : min(p.Lk - 1, hi_z);
+    s_n = (min(w.sink, p.Lk) + KVBLK - 1) / KVBLK;
+    s_full = w.sink / KVBLK;
+    gap = max(0, k_first / KVBLK - s_n);
+    w_n = max(k_last / KVBLK, s_n - 1) + 1 - gap;
+    const int lo_z = w.frame > 0 ? (fz - w.left) * w.frame : qz - w.left;
+    ti_lo = w.left < 0 ? 0 : (max(0, lo_z) + KVBLK - 1) / KVBLK;
+    const int hi_a = w.frame > 0 ? (fa + w.right + 1) * w.frame - 1 : qa + w.right;
+    const int top_key = hi_a - (KVBLK - 1);
+    ti_hi = min(w.right < 0 ? tiles_all : top_key >= 0 ? top_key / KVBLK : -1, p.Lk / KVBLK - 1);      // (whole tiles only)
+    ti_lo -= gap;
+    ti_hi -= gap;
+  }
+  const int t0 = WIN ? 0 : split * tps;
+  const int ntiles = WIN ? w_n : min(tps, tiles_all - t0);
   // records: [chunk][B][H][chunk_tiles]; one chunk holds all tiles unless the records came out of a sequence-parallel all-gather
   // (flexam_attn_fwd_fp8_chunked).  Tile g = t0 + t -> chunk g / chunk_tiles by one scalar multiply-high (uniform: scalar registers)
   const unsigned ct = (unsigned)p.kv8_chunk_tiles, cmagic = p.kv8_chunk_magic;
@@ -92,8 +133,8 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
   const unsigned voff16 = (unsigned)tid * 16u;
   auto issue_tile = [&](int t, int parts, int tslot = -1) {      // parts: 1 = K (+ the scales of both), 2 = V; tslot: the ring position (default t)
     const unsigned slot = lds0 + (unsigned)(((tslot < 0 ? t : tslot) & (NSLOT - 1)) * REC_BYTES);
-    const unsigned gt = (unsigned)(t0 + t);
-    const unsigned chunk = ct > 1 ? __umulhi(gt, cmagic) : gt;
+    const unsigned gt = WIN ? (unsigned)(t < s_n ? t : t + gap) : (unsigned)(t0 + t);      // (WIN: one chunk holds all tiles)
+    const unsigned chunk = WIN ? 0u : ct > 1 ? __umulhi(gt, cmagic) : gt;
     const char* src = rec0 + (chunk * chunk_recs + (gt - chunk * ct)) * REC_BYTES;
     if (parts & 1) {
       lds_dma16_sbase(src, voff16, slot + wave * 1024);
@@ -124,6 +165,27 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) sacc[e] = (e & 3) + 8 * (e >> 2) < lim ? sacc[e] : -INFINITY;
   };
+  // WIN: keys the lane's row does not see -> -inf.  Element e is key 32 gg + 4 h + (e & 3) + 8 (e >> 2) of global half gg; the row's bounds
+  // (hi clipped to the last key: this is the mask of the ragged tile too) and the sink less 4 h are the three per-lane values, the
+  // half's base is uniform.  The visible in-half positions as ONE bit mask, as attn_fwd_body's mask_window has them and for its reason.
+  int w_lo = 0, w_hi = 0, w_sk = 0;
+  if constexpr (WIN) {
+    const int row = q0 + r_, h4 = 4 * h_;
+    const int f = w.frame > 0 ? (int)((unsigned)row / (unsigned)w.frame) : 0;
+    w_lo = w.left < 0 ? -(1 << 30) : (w.frame > 0 ? (f - w.left) * w.frame : row - w.left) - h4;
+    w_hi = (w.right < 0 ? p.Lk - 1 : min(p.Lk - 1, w.frame > 0 ? (f + w.right + 1) * w.frame - 1 : row + w.right)) - h4;
+    w_sk = w.sink - h4;
+  }
+  auto mask_window = [&](int g, f32x16& sacc) {
+    const int tl = g >> 1;
+    const int base = (2 * (tl < s_n ? tl : tl + gap) + (g & 1)) * 32;
+    const int lo = w_lo - base, hi = w_hi - base, sk = w_sk - base;
+    const unsigned below_sk = (1u << min(max(sk, 0), 28)) - 1u, below_lo = (1u << min(max(lo, 0), 28)) - 1u, to_hi = (1u << min(max(hi + 1, 0), 28)) - 1u;
+    const unsigned seen = below_sk | (to_hi & ~below_lo);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sacc[e] = seen & (1u << ((e & 3) + 8 * (e >> 2))) ? sacc[e] : -INFINITY;
+  };
+  float gate = WIN ? -INFINITY : F8_RESCALE_THR;      // WIN: what a row's maximum less its reference must exceed for the reference to move; -inf = unstarted
   f32x16 o_acc[4];
 #pragma unroll
   for (int dt = 0; dt < 4; ++dt)
@@ -159,7 +221,7 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
   }
   i32x8 kf_pre = k_read(IC<1>{}, IC<0>{});
   int ks_nxt = ks_read(IC<1>{});
-  {   // the first reference (= ref0): a whole number 2^6 ... 2^7 below the row maximum of half tile 0's VALID keys -- a range whose
+  if constexpr (!WIN) {   // the first reference (= ref0): a whole number 2^6 ... 2^7 below the row maximum of half tile 0's VALID keys -- a range whose
       // only tile holds fewer than 32 keys has padding here (zero rows: score 0), which would otherwise set ref0 and flush P to zero
     mask_half(0, s_a);
     float mx = s_a[0];
@@ -181,6 +243,10 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
     constexpr int g8 = decltype(g8_c)::value;
     constexpr int cur = (g8 >> 1) & 1;                   // pk[cur]: this tile's P, pk[cur ^ 1]: the previous tile's
     if constexpr (MASK) mask_half(g, s_cur);
+    if constexpr (WIN) {
+      const int tl = g >> 1;               // (local: a tile below s_full is its own global index)
+      if (tl >= s_full && (tl < ti_lo || tl > ti_hi)) mask_window(g, s_cur);
+    }
     // first K fragment and the scales of the next half tile: read here, used behind the row maxima (held across part B of the
     // previous step instead, they are 8 registers the loop does not have)
     const i32x8 kf0 = kf_pre;                         // read behind the last MFMA of the previous step (part B, block 3)
@@ -189,11 +255,20 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
     const float m1 = vmax8(s_cur[8], s_cur[9], s_cur[10], s_cur[11], s_cur[12], s_cur[13], s_cur[14], s_cur[15]);
     const float mloc = vmax(m0, m1) - ref;            // relative to the row reference
     s_nxt = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(kf0, qf0, zero16, 0, 0, 0, ks_nxt, 0, qsc);
-    if (__any(mloc > F8_RESCALE_THR)) {
+    if (WIN ? __any(mloc > gate) : __any(mloc > F8_RESCALE_THR)) {
       // rows whose maximum stays below the threshold keep their reference; the others move it by a whole number to 2^6 ... 2^7
       // below the maximum (as far as the cap allows).  Only the row sum is rescaled (see the file header).
       const float mx = pair_max(mloc);
-      const float delta = fminf(mx > F8_RESCALE_THR ? floorf(mx - F8_REF_HEAD) : 0.f, F8_RD_MAX - rd);
+      float delta = fminf(mx > F8_RESCALE_THR ? floorf(mx - F8_REF_HEAD) : 0.f, F8_RD_MAX - rd);
+      if constexpr (WIN) {
+        // an unstarted row (reference 0, O = l = 0, rd = 0) takes floor(its first maximum) - 6 as its FIRST reference: rd stays 0, the
+        // cap counts from here, nothing is rescaled; while that maximum is -inf the row stays unstarted
+        const bool started = gate > -INFINITY, live = mx > -INFINITY;
+        const float first = live ? floorf(mx) - F8_REF_HEAD : 0.f;
+        ref += started ? 0.f : first;
+        delta = started ? delta : 0.f;
+        gate = started || live ? F8_RESCALE_THR : -INFINITY;
+      }
       ref += delta;
       rd += delta;
       l_run *= __builtin_amdgcn_exp2f(-delta);
@@ -278,10 +353,11 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p) {
     tile(t + 3, IC<3>{}, M_{});
   }
   const int rem = ntiles - t;               // 1..4 tail tiles (the last one may be partial), same code with static slots and the mask
-  tile(t, IC<0>{}, T_{});
-  if (rem > 1) tile(t + 1, IC<1>{}, T_{});
-  if (rem > 2) tile(t + 2, IC<2>{}, T_{});
-  if (rem > 3) tile(t + 3, IC<3>{}, T_{});
+  using TM_ = std::integral_constant<bool, !WIN>;      // (WIN: mask_window masks the keys past the end as well)
+  tile(t, IC<0>{}, TM_{});
+  if (rem > 1) tile(t + 1, IC<1>{}, TM_{});
+  if (rem > 2) tile(t + 2, IC<2>{}, TM_{});
+  if (rem > 3) tile(t + 3, IC<3>{}, TM_{});
   // pending PV of the last tile: slot (ntiles - 1) & 3, operand pk[(ntiles - 1) & 1]
   auto pv_last = [&](auto slot_c) {
     constexpr int sl = decltype(slot_c)::value;
@@ -319,6 +395,13 @@ template <int KIND>
 __global__ __launch_bounds__(NT, 2) void attn8_fwd_kernel(AttnParams p) { attn8_fwd_body<KIND, false>(p); }
 // the same kernel with the output shift: a symbol of its own (flexam_attn_fwd_fp8_oshift)
 __global__ __launch_bounds__(NT, 2) void attn8_oshift_kernel(AttnParams p) { attn8_fwd_body<0, true>(p); }
+// The windowed instances (flexam_attn_fwd_fp8_window), without and with the output shift.  Templates for the order of emission alone:
+// hipcc emits a template's instances in the order of their first use, and attn8_window_instance at the end of attn.hip is theirs -- a
+// listing of that file then differs from one without them by the two kernels alone (tools/isa_diff.py), the labels of the others included
+template <int KIND>
+__global__ __launch_bounds__(NT, 2) void attn8_window_kernel(AttnParams p, Attn8Window w) { attn8_fwd_body<KIND, false, true>(p, w); }
+template <int KIND>
+__global__ __launch_bounds__(NT, 2) void attn8_window_oshift_kernel(AttnParams p, Attn8Window w) { attn8_fwd_body<KIND, true, true>(p, w); }
 
 // ---- the pack kernel: q, k (after RMSNorm + RoPE; q carrying softmax_scale * log2 e) and v, bf16 [B, L, H, 128] -> MXFP8 operands.
 // One workgroup per (64-token tile, head, batch).  K and Q: thread = (token row, 32-channel block); V: thread = (channel, 32-key half

@@ -26,7 +26,7 @@ from typing import List, Optional
 import torch
 
 from . import hip
-from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, smooth_k_asked, smooth_v_asked
+from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, sage_window_asked, smooth_k_asked, smooth_v_asked
 from .dit_sp import HeadAllToAll, KVGather, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
@@ -429,7 +429,9 @@ class DiTEngine:
             import warnings
             warnings.warn("flexam_amd: FLEXAM_SAGE_SMOOTH_V=1 is ignored under sequence parallelism: V is quantised as it is",
                           RuntimeWarning, stacklevel=3)
-        if (window != (-1, -1) or frames != (-1, -1)) and m.sage:      # the MXFP8 kernel has no mask: the windowed bf16 kernel runs
+        # FLEXAM_SAGE_WINDOW=1 (default 0): a windowed model under SAGE runs the windowed MXFP8 kernel (flexam_attn_fwd_fp8_window); the mode
+        # keeps `sage` then, which tells a launch plan of it from one of the replacement below.  Without the switch:
+        if (window != (-1, -1) or frames != (-1, -1)) and m.sage and not sage_window_asked(env):      # the windowed bf16 kernel runs
             m = m._replace(sage=False, sage_gather=False, sage_fused=False)
             self._smooth_k = self._smooth_v = False
             if not DiTEngine._sage_window_warned:          # said once per process
@@ -676,7 +678,9 @@ class DiTEngine:
         if m.sage:
             bufs = self._attn8_buffers(nb, m.lc)
             v_mean = self._norm_rope_qk(p, m, ws, nb, bufs)
-            hip.attn_fwd_fp8(bufs, m.lc, out=ao4[:nb], o_shift=v_mean)
+            # (a window here: FLEXAM_SAGE_WINDOW=1, else _mode cleared `sage`; without one the call is the one it has always been)
+            window, frame_t = (self.window, 0) if self.window_frames == (-1, -1) else self._window_frames()
+            hip.attn_fwd_fp8(bufs, m.lc, out=ao4[:nb], o_shift=v_mean, window=window, sink=self.window_sink, frame_tokens=frame_t)
         else:
             self._norm_rope_qk(p, m, ws, nb)
             if self.window != (-1, -1):

@@ -103,6 +103,13 @@ def smooth_v_asked(env) -> bool:
     return env.get("FLEXAM_SAGE_SMOOTH_V", "0") == "1"
 
 
+def sage_window_asked(env) -> bool:
+    """FLEXAM_SAGE_WINDOW=1 (default 0): a windowed self-attention (window_size / window_frames, with window_sink) under SAGE_ATTENTION
+    runs the windowed MXFP8 kernel instead of falling back to the windowed bf16 one.  Not a field of _Mode: with it the mode keeps
+    `sage`, without it DiTEngine._mode clears it, so the two forwards already differ in their mode and their launch plans."""
+    return env.get("FLEXAM_SAGE_WINDOW", "0") == "1"
+
+
 def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, parallel: Parallel, B, L, dens_same,
                  bx, R, rows_per_batch, only_row, rows_shared, teacache: bool) -> _Mode:
     """The mode of one forward.  env: the environment mapping; fused .. parallel: the engine (all blocks native, layers, heads, head

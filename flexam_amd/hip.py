@@ -785,9 +785,11 @@ def _fp8_split_words(device, kv_splits, split_from_unit, batch_heads, lq, lk):
     return S, from_unit, _ptr(ws_o, F32), _ptr(ws_ml, F32)
 
 
-def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None, o_shift=None):
+def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None, o_shift=None, window=(-1, -1), sink=0, frame_tokens=0):
     """Self-attention from packed MXFP8 operands (attn_fp8_pack) -> out [B, L, H, 128] bf16.  o_shift (smooth-V, fp32 [B, H * 128]: the
-    v_shift the operands were packed with) is added to the output in fp32 before its one rounding (flexam_attn_fwd_fp8_oshift)."""
+    v_shift the operands were packed with) is added to the output in fp32 before its one rounding (flexam_attn_fwd_fp8_oshift).
+    window / sink / frame_tokens: attn_fwd_window's mask (flexam_attn_fwd_fp8_window: whole work units, so no kv_splits); the defaults
+    make the call this function has always made."""
     q8, qs, kv8 = bufs
     B, H, D = q8.shape[0], q8.shape[1], ATTN_HEAD_DIM
     _check_fp8_bufs(bufs, B, H, L, q8.device, "attn_fwd_fp8")
@@ -796,12 +798,20 @@ def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None, o_shif
     _packed_heads("attn_fwd_fp8", out)
     if tuple(out.shape) != (B, L, H, D):
         raise RuntimeError(f"attn_fwd_fp8: out must be [B={B}, L={L}, H={H}, {D}] with heads packed along the row, got {tuple(out.shape)}")
+    shift = _k_shift("attn_fwd_fp8", o_shift, B, H * D, q8.device, "o_shift") if o_shift is not None else None
+    left, right = attn_window(window)
+    if (left, right) != (-1, -1):
+        if kv_splits is not None:
+            raise RuntimeError("attn_fwd_fp8: a window runs whole work units (no kv_splits)")
+        _call("flexam_attn_fwd_fp8_window", _raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D,
+              left, right, int(sink), int(frame_tokens), shift)
+        return out
     args = (_raw(q8), _raw(qs), _raw(kv8), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, D,
             *_fp8_split_words(q8.device, kv_splits, split_from_unit, B * H, L, L))
     if o_shift is None:
         _call("flexam_attn_fwd_fp8", *args)
     else:
-        _call("flexam_attn_fwd_fp8_oshift", *args, _k_shift("attn_fwd_fp8", o_shift, B, H * D, q8.device, "o_shift"))
+        _call("flexam_attn_fwd_fp8_oshift", *args, shift)
     return out
 
 

@@ -215,7 +215,7 @@ class _SelfAttn(_Attn):
         (angle table, or the reference's complex exp(i angle) table)."""
         from . import hip
         from .dist import current_sp_context
-        from .dit_layout import smooth_k_asked, smooth_v_asked
+        from .dit_layout import sage_window_asked, smooth_k_asked, smooth_v_asked
         b, l, c = x.shape
         nh, hd = self.num_heads, self.head_dim
         sp = current_sp_context()
@@ -248,21 +248,27 @@ class _SelfAttn(_Attn):
                          tokens_per_batch=l, token_offset=0, head_dim=hd)
         q3 = qkv.view(b, l, 3 * c)
         q4, k4, v4 = (q3[:, :, i * c:(i + 1) * c].unflatten(2, (nh, hd)) for i in range(3))
-        if window != (-1, -1):
-            if n_keys < l:
-                raise NotImplementedError("flexam_amd: window_size with seq_lens shorter than the sequence is not served: flash-attn aligns "
-                                          "the mask of Lq != Lk bottom-right, SDPA top-left")
-            ao = hip.attn_fwd_window(q4, k4, v4, window, prescaled=True, sink=self.window_sink)      # (SAGE_ATTENTION too: the MXFP8 kernel has no mask)
-        elif frames != (-1, -1):
-            ao = hip.attn_fwd_window(q4, k4, v4, frames, prescaled=True, sink=self.window_sink, frame_tokens=frame_t)
+        sage = os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION" and not torch.is_grad_enabled() and hd == 128
+        if window != (-1, -1) and n_keys < l:
+            raise NotImplementedError("flexam_amd: window_size with seq_lens shorter than the sequence is not served: flash-attn aligns "
+                                      "the mask of Lq != Lk bottom-right, SDPA top-left")
+        masked = window != (-1, -1) or frames != (-1, -1)
+        if masked and not (sage and sage_window_asked(os.environ)):      # (SAGE_ATTENTION too, unless FLEXAM_SAGE_WINDOW=1: the windowed bf16 kernel)
+            if window != (-1, -1):
+                ao = hip.attn_fwd_window(q4, k4, v4, window, prescaled=True, sink=self.window_sink)
+            else:
+                ao = hip.attn_fwd_window(q4, k4, v4, frames, prescaled=True, sink=self.window_sink, frame_tokens=frame_t)
         elif n_keys < l:
             ao = hip.attn_fwd(q4, k4[:, :n_keys], v4[:, :n_keys], prescaled=True)
-        elif os.environ.get("VIDEOX_ATTENTION_TYPE", "FLASH_ATTENTION") == "SAGE_ATTENTION" and not torch.is_grad_enabled() and hd == 128:
+        elif sage:
             # the reference's attention() reads the switch per call (ATT.py:195-203); FLEXAM_SAGE_SMOOTH_K=1: K - mean_tokens(K) is quantised;
-            # FLEXAM_SAGE_SMOOTH_V=1: V - mean_tokens(V) is, and the kernel adds the mean back in fp32
+            # FLEXAM_SAGE_SMOOTH_V=1: V - mean_tokens(V) is, and the kernel adds the mean back in fp32; under a window (FLEXAM_SAGE_WINDOW=1)
+            # the windowed MXFP8 launch runs, else the call is the one it has always been
             mean = hip.k_mean(qkv[:, c:2 * c], None, None, None, l) if smooth_k_asked(os.environ) else None
             v_mean = hip.k_mean(qkv[:, 2 * c:3 * c], None, None, None, l) if smooth_v_asked(os.environ) else None
-            ao = hip.attn_fwd_fp8(hip.attn_fp8_pack(q4, k4, v4, k_shift=mean, v_shift=v_mean), l, o_shift=v_mean)
+            mask = dict(window=window, sink=self.window_sink) if window != (-1, -1) else \
+                dict(window=frames, sink=self.window_sink, frame_tokens=frame_t) if frames != (-1, -1) else {}
+            ao = hip.attn_fwd_fp8(hip.attn_fp8_pack(q4, k4, v4, k_shift=mean, v_shift=v_mean), l, o_shift=v_mean, **mask)
         else:
             ao = hip.attn_fwd(q4, k4, v4, prescaled=True)
         return hip.gemm(ao.view(b * l, c), pk["wo"], pk["bo"]).view(b, l, c)

@@ -271,6 +271,22 @@ int flexam_attn_fwd_fp8_oshift(const void* q8, const void* qs, const void* kv8, 
 int flexam_attn_fwd_fp8_chunked(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
                                 int Lq, int Lk, int chunk_tiles, int head_dim, int kv_splits, int split_from_unit, float* ws_o,
                                 float* ws_ml, void* stream);
+/* flexam_attn_fwd_fp8 under the masks of flexam_attn_fwd_window / _window_sink / _window_frames, Lq == Lk = L, whole work units (no
+ * split-KV): query i sees key j iff j < sink or lo(i) <= j <= hi(i), both clipped to [0, L) and a negative side unbounded.
+ * frame_tokens = 0: a token window, lo = i - window_left, hi = i + window_right.  frame_tokens = T > 0: the two words count frames of T
+ * tokens from token 0, lo = (i / T - window_left) T, hi = (i / T + window_right + 1) T - 1.  The operands are what flexam_attn_fp8_pack*
+ * and flexam_rmsnorm_rope_mx* write (one chunk).  A work unit visits the sink tiles and the tiles that hold a key one of its 256 rows
+ * sees, as the bf16 windowed kernel does; the kernels are instances of the MXFP8 kernel under their own symbols (attn8_window_kernel,
+ * attn8_window_oshift_kernel) that take the four window words as a kernel argument of their own.  A row's first reference comes from
+ * the first half tile in which it sees a key (floor(max of the scores it sees there) - 6), and the cap of 96 counts from there; keys it
+ * does not see weigh exactly 0 and are in no row sum.  Smooth-K's operands need nothing new (q.c is one number per row whatever the
+ * mask); o_shift != NULL adds smooth-V's shift as flexam_attn_fwd_fp8_oshift does (the rows of a masked softmax sum to 1 as well), NULL
+ * is the plain instance.  Normalisations, each the very launch named: no bound on either side (or both reaching past the sequence from
+ * every row), sink >= L, or frame_tokens >= L is flexam_attn_fwd_fp8 (with o_shift: _oshift) at kv_splits = 1; window_left < 0 drops
+ * the sink.  sink < 0 and frame_tokens < 0 are FLEXAM_E_ARG. */
+int flexam_attn_fwd_fp8_window(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
+                               int head_dim, int window_left, int window_right, int sink, int frame_tokens, const float* o_shift,
+                               void* stream);
 
 /* out_bf16[m,:] = LN(x_f32[m,:]; eps) [* ln_w + ln_b] [* scale[row(m),:] + shift[row(m),:]]
  * row(m) = row_index[m] if row_index else m / rows_per_batch; scale rows already hold (1+scale),

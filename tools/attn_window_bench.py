@@ -25,7 +25,15 @@ window of the same span, (448 k, 448 k) with the same sink: the frame form visit
 tokens are 7 key tiles), `faster_per_visited_tile` records which of the two takes less time per tile it visits.  With --base the same
 call times the token-window launches (frame_tokens = 0, every sink of the list) of the in-tree library against that build, as above.
 
+--sage [--base=...]: the windows under the MXFP8 kernel (hip.attn_fwd_fp8 with a window: FLEXAM_SAGE_WINDOW=1's launch) -> profiles/
+attn_window_sage_bench.json.  Arms: the full MXFP8 launch (hip.attn_fwd_fp8, the engine's call: tail split and merge included), the
+token windows of +-2 / +-5 / +-12 frames and the frame windows +-2 / +-5 / +-12, (-1, 0) and (0, 0), each with sink 0 and 448.  Per
+arm: the time, its share of the full MXFP8 launch, the share of tiles visited, and the time of the bf16 windowed launch of the SAME mask
+taken in the same call (the two alternate inside every round), `mxfp8_over_bf16` their ratio.  With --base the unwindowed MXFP8
+launch and the full bf16 launch of the in-tree library are timed against that build as above (base, in-tree, base).  No condition.
+
 usage: attn_window_bench.py [--iters=10] [--rounds=7] [--out=profiles/attn_window_bench.json]
+       attn_window_bench.py --sage [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sage_bench.json]
        attn_window_bench.py --sink=0,448,896 [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sink_bench.json]
        attn_window_bench.py --frames[=2,5,12] [--sink=0,448] [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_frames_bench.json]"""
 import json
@@ -88,6 +96,93 @@ def timed(window, sink=0, frame_tokens=0):
     torch.cuda.synchronize()
     return a.elapsed_time(b) / iters
 
+
+def timed_call(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(iters):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / iters
+
+
+def sage_bench():
+    """--sage: see the module docstring."""
+    bufs = H.attn_fp8_pack(q, k, v)
+    masks = [(f"tokens_{n}_{n}_sink_{s}", (FRAME * n, FRAME * n), s, 0) for n in (2, 5, 12) for s in (0, FRAME)]
+    masks += [(f"{name}_sink_{s}", w, s, FRAME) for name, w in [(f"frames_{n}_{n}", (n, n)) for n in (2, 5, 12)] +
+              [("frames_block_causal", (-1, 0)), ("frames_per_frame", (0, 0))] for s in (0, FRAME)]
+    calls = {"full": lambda: H.attn_fwd_fp8(bufs, L, out=o), "full_bf16": lambda: launch(None)}
+    for name, w, s, ft in masks:
+        calls[name] = lambda w=w, s=s, ft=ft: H.attn_fwd_fp8(bufs, L, out=o, window=w, sink=s, frame_tokens=ft)
+        calls[name + "/bf16"] = lambda w=w, s=s, ft=ft: launch(w, s, ft)
+    for fn in calls.values():                      # warm-up: every instance once
+        fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in calls}
+    for _ in range(rounds):
+        for name, fn in calls.items():
+            ms[name].append(timed_call(fn))
+    med = {name: statistics.median(x) for name, x in ms.items()}
+    arms = dict(full=dict(ms=round(med["full"], 4), ms_min=round(min(ms["full"]), 4), ms_max=round(max(ms["full"]), 4), bf16_ms=round(med["full_bf16"], 4),
+                          mxfp8_over_bf16=round(med["full"] / med["full_bf16"], 4)))
+    print(f"{'full':32s} {med['full']:8.3f} ms  bf16 {med['full_bf16']:8.3f} ms  mxfp8 / bf16 {med['full'] / med['full_bf16']:6.3f}")
+    for name, w, s, ft in masks:
+        t, tb, sh = med[name], med[name + "/bf16"], share(w, 0 if w[0] < 0 else s, ft)
+        arms[name] = dict(window=list(w), sink=s, frame_tokens=ft, ms=round(t, 4), ms_min=round(min(ms[name]), 4), ms_max=round(max(ms[name]), 4),
+                          tile_share=round(sh, 4), time_ratio=round(t / med["full"], 4), time_per_tile_ratio=round(t / med["full"] / sh, 3),
+                          bf16_ms=round(tb, 4), bf16_time_ratio=round(tb / med["full_bf16"], 4), mxfp8_over_bf16=round(t / tb, 4))
+        print(f"{name:32s} {t:8.3f} ms  tiles {sh:6.4f}  of full mxfp8 {t / med['full']:6.3f}  bf16 same mask {tb:8.3f} ms  mxfp8 / bf16 {t / tb:6.3f}")
+    rec = dict(shape=dict(B=B, H=heads, L=L, head_dim=D, frame_tokens=FRAME), iters=iters, rounds=rounds, device=torch.cuda.get_device_name(0),
+               method="one process, every MXFP8 arm and the bf16 windowed launch of the same mask alternating per round, device events around "
+                      "`iters` back-to-back launches, median over the rounds; time_ratio: of the full MXFP8 launch (hip.attn_fwd_fp8)",
+               arms=arms, windowed_mxfp8_faster_than_windowed_bf16={name: bool(med[name] < med[name + "/bf16"]) for name, *_ in masks})
+    if opt.get("base"):
+        import ctypes
+        base_lib, new_lib = ctypes.CDLL(os.path.abspath(opt["base"])), H.load_library(H.LIB_PATH)
+        for fn_name, (argtypes, restype) in H._SIGNATURES.items():
+            fn = getattr(base_lib, fn_name, None)
+            if fn is not None:
+                fn.argtypes, fn.restype = argtypes, restype
+        libs = {"base_a": base_lib, "new": new_lib, "base_b": base_lib}
+        outs = {tag: torch.empty_like(q) for tag in ("base_a", "new")}
+        both = {"mxfp8_full": lambda out=o: H.attn_fwd_fp8(bufs, L, out=out), "bf16_full": lambda out=o: launch(None, out=out)}
+        same, ab = {}, {name: {tag: [] for tag in libs} for name in both}
+        for name, fn in both.items():              # warm-up of both builds, and the bytes they give
+            for tag in outs:
+                H._lib = libs[tag]
+                fn(outs[tag])
+            torch.cuda.synchronize()
+            same[name] = bool(torch.equal(outs["base_a"], outs["new"]))
+        order = list(libs)
+        for r in range(rounds):
+            for name, fn in both.items():
+                for tag in order[r % 3:] + order[:r % 3]:
+                    H._lib = libs[tag]
+                    ab[name][tag].append(timed_call(fn))
+        H._lib = new_lib
+        rec["unwindowed_against_base"] = dict(method="the unwindowed MXFP8 launch (hip.attn_fwd_fp8) and the full bf16 launch (hip.attn_fwd) of the base build "
+                                              "and of the in-tree build in this process: per round base, in-tree, base again in rotating order; margin = the "
+                                              "base build against itself", launches={})
+        for name in both:
+            a, n, b = (statistics.median(ab[name][tag]) for tag in libs)
+            base = statistics.median(ab[name]["base_a"] + ab[name]["base_b"])
+            margin = abs(a - b) / base
+            rec["unwindowed_against_base"]["launches"][name] = dict(base_a_ms=round(a, 4), base_b_ms=round(b, 4), new_ms=round(n, 4), margin=round(margin, 4),
+                                                                    new_over_base=round(n / base, 4), slower_beyond_margin=bool(n / base > 1 + margin),
+                                                                    same_bytes=same[name])
+            print(f"{name:12s} base {a:7.3f} / {b:7.3f} ms  in-tree {n:7.3f} ms  new / base {n / base:6.4f}  margin {margin:6.4f}  same bytes {same[name]}")
+    path = os.path.join(root, opt.get("out", "profiles/attn_window_sage_bench.json"))
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
+
+
+if "sage" in opt:
+    sage_bench()
+    sys.exit(0)
 
 for _, w, s, ft in ARMS:                           # warm-up: every instance once (LDS attribute, code load), then the clock
     launch(w, s, ft)

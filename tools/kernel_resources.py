@@ -1,5 +1,5 @@
 """Register / scratch footprint of every kernel in libflexam_hip.so, read from the code objects the library carries (the AMDGPU
-metadata notes hipcc writes: .vgpr_count, .agpr_count, .vgpr_spill_count, .private_segment_fixed_size, LDS).  Library for
+metadata notes hipcc writes: .vgpr_count, .agpr_count, .vgpr_spill_count, .private_segment_fixed_size, LDS, the launch bound).  Library for
 tests/test_isa_resources_cpu.py (no shipped hot-loop instance may spill) and a CLI:  python tools/kernel_resources.py [substring]"""
 import os
 import re
@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "flexam_amd", "libflexam_hip.so")
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 FIELDS = ("agpr_count", "vgpr_count", "sgpr_count", "vgpr_spill_count", "sgpr_spill_count", "private_segment_fixed_size",
-          "group_segment_fixed_size")
+          "group_segment_fixed_size", "max_flat_workgroup_size")
 
 
 def demangle(names):
