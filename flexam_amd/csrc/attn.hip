@@ -57,7 +57,10 @@ struct AttnParams {
   // partial: write un-normalised O and (reference, row sum) to workspace slot slot0 + split even with one key range (the keys of
   // this call are only PART of the softmax: local-chunk-first attention under a sequence-parallel K|V all-gather);
   // n_slots: slots the merge kernel adds up
-  int partial, slot0, n_slots;
+  // (the attn_window_at_kernel instances, whole units that no merge follows, read n_slots as win_q0: the global token of the call's row 0
+  //  (flexam_attn_fwd_window_at).  The struct, and with it the kernarg loads of every other instance, stay as they are)
+  int partial, slot0;
+  union { int n_slots; int win_q0; };
   float last_key_bias;  // added to the score of key Lk - 1 in exp2 units (log2 of its multiplicity), 0 = none: see flexam_attn_fwd_lastkey
   // MXFP8 operands (attn_fp8.inc; q8 != nullptr selects that kernel): written by flexam_attn_fp8_pack
   const unsigned char* q8;   // [B][H][lq_pad][128] e4m3
@@ -296,7 +299,13 @@ __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (
 // last tile only.
 // (The one-block step of FULL for runs of interior tiles, next to the general step for the edges, was built and not kept: two step
 //  bodies in one loop cost hipcc 70 (scale in kernel) to 330 (PRE) spilled VGPRs, and a loop for each does not fit the instruction cache.)
-template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN, bool FRAMES = false>
+// AT (attn_window_at_kernel; flexam_attn_fwd_window_at, FRAMES with a token window as frames of one token): row i of the call is the global
+// token win_q0 + i, its bounds are those of that token, and Lq and Lk are two lengths: a rank's chunk of queries against the gathered
+// keys, pad rows (global tokens from Lk on) included.  The bounds stay non-decreasing in the row, so the walk, the interior test and the
+// per-lane mask are the ones above on global rows.  New: a unit whose rows see no key at all (pad rows, no sink) walks no tile -- it
+// reads no key and writes zeros --, and a row that sees no key in a unit that walks some ends with l = 0 and its reference never set
+// (the guards above keep its O at 0): it is written as zeros, not as 0 * inf.
+template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN, bool FRAMES = false, bool AT = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p by value, as attn8_fwd_body takes it and for its reason)
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [4 K tiles][4 V tiles], each a ring
   const int tid = threadIdx.x;
@@ -353,7 +362,8 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   if constexpr (WIN) {
     int qb = unit % p.q_blocks;
     if (p.win_left < 0) qb = p.q_blocks - 1 - qb;
-    const int qa = qb * QBLK, qz = min(qa + QBLK, p.Lq) - 1;      // first and last row of the unit
+    const int g0 = AT ? p.win_q0 : 0;                             // (AT: rows as global tokens)
+    const int qa = g0 + qb * QBLK, qz = g0 + min(qb * QBLK + QBLK, p.Lq) - 1;      // first and last row of the unit
     // the key ranges [lo, hi] of the first (_a) and the last (_z) row before clipping (an unbounded side's are not used): in tokens, or
     // FRAMES in whole frames of win_frame = T tokens counted from token 0 (fa, fz: the two rows' frames).  Non-decreasing in the row
     // either way
@@ -367,6 +377,9 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
     s_full = p.win_sink / KVBLK;
     gap = max(0, k_first / KVBLK - s_n);
     w_n = max(k_last / KVBLK, s_n - 1) + 1 - gap;
+    // AT: the window of every row of the unit may lie behind the last key (pad rows): the sink tiles alone, or no tile at all.  (The
+    // interior test below is empty by itself then: lo_z lies behind every whole tile)
+    if constexpr (AT) if (k_first > k_last) { gap = 0; w_n = s_n; }
     const int lo_z = FRAMES ? (fz - p.win_left) * p.win_frame : qz - p.win_left;
     ti_lo = p.win_left < 0 ? 0 : (max(0, lo_z) + KVBLK - 1) / KVBLK;      // its first key is the last row's first or later
     const int hi_a = FRAMES ? (fa + p.win_right + 1) * p.win_frame - 1 : qa + p.win_right;
@@ -435,6 +448,17 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   // ---- Q fragment (B operand of S^T = K.Q^T): lane (r, h) holds Q[q0 + r][16*ds + 8h .. +7]
   const int q0 = qbi * QBLK + wave * 32;
   const int qrow = min(q0 + r, p.Lq - 1);
+  if constexpr (AT) {
+    if (ntiles == 0) {                       // no row of the unit sees a key: zeros, and no key tile read (uniform over the workgroup)
+      f32x16 z[4];
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) z[dt][e] = 0.f;
+      store_output(p, z, 0.f, b, head, q0 + r, h);
+      return;
+    }
+  }
   bf16x8 qf[8];
 #pragma unroll
   for (int ds = 0; ds < 8; ++ds) qf[ds] = *(const bf16x8*)(qbase + (int64_t)qrow * p.q_rs + ds * 16 + h * 8);
@@ -505,10 +529,11 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   // (the three bounds less `base` are kept per lane: as uniform values next to s_n, gap and s_full they cost the loop 40 SGPR lane reloads)
   // FRAMES: the range is that of the row's frame, [(f - left) T, (f + right + 1) T - 1] with f = row / T: one division
   // per row here, nothing in the tile loop.
-  const int w_row = q0 + r - 4 * h;
+  const int w_g = (AT ? p.win_q0 : 0) + q0 + r;      // the lane's row (AT: as a global token)
+  const int w_row = w_g - 4 * h;
   int w_lo = w_row - (p.win_left < 0 ? (1 << 30) : p.win_left), w_hi = w_row + (p.win_right < 0 ? (1 << 30) : p.win_right);
   if constexpr (FRAMES) {
-    const int w_f = (int)((unsigned)(q0 + r) / (unsigned)p.win_frame);
+    const int w_f = (int)((unsigned)w_g / (unsigned)p.win_frame);
     if (p.win_left >= 0) w_lo = (w_f - p.win_left) * p.win_frame - 4 * h;
     if (p.win_right >= 0) w_hi = (w_f + p.win_right + 1) * p.win_frame - 1 - 4 * h;
   }
@@ -771,7 +796,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
     store_partial<false>(p, o_acc, 1.0f, PRE ? ref : m_run, l_tot, split, ul, wave, r, h, q0 + r);      // PRE: reference in exp2 units
     return;
   }
-  store_output(p, o_acc, 1.0f / l_tot, b, head, q0 + r, h);
+  store_output(p, o_acc, AT && !(l_tot > 0.f) ? 0.f : 1.0f / l_tot, b, head, q0 + r, h);      // (AT: a row that saw no key is zeros)
   }   // q blocks of this workgroup
 }
 template <int KIND, bool PRE, bool FULL = false, bool SHORT = false>
@@ -843,17 +868,23 @@ struct AttnCall {
   int win_sink = 0;                            // flexam_attn_fwd_window_sink: see AttnParams::win_sink
   bool win_by_frames = false;                  // flexam_attn_fwd_window_frames: win_left / win_right count frames of win_frame tokens
   int win_frame = 0;                           // see AttnParams::win_frame; read under win_by_frames only
+  // flexam_attn_fwd_window_at: row i is global token win_q0 + i, Lq and Lk two lengths.  Its entry point has normalised the window (the
+  // sides and the sink as the kernel takes them, win_frame >= 1 with a token window as frames of one token): attn_run takes them as they are
+  bool win_at = false;
+  int win_q0 = 0;
 };
 // The twelve instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
 struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
-constexpr int ATTN_INSTANCES = 12;
+constexpr int ATTN_INSTANCES = 14;
 // the two windowed MXFP8 kernels take their mask as a second argument; defined at the end of this file, as the two below
 struct Attn8WindowInstance { void (*kern)(AttnParams, Attn8Window); int slot; };      // slot in win_attr_set (attn_run)
 Attn8WindowInstance attn8_window_instance(bool oshift);
 // the two attn_window_frames_kernel instances (slots 10 and 11).  Defined at the end of this file, so that they are emitted behind every
 // other kernel of it: a listing of this file then differs from one without them by the two kernels alone (tools/isa_diff.py)
 AttnInstance attn_frames_instance(bool prescaled);
+// ... and, behind those, the two attn_window_at_kernel instances (slots 12 and 13), for the same reason
+AttnInstance attn_at_instance(bool prescaled);
 AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx, bool window, bool frames) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES, F8 = NSLOT * REC_BYTES;
   static const AttnInstance table[10] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
@@ -907,12 +938,15 @@ int attn_run(const AttnCall& c) {
   // (in frames: the last frame is ceil(Lk / T) - 1, and frame_tokens >= Lk is one frame that holds every key)
   FX_REQUIRE(!c.win_by_frames || c.win_frame > 0, FLEXAM_E_ARG, "attn_fwd: frame_tokens %d (1 or more)", c.win_frame);
   const int win_reach = c.win_by_frames ? (int)(((int64_t)c.Lk + c.win_frame - 1) / c.win_frame) - 1 : c.Lk - 1;
-  const int win_left = c.win_left < 0 || c.win_left >= win_reach ? -1 : c.win_left, win_right = c.win_right < 0 || c.win_right >= win_reach ? -1 : c.win_right;
+  // (win_at: the sides as flexam_attn_fwd_window_at normalised them for the rows of ITS call, which are not rows 0 .. Lk - 1)
+  const int win_left = c.win_left < 0 || (!c.win_at && c.win_left >= win_reach) ? -1 : c.win_left;
+  const int win_right = c.win_right < 0 || (!c.win_at && c.win_right >= win_reach) ? -1 : c.win_right;
   FX_REQUIRE(c.win_sink >= 0, FLEXAM_E_ARG, "attn_fwd: negative sink %d", c.win_sink);
   // a sink that holds every key leaves no mask; one under a window without a left bound (nothing lies to the left of it) adds no key
   const bool window = (win_left >= 0 || win_right >= 0) && c.win_sink < c.Lk;
   const int win_sink = win_left < 0 ? 0 : c.win_sink;
-  FX_REQUIRE(!window || (c.Lq == c.Lk && c.kv8_chunk_tiles == 0 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
+  FX_REQUIRE(!c.win_at || (window && !c.q8 && c.win_by_frames && c.win_q0 >= 0), FLEXAM_E_ARG, "attn_fwd: a window at an offset is a bf16 call under a mask");
+  FX_REQUIRE(!window || ((c.Lq == c.Lk || c.win_at) && c.kv8_chunk_tiles == 0 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
              "attn_fwd: a window goes with operands of one length (MXFP8: one chunk) and whole work units");
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
@@ -920,6 +954,7 @@ int attn_run(const AttnCall& c) {
   //  the instances that do not read it)
   const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
   if (window && !fp8) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; if (c.win_by_frames) p.win_frame = c.win_frame; }
+  if (c.win_at) p.win_q0 = c.win_q0;       // (in the word of n_slots, which only a merge reads: see AttnParams)
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
   if (window && fp8) {
@@ -942,7 +977,8 @@ int attn_run(const AttnCall& c) {
   }
   const bool short_ctx = !window && !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
   const bool full = !window && !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
-  const AttnInstance inst = attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window, window && c.win_by_frames);
+  const AttnInstance inst = c.win_at ? attn_at_instance(p.prescaled)
+                                     : attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window, window && c.win_by_frames);
   static bool attr_set[FLEXAM_MAX_DEVICES][ATTN_INSTANCES] = {};      // per device and kernel instance
   bool& lds_raised = attr_set[flexam_current_device()][inst.slot];
   if (!lds_raised) {
@@ -1022,6 +1058,40 @@ extern "C" int flexam_attn_fwd_window_frames(const void* q, int64_t q_bs, int64_
   c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
   c.B = B; c.H = H; c.Lq = L; c.Lk = L; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
   c.win_left = frames_left; c.win_right = frames_right; c.win_sink = sink; c.win_by_frames = true; c.win_frame = frame_tokens;
+  return attn_run(c);
+}
+
+extern "C" int flexam_attn_fwd_window_at(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
+                                         const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
+                                         int Lq, int Lk, int head_dim, float softmax_scale, int window_left, int window_right,
+                                         int frame_tokens, int sink, int q_offset, void* stream) {
+  FX_REQUIRE(q_offset >= 0, FLEXAM_E_ARG, "attn_fwd_window_at: negative q_offset %d", q_offset);
+  FX_REQUIRE(sink >= 0, FLEXAM_E_ARG, "attn_fwd: negative sink %d", sink);
+  FX_REQUIRE(frame_tokens >= 0, FLEXAM_E_ARG, "attn_fwd_window_at: frame_tokens %d (0 = a token window)", frame_tokens);
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  if (q_offset == 0 && Lq == Lk) {         // one length from token 0: the entry point of the form asked for, launch for launch
+    c.win_left = window_left; c.win_right = window_right; c.win_sink = sink; c.win_by_frames = frame_tokens > 0; c.win_frame = frame_tokens;
+    return attn_run(c);
+  }
+  if (Lq <= 0 || Lk <= 0) return attn_run(c);      // (attn_run says what is wrong with it)
+  const int64_t rows = (int64_t)q_offset + Lq;     // the call's rows are the global tokens q_offset .. rows - 1
+  // (the kernel's bounds are 32-bit: at most (2 (rows + Lk) / T + 3) T)
+  FX_REQUIRE(rows + Lk < (1ll << 29), FLEXAM_E_SHAPE, "attn_fwd_window_at: q_offset %d + Lq %d + Lk %d tokens (below 2^29)", q_offset, Lq, Lk);
+  // a token window is a window of one-token frames: lo(g) = (g / T - left) T, hi(g) = (g / T + right + 1) T - 1 are g - left and g + right
+  // at T = 1.  A frame longer than every index of the call holds all of them; a side no shorter than the call's reach is that reach
+  const int64_t T = frame_tokens == 0 ? 1 : frame_tokens < rows + Lk ? frame_tokens : rows + Lk;
+  const int64_t reach = (rows + Lk) / T + 1;
+  const int left = window_left < 0 ? -1 : (int)(window_left < reach ? window_left : reach);
+  const int right = window_right < 0 ? -1 : (int)(window_right < reach ? window_right : reach);
+  // does a side clip a row of THIS call?  lo and hi are non-decreasing in the row: the left side clips iff it clips the last row (pad rows,
+  // whose window may lie behind every key, included), the right side iff it clips the first
+  const bool clip_left = left >= 0 && ((rows - 1) / T - left) * T > 0;
+  const bool clip_right = right >= 0 && (q_offset / T + right + 1) * T - 1 < Lk - 1;
+  if ((!clip_left && !clip_right) || sink >= Lk) return attn_run(c);      // every row sees every key: flexam_attn_fwd on (Lq, Lk)
+  c.win_at = true; c.win_q0 = q_offset; c.win_by_frames = true; c.win_frame = (int)T;
+  c.win_left = left; c.win_right = right; c.win_sink = sink;      // (attn_run drops the sink under left < 0, as for the sibling entry points)
   return attn_run(c);
 }
 
@@ -1238,5 +1308,15 @@ AttnInstance attn_frames_instance(bool prescaled) {      // (declared next to at
 Attn8WindowInstance attn8_window_instance(bool oshift) {      // (the windowed MXFP8 kernels, see attn_fp8.inc: why it stands here)
   if (oshift) return {attn8_window_oshift_kernel<0>, 1};
   return {attn8_window_kernel<0>, 0};
+}
+// The windowed kernel at a query offset (flexam_attn_fwd_window_at; AT in attn_fwd_body).  Two instances, not four: the frame form
+// serves a token window as frames of one token, so the bounds are derived one way and nothing branches on the form.  Defined here, behind
+// every other kernel of the file: the instances above are emitted as they were.
+template <bool PRE>
+__global__ __launch_bounds__(NT, 2) void attn_window_at_kernel(AttnParams p) { attn_fwd_body<0, PRE, false, false, true, true, true>(p); }
+AttnInstance attn_at_instance(bool prescaled) {
+  constexpr int BF = NSLOT * 2 * KV_TILE_BYTES;
+  if (prescaled) return {attn_window_at_kernel<true>, BF, 13};
+  return {attn_window_at_kernel<false>, BF, 12};
 }
 }  // namespace

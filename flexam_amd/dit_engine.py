@@ -26,7 +26,7 @@ from typing import List, Optional
 import torch
 
 from . import hip
-from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, sage_window_asked, smooth_k_asked, smooth_v_asked
+from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, sage_window_asked, smooth_k_asked, smooth_v_asked, sp_window_asked
 from .dit_sp import HeadAllToAll, KVGather, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
@@ -72,6 +72,7 @@ class DiTEngine:
     _smooth_k_warned = False
     _smooth_v_warned = False
     _sage_window_warned = False
+    _sp_window_overlap_warned = False
 
     def __init__(self, model):
         self.model = model
@@ -395,16 +396,32 @@ class DiTEngine:
         cd, env = self.cond, os.environ
         window = getattr(self, "window", (-1, -1))         # (tests/test_smooth_k_mode_cpu.py resolves modes on a bare namespace)
         frames = getattr(self, "window_frames", (-1, -1))
-        if (window != (-1, -1) or frames != (-1, -1)) and self.sp_size > 1:
+        windowed = window != (-1, -1) or frames != (-1, -1)
+        # FLEXAM_SP_WINDOW=1 (default 0): a windowed model under sequence parallelism runs the windowed kernel at each rank's query offset
+        # (flexam_attn_fwd_window_at; flexam_amd/dit_sp.py).  Without the switch:
+        sp_window = windowed and self.sp_size > 1
+        if sp_window and not sp_window_asked(env):
             raise NotImplementedError(f"flexam_amd: {'window_size' if frames == (-1, -1) else 'window_frames'} under sequence parallelism is not "
                                       "served: a rank's queries and the keys it gathers carry global token indices, which the windowed "
                                       "kernel does not take")
+        overlap = self.sp_overlap_level
+        if sp_window and self.fused and self.sp_mode == "allgather" and overlap >= 1:
+            # the overlapped K|V gather (local chunk first, partial softmaxes + merge) has no windowed form: the gather is waited for, piece
+            # by piece, and one windowed call per piece follows.  The mode says so (sp_overlap_level 0), and with it a launch plan's key
+            overlap = 0
+            if not DiTEngine._sp_window_overlap_warned:    # said once per process
+                DiTEngine._sp_window_overlap_warned = True
+                import warnings
+                warnings.warn("flexam_amd: FLEXAM_SP_OVERLAP is ignored with window_size / window_frames under the K|V all-gather: each "
+                              "piece of the gather is waited for and one windowed attention call follows", RuntimeWarning, stacklevel=3)
+        # (record_gather: the gathered MXFP8 records are read by flexam_attn_fwd_fp8_chunked, which has no mask -- under a window the
+        #  ranks gather bf16 K|V and pad to the ranks alone, whatever FLEXAM_SAGE_WINDOW says)
         m = resolve_mode(env, fused=self.fused, nl=self.nl, nh=self.nh, hd=self.hd, dim=self.dim, table_limit=self.table_limit, fp8=self.fp8,
                          sp=self.sp_size, rank=self.sp_rank,
-                         parallel=(self.sp_mode, self.sp_overlap_level, self.sp_pieces, self.sp_fused_qkv),
+                         parallel=(self.sp_mode, overlap, self.sp_pieces, self.sp_fused_qkv),
                          B=cd["B"], L=cd["L"], dens_same=cd.get("dens_same", False), bx=bx, R=R, rows_per_batch=rows_per_batch,
-                         only_row=only_row, rows_shared=rows_shared, teacache=teacache is not None)
-        if sage_asked(env) and not m.sage and not DiTEngine._sage_warned:          # said once per process
+                         only_row=only_row, rows_shared=rows_shared, teacache=teacache is not None, record_gather=not sp_window)
+        if sage_asked(env) and not m.sage and not sp_window and not DiTEngine._sage_warned:          # said once per process
             DiTEngine._sage_warned = True
             import warnings
             warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored " +
@@ -431,7 +448,9 @@ class DiTEngine:
                           RuntimeWarning, stacklevel=3)
         # FLEXAM_SAGE_WINDOW=1 (default 0): a windowed model under SAGE runs the windowed MXFP8 kernel (flexam_attn_fwd_fp8_window); the mode
         # keeps `sage` then, which tells a launch plan of it from one of the replacement below.  Without the switch:
-        if (window != (-1, -1) or frames != (-1, -1)) and m.sage and not sage_window_asked(env):      # the windowed bf16 kernel runs
+        # (under sequence parallelism, FLEXAM_SP_WINDOW=1: the same, and with the switch the all-to-all over heads alone keeps `sage` --
+        #  resolve_mode never asked for the record gather above, which is said here as well)
+        if windowed and ((m.sage and not sage_window_asked(env)) or (sp_window and self.fused and sage_asked(env) and not m.sage)):      # the windowed bf16 kernel runs
             m = m._replace(sage=False, sage_gather=False, sage_fused=False)
             self._smooth_k = self._smooth_v = False
             if not DiTEngine._sage_window_warned:          # said once per process
@@ -549,6 +568,16 @@ class DiTEngine:
             return frames, 0
         from .wan_transformer3d_FlexAM import frame_tokens
         return frames, frame_tokens(self.cond["grid"], self.cond["L"])
+
+    def _window_mask(self):
+        """None without a window, else (window, sink, frame_tokens) as hip.attn_fwd_window takes them: the token window with frame_tokens
+        0, or the frame window with the tokens of one frame of this clip's grid (whole frames of the REAL length, never of a chunk)."""
+        if self.window != (-1, -1):
+            return self.window, self.window_sink, 0
+        if self.window_frames != (-1, -1):
+            frames, T = self._window_frames()
+            return frames, self.window_sink, T
+        return None
 
     def _record_or_replay(self, m, ws, e0, dens0):
         """The blocks and the head through a launch plan: they issue the same ~420 launches on the same buffers every step (only buffer

@@ -110,8 +110,16 @@ def sage_window_asked(env) -> bool:
     return env.get("FLEXAM_SAGE_WINDOW", "0") == "1"
 
 
+def sp_window_asked(env) -> bool:
+    """FLEXAM_SP_WINDOW=1 (default 0): a windowed self-attention (window_size / window_frames, with window_sink) under sequence
+    parallelism runs the windowed bf16 kernel at each rank's query offset (flexam_attn_fwd_window_at) instead of being refused: one call
+    per head-group piece of the K|V gather on the gathered keys, or on the rank's heads behind the all-to-all.  Not a field of _Mode:
+    without it DiTEngine._mode and _SelfAttn.forward raise before any mode exists."""
+    return env.get("FLEXAM_SP_WINDOW", "0") == "1"
+
+
 def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, parallel: Parallel, B, L, dens_same,
-                 bx, R, rows_per_batch, only_row, rows_shared, teacache: bool) -> _Mode:
+                 bx, R, rows_per_batch, only_row, rows_shared, teacache: bool, record_gather: bool = True) -> _Mode:
     """The mode of one forward.  env: the environment mapping; fused .. parallel: the engine (all blocks native, layers, heads, head
     width, model width, byte limit of the all-layer AdaLN table, enable_fp8, ranks, this rank, set_parallel's resolution); B, L,
     dens_same: the clip (samples, real tokens, all samples carry one density); the rest: the call (samples of the latent, table rows,
@@ -121,7 +129,9 @@ def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, par
     # VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION under the K|V gather (one gather, waited for): the ranks exchange their MXFP8 key / value
     # RECORDS (one per 64 keys) instead of bf16 rows, so every chunk is a whole number of 64-key tiles: the padding unit is 64 x ranks
     asked = sage_asked(env)
-    sage_gather = asked and fused and sp > 1 and sp_mode == "allgather" and overlap == 0 and pieces == 1
+    # (record_gather = False: the caller cannot use the gathered records -- a windowed model, whose mask flexam_attn_fwd_fp8_chunked does
+    #  not take -- and the bf16 K|V gather runs, padded to the ranks alone)
+    sage_gather = asked and fused and sp > 1 and sp_mode == "allgather" and overlap == 0 and pieces == 1 and record_gather
     Lp, lc, tok0 = token_layout(L, sp, rank, sp * hip.ATTN_KV_TILE if sage_gather else sp)
     # quantised self-attention on one rank: MXFP8 operands of the rank's tokens.  Sequence parallel with the all-to-all over heads:
     # every rank ends up with ALL tokens of its heads in bf16, packs them and runs the MXFP8 kernel on them.  K|V all-gather in its

@@ -67,10 +67,17 @@ class HeadAllToAll:
         nk = eng.cond["L"]                    # keys: the real tokens (rows nk .. sp*lc - 1 are the reference's zero pads, FX.py:919-925)
         full, out = self.full, self.out
         q_, k_, v_ = full[b0:b0 + nb, :, 0], full[b0:b0 + nb, :nk, 1], full[b0:b0 + nb, :nk, 2]
+        # a windowed model (FLEXAM_SP_WINDOW=1, DiTEngine._mode): the rank holds every padded row of its heads from token 0 on, so the
+        # mask sits at offset 0 -- with Lq = sp * lc >= Lk = nk rows, the pad rows behind the keys.  SAGE (FLEXAM_SAGE_WINDOW=1; asked for
+        # on an unpadded sequence only): the windowed MXFP8 launch, one length
+        mask = eng._window_mask()
         if m.sage:
             bufs = eng._attn8_buffers(nb, m.sp * m.lc, eng.nh // m.sp)
             hip.attn_fp8_pack(q_, k_, v_, bufs)
-            hip.attn_fwd_fp8(bufs, m.sp * m.lc, out=out[b0:b0 + nb])
+            kw = {} if mask is None else dict(window=mask[0], sink=mask[1], frame_tokens=mask[2])
+            hip.attn_fwd_fp8(bufs, m.sp * m.lc, out=out[b0:b0 + nb], **kw)
+        elif mask is not None:
+            hip.attn_fwd_window(q_, k_, v_, mask[0], out=out[b0:b0 + nb], prescaled=True, sink=mask[1], frame_tokens=mask[2], q_offset=0)
         else:
             hip.attn_fwd(q_, k_, v_, out=out[b0:b0 + nb], prescaled=True)
 
@@ -165,13 +172,22 @@ class KVGather:
         hip.rmsnorm_rope(qkv[:, 0:d], p["nq"], eps=eng.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=lc, token_offset=tok0,
                          head_dim=hd)
         heads = lambda t: t.unflatten(2, (hg, hd))
+        # a windowed model (FLEXAM_SP_WINDOW=1): the local queries are the global tokens tok0 .. tok0 + lc - 1, the gathered rows the keys
+        # 0 .. Lr - 1: one windowed call per piece at that offset, once the piece has landed (DiTEngine._mode resolves the overlap level to
+        # 0 under a window: the local-chunk-first form below has no mask)
+        mask = eng._window_mask()
         for g in range(m.sp_pieces):
             qg, og = q4[:, :, g * hg:(g + 1) * hg], ao4[:, :, g * hg:(g + 1) * hg]
             kc, vc = cat[g, :, :, 0:cb], cat[g, :, :, cb:]
             if g > 0 or m.sp_overlap_level == 0:
                 hip.host_op(lambda g=g: self._wait(g))
-                hip.attn_fwd(qg, heads(kc[:, :Lr]), heads(vc[:, :Lr]), out=og, prescaled=True)
+                if mask is not None:
+                    hip.attn_fwd_window(qg, heads(kc[:, :Lr]), heads(vc[:, :Lr]), mask[0], out=og, prescaled=True, sink=mask[1],
+                                        frame_tokens=mask[2], q_offset=tok0)
+                else:
+                    hip.attn_fwd(qg, heads(kc[:, :Lr]), heads(vc[:, :Lr]), out=og, prescaled=True)
                 continue
+            assert mask is None, "a window under the overlapped K|V gather is not served"
             if Lr != self.sizes_of:                    # another clip under the same chunk size: its own key ranges
                 self.sizes, self.sizes_of = key_range_sizes(Lr, m.sp, m.rank), Lr
             (n_loc, n_before, n_after), (s_loc, s_before, s_after) = self.sizes, self.splits

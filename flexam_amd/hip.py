@@ -602,13 +602,58 @@ def attn_window_frames_tiles(L: int, window_frames, frame_tokens: int, sink: int
     return out
 
 
-def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0, frame_tokens=0):
+def attn_window_at_tiles(Lq: int, Lk: int, q_offset: int, window, sink: int = 0, frame_tokens: int = 0):
+    """The three planners above for a call at a query offset (flexam_attn_fwd_window_at): row i of Lq is global token g = q_offset + i
+    and sees key j of Lk iff j < sink or lo(g) <= j <= hi(g), the bounds in tokens (frame_tokens = 0) or in frames of T = frame_tokens
+    tokens, a negative side unbounded (and a negative left side drops the sink, as everywhere).  Per block of ATTN_Q_BLOCK query rows the
+    list of (first, last) key-tile runs the kernel walks; [] for a block none of whose rows sees a key (pad rows behind the keys: the
+    kernel reads no tile and writes zeros).  Both bounds are non-decreasing in g, so a block's window keys run from its first row's first
+    key to its last row's last.  At q_offset = 0, Lq = Lk it is the planner of the form asked for (but for a sink under a token window
+    without a left bound, which attn_window_sink_tiles keeps and every entry point drops: this follows the entry points).  GPU-free."""
+    a, b = attn_window(window)
+    Lq, Lk, q0, sink, T = int(Lq), int(Lk), int(q_offset), int(sink), int(frame_tokens)
+    if q0 < 0 or sink < 0 or T < 0:
+        raise ValueError(f"attn_window_at_tiles: q_offset {q0}, sink {sink}, frame_tokens {T} (none may be negative)")
+    T = max(T, 1)                                              # (a token window is a window of one-token frames)
+    n_sink = -(-min(sink, Lk) // ATTN_KV_TILE) if a >= 0 else 0
+    out = []
+    for r0 in range(0, Lq, ATTN_Q_BLOCK):
+        ga, gz = q0 + r0, q0 + min(r0 + ATTN_Q_BLOCK, Lq) - 1
+        first = 0 if a < 0 else max(0, (ga // T - a) * T)
+        last = Lk - 1 if b < 0 else min(Lk - 1, (gz // T + b + 1) * T - 1)
+        runs = [(0, n_sink - 1)] if n_sink else []
+        if first <= last:
+            first, last = first // ATTN_KV_TILE, last // ATTN_KV_TILE
+            if n_sink and n_sink >= first:
+                runs = [(0, max(last, n_sink - 1))]
+            else:
+                runs.append((first, last))
+        out.append(runs)
+    return out
+
+
+def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0, frame_tokens=0, q_offset=None):
     """attn_fwd under flash-attn's sliding-window mask (see flexam_hip.h): q, k, v [B, L, H, 128] bf16 with the layouts of attn_fwd and
     ONE length L; window = (left, right), a negative side unbounded, (-1, -1) the ordinary call.  Whole work units only (no split-KV).
     sink > 0: the first `sink` keys stay visible to every row whatever the window says (flexam_attn_fwd_window_sink); sink = 0 is the
     call this function has always made.  frame_tokens = T > 0: `window` = (a, b) counts frames of T tokens from token 0, row i sees the
-    frames i // T - a .. i // T + b whole (flexam_attn_fwd_window_frames); frame_tokens = 0 changes no call."""
+    frames i // T - a .. i // T + b whole (flexam_attn_fwd_window_frames); frame_tokens = 0 changes no call.
+    q_offset (None: the calls above, one length): the Lq rows of q are the global tokens q_offset .. q_offset + Lq - 1 of a sequence whose
+    first Lk tokens are the keys (flexam_attn_fwd_window_at: a rank's chunk under sequence parallelism; Lq != Lk is welcome, rows from Lk on
+    are pad rows, and a row that sees no key comes back as zeros)."""
     B, L, H, D = q.shape
+    if q_offset is not None and (int(q_offset) != 0 or k.shape[1] != L):
+        Lk = k.shape[1]
+        if v.shape[1] != Lk:
+            raise RuntimeError(f"attn_fwd_window: keys and values share one length (Lk = {Lk}, Lv = {v.shape[1]})")
+        _packed_heads("attn_fwd_window", q, k, v)
+        if out is None:
+            out = torch.empty(B, L, H, D, device=q.device, dtype=BF16)
+        left, right = attn_window(window)
+        _call("flexam_attn_fwd_window_at", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+              v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, Lk, D, _softmax_scale(softmax_scale, prescaled, D),
+              left, right, int(frame_tokens), int(sink), int(q_offset))
+        return out
     if k.shape[1] != L or v.shape[1] != L:
         raise RuntimeError(f"attn_fwd_window: queries and keys share one length (Lq = {L}, Lk = {k.shape[1]})")
     _packed_heads("attn_fwd_window", q, k, v)

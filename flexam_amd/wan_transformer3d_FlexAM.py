@@ -215,17 +215,18 @@ class _SelfAttn(_Attn):
         (angle table, or the reference's complex exp(i angle) table)."""
         from . import hip
         from .dist import current_sp_context
-        from .dit_layout import sage_window_asked, smooth_k_asked, smooth_v_asked
+        from .dit_layout import sage_window_asked, smooth_k_asked, smooth_v_asked, sp_window_asked
         b, l, c = x.shape
         nh, hd = self.num_heads, self.head_dim
         sp = current_sp_context()
         window, frames = hip.attn_window(self.window_size), hip.attn_window(self.window_frames)
         if sp is not None and sp["size"] > 1:
-            if window != (-1, -1) or frames != (-1, -1):
+            # FLEXAM_SP_WINDOW=1 (default 0): the windowed kernel at the chunk's global token offset (_forward_chunk)
+            if (window != (-1, -1) or frames != (-1, -1)) and not sp_window_asked(os.environ):
                 raise NotImplementedError(f"flexam_amd: {'window_size' if frames == (-1, -1) else 'window_frames'} under sequence parallelism is "
                                           "not served (a rank's queries are a chunk of the sequence: the window would have to follow their "
                                           "global indices)")
-            return self._forward_chunk(x, seq_lens, sp)
+            return self._forward_chunk(x, seq_lens, sp, grid_sizes)
         # A caller that hands over a PADDED sequence (FX.py:918-925: zero tokens behind seq_lens[b] real ones, the same count for every
         # sample) gets flash-attention's semantics: the pads are no keys (k_lens, FX.py:251-256 -> ATT.py:87-95); their own rows are
         # computed like any other and are the caller's to drop.  The model's own forward never pads (it does not create the tokens).
@@ -274,7 +275,7 @@ class _SelfAttn(_Attn):
         return hip.gemm(ao.view(b * l, c), pk["wo"], pk["bo"]).view(b, l, c)
 
 
-    def _forward_chunk(self, x, seq_lens, sp):
+    def _forward_chunk(self, x, seq_lens, sp, grid_sizes=None):
         """Sequence-parallel form of forward() for blocks that are called as modules (the reference's `usp_attn_forward`, re-bound at
         wan_transformer3d_FlexAM.py:807-815): x is this rank's token chunk [B, L/N, C]; q|k|v of the chunk, RMSNorm + RoPE at the
         chunk's GLOBAL token offset, ONE all-gather of the normed / rotated K|V over the sequence-parallel group (RCCL over xGMI; the
@@ -290,6 +291,14 @@ class _SelfAttn(_Attn):
         if not (L <= Lp < L + sp["size"]) or (seq_lens is not None and any(int(v) != L for v in (seq_lens.tolist() if torch.is_tensor(seq_lens) else seq_lens))):
             raise NotImplementedError(f"flexam_amd: a sequence-parallel chunk of {lc} tokens x {sp['size']} ranks is not the padded form of seq_lens / L = {L} "
                                       "(ceil(L / ranks) * ranks rows, FX.py:919-920)")
+        # a window (FLEXAM_SP_WINDOW=1, forward() refuses it otherwise): the chunk's rows are the global tokens token_offset .. and the
+        # gathered rows the keys 0 .. L - 1; a frame is a frame of the grid and the REAL length is whole frames, whatever the chunk holds
+        window, frames = hip.attn_window(self.window_size), hip.attn_window(self.window_frames)
+        mask = None
+        if window != (-1, -1):
+            mask = dict(window=window, sink=self.window_sink)
+        elif frames != (-1, -1):
+            mask = dict(window=frames, sink=self.window_sink, frame_tokens=frame_tokens(grid_sizes, L))
         pk = self.packed()
         h = x.reshape(b * lc, c).to(BF16).contiguous()
         qkv = _proj_fp8(h, pk, "wqkv", pk["bqkv"]) if self._fp8 else hip.gemm(h, pk["wqkv"], pk["bqkv"])
@@ -297,8 +306,12 @@ class _SelfAttn(_Attn):
                          tokens_per_batch=lc, token_offset=sp["token_offset"], head_dim=hd)
         q3 = qkv.view(b, lc, 3 * c)
         kv = all_gather_seq(q3[:, :, c:].contiguous(), sp["group"])                  # [B, Lp, 2C]; rows L .. Lp - 1 are the zero pad tokens:
-        ao = hip.attn_fwd(q3[:, :, 0:c].unflatten(2, (nh, hd)), kv[:, :L, 0:c].unflatten(2, (nh, hd)), kv[:, :L, c:].unflatten(2, (nh, hd)),   # no keys (k_lens, FX.py:251-256)
-                          prescaled=True)
+        q4, k4, v4 = q3[:, :, 0:c].unflatten(2, (nh, hd)), kv[:, :L, 0:c].unflatten(2, (nh, hd)), kv[:, :L, c:].unflatten(2, (nh, hd))      # no keys (k_lens, FX.py:251-256)
+        if mask is not None:
+            win = mask.pop("window")
+            ao = hip.attn_fwd_window(q4, k4, v4, win, prescaled=True, q_offset=sp["token_offset"], **mask)
+        else:
+            ao = hip.attn_fwd(q4, k4, v4, prescaled=True)
         return hip.gemm(ao.view(b * lc, c), pk["wo"], pk["bo"]).view(b, lc, c)
 
 

@@ -173,6 +173,22 @@ int flexam_attn_fwd_window_sink(const void* q, int64_t q_bs, int64_t q_rs, const
 int flexam_attn_fwd_window_frames(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
                                   int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L, int head_dim,
                                   float softmax_scale, int frames_left, int frames_right, int frame_tokens, int sink, void* stream);
+/* The three masks above for a call whose Lq queries are the global tokens q_offset .. q_offset + Lq - 1 of a sequence whose first Lk
+ * tokens are the keys: what a rank runs under sequence parallelism (its chunk of queries against the gathered keys, q_offset = the
+ * chunk's first token; or every padded row of its heads at q_offset = 0 with Lq >= Lk).  Row i is global token g = q_offset + i and sees
+ * key j (0 <= j < Lk) iff j < sink or lo(g) <= j <= hi(g): frame_tokens = 0, a token window, lo = g - window_left and hi = g +
+ * window_right; frame_tokens = T > 0, the two words count frames, lo = (g / T - window_left) T and hi = (g / T + window_right + 1) T - 1.
+ * A negative side is unbounded.  q_offset + Lq may exceed Lk: those rows are the zero pad rows of a sequence that does not divide over
+ * the ranks; they are never keys, as queries they follow the same rule, and a row that sees no key is written as zeros.  A work unit
+ * visits the sink tiles and the tiles that hold a key one of its 256 rows sees, as one run or two, interior tiles unmasked, as the
+ * sibling kernels do; a unit none of whose rows sees a key reads no key tile and writes zeros.  Whole units only (no split-KV).  The
+ * kernels are instances of their own (attn_window_at_kernel).  Normalisations, each the very launch named: q_offset = 0 and Lq = Lk is
+ * flexam_attn_fwd_window, _window_sink or _window_frames; a window that clips no row of this call on either side, or sink >= Lk, is
+ * flexam_attn_fwd on (Lq, Lk); window_left < 0 drops the sink.  q_offset < 0, sink < 0 and frame_tokens < 0 are FLEXAM_E_ARG. */
+int flexam_attn_fwd_window_at(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                              int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int Lk, int head_dim,
+                              float softmax_scale, int window_left, int window_right, int frame_tokens, int sink, int q_offset,
+                              void* stream);
 /* flexam_attn_fwd with the work units u =(batch*H + head)*ceil(Lq/256) + q_block at and after `split_from_unit` cut into kv_splits key
  * ranges each (flash-decoding style partial softmaxes + a merge launch), the units before it in one pass: with
  * split_from_unit = floor(units/256)*256 only the last, partial round of the 256 CUs is split; 0 splits everything (ranks of a

@@ -32,7 +32,15 @@ arm: the time, its share of the full MXFP8 launch, the share of tiles visited, a
 taken in the same call (the two alternate inside every round), `mxfp8_over_bf16` their ratio.  With --base the unwindowed MXFP8
 launch and the full bf16 launch of the in-tree library are timed against that build as above (base, in-tree, base).  No condition.
 
+--rank-of=N (N = 8): the windows at a rank's shape under sequence parallelism (FLEXAM_SP_WINDOW=1's launch, hip.attn_fwd_window(...,
+q_offset=)) -> profiles/attn_window_sp_bench.json.  Lk = 11648 keys, Lq = ceil(11648 / N) queries at the offsets of ranks 0, N / 2 and
+N - 1; per rank the unmasked launch a rank runs today (hip.attn_fwd on (Lq, Lk), tail split and merge included) and the masks --sage
+walks (token and frame windows of +-2 / +-5 / +-12 frames, frame-block-causal, per-frame, sink 0 and 448), alternating inside every
+round.  Per arm: the time, its share of the rank's unmasked launch, the share of (query block, key tile) pairs visited
+(hip.attn_window_at_tiles), and the number of work units.  No condition.
+
 usage: attn_window_bench.py [--iters=10] [--rounds=7] [--out=profiles/attn_window_bench.json]
+       attn_window_bench.py --rank-of=8 [--out=profiles/attn_window_sp_bench.json]
        attn_window_bench.py --sage [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sage_bench.json]
        attn_window_bench.py --sink=0,448,896 [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sink_bench.json]
        attn_window_bench.py --frames[=2,5,12] [--sink=0,448] [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_frames_bench.json]"""
@@ -180,8 +188,58 @@ def sage_bench():
     print("wrote", path)
 
 
+def rank_bench(N):
+    """--rank-of=N: see the module docstring."""
+    Lq, n_tiles = -(-L // N), H.attn_kv_tiles(L)
+    q_pad = torch.zeros(B, N * Lq, heads, D, dtype=torch.bfloat16, device="cuda")       # the sequence padded over the ranks, zero pad rows
+    q_pad[:, :L] = q
+    out = torch.empty(B, Lq, heads, D, dtype=torch.bfloat16, device="cuda")
+    masks = [(f"tokens_{n}_{n}_sink_{s}", (FRAME * n, FRAME * n), s, 0) for n in (2, 5, 12) for s in (0, FRAME)]
+    masks += [(f"{name}_sink_{s}", w, s, FRAME) for name, w in [(f"frames_{n}_{n}", (n, n)) for n in (2, 5, 12)] +
+              [("frames_block_causal", (-1, 0)), ("frames_per_frame", (0, 0))] for s in (0, FRAME)]
+    units = H.attn_units(B * heads, Lq)
+    rec = dict(shape=dict(B=B, H=heads, Lk=L, Lq=Lq, ranks=N, head_dim=D, frame_tokens=FRAME, prescaled=True), work_units=units, iters=iters, rounds=rounds,
+               device=torch.cuda.get_device_name(0),
+               method="one process, per rank the unmasked launch (hip.attn_fwd on (Lq, Lk): the launch a rank runs today, tail split and merge "
+                      "included) and every windowed launch at the rank's offset (hip.attn_fwd_window(..., q_offset=)) alternating per round, device "
+                      "events around `iters` back-to-back launches, median over the rounds; time_ratio: of the unmasked launch of the same rank; "
+                      "tile_share: hip.attn_window_at_tiles over (query blocks x key tiles)", ranks={})
+    for rank in sorted({0, N // 2, N - 1}):
+        off = rank * Lq
+        qr = q_pad[:, off:off + Lq]
+        calls = {"full": lambda: H.attn_fwd(qr, k, v, out=out, prescaled=True)}
+        for name, w, s, ft in masks:
+            calls[name] = lambda w=w, s=s, ft=ft: H.attn_fwd_window(qr, k, v, w, out=out, prescaled=True, sink=s, frame_tokens=ft, q_offset=off)
+        for fn in calls.values():                      # warm-up: every instance once
+            fn()
+        torch.cuda.synchronize()
+        ms = {name: [] for name in calls}
+        for _ in range(rounds):
+            for name, fn in calls.items():
+                ms[name].append(timed_call(fn))
+        med = {name: statistics.median(x) for name, x in ms.items()}
+        arms = dict(full=dict(ms=round(med["full"], 4), ms_min=round(min(ms["full"]), 4), ms_max=round(max(ms["full"]), 4)))
+        print(f"rank {rank} of {N} (rows {off} .. {off + Lq - 1}), {units} work units: unmasked {med['full']:.3f} ms")
+        for name, w, s, ft in masks:
+            runs = H.attn_window_at_tiles(Lq, L, off, w, s, ft)
+            sh = sum(b - a + 1 for r in runs for a, b in r) / (len(runs) * n_tiles)
+            t = med[name]
+            arms[name] = dict(window=list(w), sink=s, frame_tokens=ft, ms=round(t, 4), ms_min=round(min(ms[name]), 4), ms_max=round(max(ms[name]), 4),
+                              tile_share=round(sh, 4), time_ratio=round(t / med["full"], 4), time_per_tile_ratio=round(t / med["full"] / sh, 3))
+            print(f"  {name:30s} {t:8.3f} ms  tiles {sh:6.4f}  time {t / med['full']:6.3f}  per tile {t / med['full'] / sh:5.2f}")
+        rec["ranks"][str(rank)] = dict(q_offset=off, arms=arms)
+    path = os.path.join(root, opt.get("out", "profiles/attn_window_sp_bench.json"))
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
+
+
 if "sage" in opt:
     sage_bench()
+    sys.exit(0)
+if "rank-of" in opt:
+    rank_bench(int(opt["rank-of"] or 8))
     sys.exit(0)
 
 for _, w, s, ft in ARMS:                           # warm-up: every instance once (LDS attribute, code load), then the clock
