@@ -18,6 +18,7 @@
 //  * softmax scale and log2(e) are folded into one FMA in front of v_exp_f32, or (PRE) into q by its producer.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 
 #include "common.h"
@@ -68,7 +69,10 @@ struct AttnParams {
   //  (flexam_attn_fwd_window_frames): win_left / win_right count frames of T tokens from token 0, see below.  attn_window_kernel, whose
   //  window counts tokens, does not read it: attn_run leaves it 0 there, the null qs)
   union { const unsigned* qs; int win_frame; };        // [B][H][lq_pad] four E8M0 bytes per row
-  const unsigned char* kv8;  // [B][H][ceil(Lk / 64)] records of REC_BYTES -- or, in chunks of kv8_chunk_tiles key tiles, [chunk][B][H][kv8_chunk_tiles]
+  // kv8: [B][H][ceil(Lk / 64)] records of REC_BYTES -- or, in chunks of kv8_chunk_tiles key tiles, [chunk][B][H][kv8_chunk_tiles]
+  // (attn_window_halo_kernel, which has no MXFP8 operands, reads the low word of this pointer as win_key_gap: the key tiles its compact
+  //  k / v leave out between the sink tiles and the window tiles (flexam_attn_fwd_window_halo).  No other instance reads the word so)
+  union { const unsigned char* kv8; int win_key_gap; };
   // (attn_window_kernel reads this word as its sink, the way it reads the two chunk words below as its window: the first win_sink keys
   //  are visible to EVERY row, whatever win_right says -- the model is not causal.  Row i sees key j iff j < win_sink or j is in its window)
   union { int lq_pad; int win_sink; };
@@ -305,7 +309,10 @@ __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (
 // per-lane mask are the ones above on global rows.  New: a unit whose rows see no key at all (pad rows, no sink) walks no tile -- it
 // reads no key and writes zeros --, and a row that sees no key in a unit that walks some ends with l = 0 and its reference never set
 // (the guards above keep its O at 0): it is written as zeros, not as 0 * inf.
-template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN, bool FRAMES = false, bool AT = false>
+// HALO (attn_window_halo_kernel; flexam_attn_fwd_window_halo, on top of AT): k and v are a compact buffer that holds the sink tiles and, behind
+// them, the key tiles from global tile s_n + win_key_gap on.  Every mask and bound stays in global indices; only the address of global
+// tile tg moves: buffer tile tg below s_n, tg - win_key_gap from there on (the entry point has checked every unit's tiles against it).
+template <int KIND, bool PRE, bool FULL, bool SHORT, bool WIN, bool FRAMES = false, bool AT = false, bool HALO = false>
 __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p by value, as attn8_fwd_body takes it and for its reason)
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [4 K tiles][4 V tiles], each a ring
   const int tid = threadIdx.x;
@@ -405,9 +412,10 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
   auto issue_tile = [&](int t, int parts = 3, int tslot = -1) {      // parts: 1 = K, 2 = V; tslot: ring position (default t)
     const unsigned slot = lds0 + (unsigned)(((tslot < 0 ? t : tslot) & (NSLOT - 1)) * KV_TILE_BYTES + wave * 1024);   // wave-uniform; K ring, V ring = + V_RING
     const int tg = global_tile(t);
+    const int skipped = HALO && tg >= s_n ? p.win_key_gap * KVBLK : 0;      // (HALO: key rows the buffer leaves out in front of this tile)
     if (FULL || (tg + 1) * KVBLK <= p.Lk) {
       // FULL: the last tile is the window [Lk - 64, Lk) (scalar select, no branch)
-      const unsigned row0 = FULL && tg == tiles_all - 1 ? (unsigned)(p.Lk - KVBLK) : (unsigned)tg * KVBLK;
+      const unsigned row0 = FULL && tg == tiles_all - 1 ? (unsigned)(p.Lk - KVBLK) : (unsigned)tg * KVBLK - (unsigned)skipped;
       const char* kt = kbase + (size_t)(row0 * (unsigned)(p.k_rs * 2));     // wave-uniform tile bases
       const char* vt = vbase + (size_t)(row0 * (unsigned)(p.v_rs * 2));
 #pragma unroll
@@ -420,7 +428,7 @@ __device__ __forceinline__ void attn_fwd_body(const AttnParams p) {      // (p b
       for (int i = 0; i < 2; ++i) {
         const int row = (tid + NT * i) >> 4;
         const int col = ((tid & 15) ^ (((row & 3) << 2) | ((row >> 2) & 3))) * 16;
-        const int key = min(tg * KVBLK + row, p.Lk - 1);
+        const int key = min(tg * KVBLK + row, p.Lk - 1) - skipped;
         if (parts & 1) lds_dma16(kbase + ((int64_t)key * p.k_rs * 2 + col), slot + i * 8192);
         if (parts & 2) lds_dma16(vbase + ((int64_t)key * p.v_rs * 2 + col), slot + V_RING + i * 8192);
       }
@@ -872,11 +880,15 @@ struct AttnCall {
   // sides and the sink as the kernel takes them, win_frame >= 1 with a token window as frames of one token): attn_run takes them as they are
   bool win_at = false;
   int win_q0 = 0;
+  // flexam_attn_fwd_window_halo (with win_at): k and v are a compact buffer of win_k_rows rows, the sink tiles and then the key tiles from
+  // global tile s_n + win_key_gap on.  attn_run walks the call's query blocks and refuses a buffer that a unit's tiles do not fit
+  bool win_halo = false;
+  int win_key_gap = 0, win_k_rows = 0;
 };
 // The twelve instances and the rule that picks one.  cross: separate symbols for the short-context (text) launches.  short_ctx: the text
 // cross-attention (at most 4 key tiles, pre-scaled q, one launch without key splits): K/V resident, several q blocks per workgroup.
 struct AttnInstance { void (*kern)(AttnParams); int smem, slot; };      // dynamic LDS: rings of 4 K and 4 V tiles, 128 KiB (fp8: 4 records, 68 KiB); slot in attr_set
-constexpr int ATTN_INSTANCES = 14;
+constexpr int ATTN_INSTANCES = 16;
 // the two windowed MXFP8 kernels take their mask as a second argument; defined at the end of this file, as the two below
 struct Attn8WindowInstance { void (*kern)(AttnParams, Attn8Window); int slot; };      // slot in win_attr_set (attn_run)
 Attn8WindowInstance attn8_window_instance(bool oshift);
@@ -885,6 +897,8 @@ Attn8WindowInstance attn8_window_instance(bool oshift);
 AttnInstance attn_frames_instance(bool prescaled);
 // ... and, behind those, the two attn_window_at_kernel instances (slots 12 and 13), for the same reason
 AttnInstance attn_at_instance(bool prescaled);
+// ... and, last, the two attn_window_halo_kernel instances (slots 14 and 15)
+AttnInstance attn_halo_instance(bool prescaled);
 AttnInstance attn_instance(bool fp8, bool oshift, bool cross, bool prescaled, bool full, bool short_ctx, bool window, bool frames) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES, F8 = NSLOT * REC_BYTES;
   static const AttnInstance table[10] = {{attn_fwd_kernel<0, false>, BF, 0}, {attn_fwd_kernel<1, false>, BF, 1}, {attn_fwd_kernel<0, true>, BF, 2},
@@ -955,6 +969,31 @@ int attn_run(const AttnCall& c) {
   const bool fp8 = c.q8 != nullptr, cross = c.Lk <= 1024;
   if (window && !fp8) { p.win_left = win_left; p.win_right = win_right; p.win_sink = win_sink; if (c.win_by_frames) p.win_frame = c.win_frame; }
   if (c.win_at) p.win_q0 = c.win_q0;       // (in the word of n_slots, which only a merge reads: see AttnParams)
+  if (c.win_halo) {
+    FX_REQUIRE(c.win_at && window, FLEXAM_E_ARG, "attn_fwd_window_halo: a call that sees every key reads all %d of them, not a compact buffer", c.Lk);
+    FX_REQUIRE(c.win_key_gap >= 0 && c.win_k_rows >= 0 && c.win_k_rows <= c.Lk, FLEXAM_E_ARG, "attn_fwd_window_halo: key_gap_tiles %d, k_rows %d (of %d keys)",
+               c.win_key_gap, c.win_k_rows, c.Lk);
+    // The tiles every query block visits, by the arithmetic of attn_fwd_body (WIN, FRAMES, AT) on the words the kernel will read: the sink
+    // tiles [0, s_n) and the window tiles [s_n + gap, w_n + gap).  A tile in the gap the buffer leaves out, or one whose last key row
+    // (cut at Lk) lies behind the buffer's last row, is a wrong plan: refused here, never read
+    const int T = p.win_frame, s_n = (std::min(p.win_sink, p.Lk) + KVBLK - 1) / KVBLK;
+    for (int qb = 0; qb < p.q_blocks; ++qb) {
+      const int qa = p.win_q0 + qb * QBLK, qz = p.win_q0 + std::min(qb * QBLK + QBLK, p.Lq) - 1;
+      const int fa = (int)((unsigned)qa / (unsigned)T), fz = (int)((unsigned)qz / (unsigned)T);
+      const int lo_a = (fa - p.win_left) * T, hi_z = (fz + p.win_right + 1) * T - 1;
+      const int k_first = p.win_left < 0 ? 0 : std::max(0, lo_a), k_last = p.win_right < 0 ? p.Lk - 1 : std::min(p.Lk - 1, hi_z);
+      int gap = std::max(0, k_first / KVBLK - s_n), w_n = std::max(k_last / KVBLK, s_n - 1) + 1 - gap;
+      if (k_first > k_last) { gap = 0; w_n = s_n; }
+      const int64_t sink_end = std::min<int64_t>((int64_t)s_n * KVBLK, p.Lk);                              // one behind the last key row read of each run
+      const int64_t win_end = std::min<int64_t>((int64_t)(w_n + gap) * KVBLK, p.Lk) - (int64_t)c.win_key_gap * KVBLK;
+      FX_REQUIRE(s_n == 0 || sink_end <= c.win_k_rows, FLEXAM_E_ARG, "attn_fwd_window_halo: query block %d reads the sink's %d key rows, the buffer holds %d",
+                 qb, (int)sink_end, c.win_k_rows);
+      FX_REQUIRE(w_n == s_n || (gap >= c.win_key_gap && win_end <= c.win_k_rows), FLEXAM_E_ARG,
+                 "attn_fwd_window_halo: query block %d reads key tiles %d .. %d; the buffer (key_gap_tiles %d, k_rows %d) holds tiles %d .. %d behind %d sink tiles",
+                 qb, s_n + gap, w_n + gap - 1, c.win_key_gap, c.win_k_rows, s_n + c.win_key_gap, (c.win_k_rows + KVBLK - 1) / KVBLK + c.win_key_gap - 1, s_n);
+    }
+    p.win_key_gap = c.win_key_gap;         // (in the low word of the null kv8: see AttnParams)
+  }
   FX_REQUIRE(c.q8 || (int64_t)c.Lk * c.k_rs * 2 < (1ll << 31) && (int64_t)c.Lk * c.v_rs * 2 < (1ll << 31), FLEXAM_E_SHAPE,
              "attn_fwd: one (batch, head) K/V panel must span < 2 GiB (32-bit tile offsets)");
   if (window && fp8) {
@@ -977,7 +1016,7 @@ int attn_run(const AttnCall& c) {
   }
   const bool short_ctx = !window && !fp8 && cross && p.prescaled && tiles_all <= NSLOT && c.kv_splits == 1 && c.partial_slot0 < 0 && attn_switch("FLEXAM_ATTN_SHORT");
   const bool full = !window && !fp8 && !cross && p.prescaled && c.Lk >= KVBLK && c.last_key_bias == 0.f && attn_switch("FLEXAM_ATTN_FULL");
-  const AttnInstance inst = c.win_at ? attn_at_instance(p.prescaled)
+  const AttnInstance inst = c.win_halo ? attn_halo_instance(p.prescaled) : c.win_at ? attn_at_instance(p.prescaled)
                                      : attn_instance(fp8, c.o_shift != nullptr, cross, p.prescaled, full, short_ctx, window, window && c.win_by_frames);
   static bool attr_set[FLEXAM_MAX_DEVICES][ATTN_INSTANCES] = {};      // per device and kernel instance
   bool& lds_raised = attr_set[flexam_current_device()][inst.slot];
@@ -1061,17 +1100,13 @@ extern "C" int flexam_attn_fwd_window_frames(const void* q, int64_t q_bs, int64_
   return attn_run(c);
 }
 
-extern "C" int flexam_attn_fwd_window_at(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
-                                         const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
-                                         int Lq, int Lk, int head_dim, float softmax_scale, int window_left, int window_right,
-                                         int frame_tokens, int sink, int q_offset, void* stream) {
+// flexam_attn_fwd_window_at and, with c.win_halo set, flexam_attn_fwd_window_halo: c holds the operands, the sizes and the stream
+static int attn_window_at(AttnCall c, int window_left, int window_right, int frame_tokens, int sink, int q_offset) {
+  const int Lq = c.Lq, Lk = c.Lk;
   FX_REQUIRE(q_offset >= 0, FLEXAM_E_ARG, "attn_fwd_window_at: negative q_offset %d", q_offset);
   FX_REQUIRE(sink >= 0, FLEXAM_E_ARG, "attn_fwd: negative sink %d", sink);
   FX_REQUIRE(frame_tokens >= 0, FLEXAM_E_ARG, "attn_fwd_window_at: frame_tokens %d (0 = a token window)", frame_tokens);
-  AttnCall c;
-  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
-  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
-  if (q_offset == 0 && Lq == Lk) {         // one length from token 0: the entry point of the form asked for, launch for launch
+  if (q_offset == 0 && Lq == Lk && !c.win_halo) {         // one length from token 0: the entry point of the form asked for, launch for launch
     c.win_left = window_left; c.win_right = window_right; c.win_sink = sink; c.win_by_frames = frame_tokens > 0; c.win_frame = frame_tokens;
     return attn_run(c);
   }
@@ -1089,10 +1124,33 @@ extern "C" int flexam_attn_fwd_window_at(const void* q, int64_t q_bs, int64_t q_
   // whose window may lie behind every key, included), the right side iff it clips the first
   const bool clip_left = left >= 0 && ((rows - 1) / T - left) * T > 0;
   const bool clip_right = right >= 0 && (q_offset / T + right + 1) * T - 1 < Lk - 1;
-  if ((!clip_left && !clip_right) || sink >= Lk) return attn_run(c);      // every row sees every key: flexam_attn_fwd on (Lq, Lk)
+  // every row sees every key: flexam_attn_fwd on (Lq, Lk).  (win_halo: a compact buffer cannot serve that call; attn_run refuses it)
+  if ((!clip_left && !clip_right) || sink >= Lk) return attn_run(c);
   c.win_at = true; c.win_q0 = q_offset; c.win_by_frames = true; c.win_frame = (int)T;
   c.win_left = left; c.win_right = right; c.win_sink = sink;      // (attn_run drops the sink under left < 0, as for the sibling entry points)
   return attn_run(c);
+}
+
+extern "C" int flexam_attn_fwd_window_at(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
+                                         const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
+                                         int Lq, int Lk, int head_dim, float softmax_scale, int window_left, int window_right,
+                                         int frame_tokens, int sink, int q_offset, void* stream) {
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  return attn_window_at(c, window_left, window_right, frame_tokens, sink, q_offset);
+}
+
+extern "C" int flexam_attn_fwd_window_halo(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
+                                           const void* v, int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H,
+                                           int Lq, int Lk, int head_dim, float softmax_scale, int window_left, int window_right,
+                                           int frame_tokens, int sink, int q_offset, int key_gap_tiles, int k_rows, void* stream) {
+  AttnCall c;
+  c.q = q; c.q_bs = q_bs; c.q_rs = q_rs; c.k = k; c.k_bs = k_bs; c.k_rs = k_rs; c.v = v; c.v_bs = v_bs; c.v_rs = v_rs; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = softmax_scale; c.stream = stream;
+  // the whole sequence from row 0 on is flexam_attn_fwd_window_at, launch for launch
+  c.win_halo = !(key_gap_tiles == 0 && k_rows == Lk); c.win_key_gap = key_gap_tiles; c.win_k_rows = k_rows;
+  return attn_window_at(c, window_left, window_right, frame_tokens, sink, q_offset);
 }
 
 extern "C" int flexam_attn_fwd_lastkey(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs,
@@ -1318,5 +1376,13 @@ AttnInstance attn_at_instance(bool prescaled) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES;
   if (prescaled) return {attn_window_at_kernel<true>, BF, 13};
   return {attn_window_at_kernel<false>, BF, 12};
+}
+// ... and the same kernel on a compact key buffer (flexam_attn_fwd_window_halo; HALO in attn_fwd_body), behind those
+template <bool PRE>
+__global__ __launch_bounds__(NT, 2) void attn_window_halo_kernel(AttnParams p) { attn_fwd_body<0, PRE, false, false, true, true, true, true>(p); }
+AttnInstance attn_halo_instance(bool prescaled) {
+  constexpr int BF = NSLOT * 2 * KV_TILE_BYTES;
+  if (prescaled) return {attn_window_halo_kernel<true>, BF, 15};
+  return {attn_window_halo_kernel<false>, BF, 14};
 }
 }  // namespace

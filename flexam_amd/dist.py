@@ -288,6 +288,94 @@ def all_to_all_blocks(outs, ins, group=None, async_op: bool = False, packed=None
     return None
 
 
+class _Works:
+    """The Work handles of one grouped send / receive as one."""
+
+    def __init__(self, works):
+        self.works = works
+
+    def wait(self):
+        for w in self.works:
+            w.wait()
+        return True
+
+
+def exchange_rows(recvs, sends, group=None, async_op: bool = False, like: torch.Tensor = None):
+    """Point-to-point row ranges of uneven sizes (the halo exchange of windowed self-attention, dit_layout.halo_plan): sends = [(peer,
+    contiguous view), ...] leave for those ranks of `group`, recvs = [(peer, contiguous view), ...] are filled by them; either list may
+    be empty, for a peer or altogether.  The k-th view a rank sends a peer is the k-th that peer receives from it, so both sides list
+    their ranges in one order.  RCCL, and any backend on CPU tensors: ONE dist.batch_isend_irecv (a grouped send / receive; async_op =
+    True returns its Work, wait() makes the caller's stream wait for the exchange); no pack pass, every range lands where its consumer
+    reads it.  Other backends on device tensors (the gloo runs of the tests, which lack device send / receive): the same result from an
+    all-gather of every rank's packed sends, finished before returning (None), as all_to_all_blocks serves them.  LoopbackGroup: every
+    received range is filled by a copy of its own size, the link time that of the largest block one peer sends.
+    like: any tensor of the exchange's device and dtype, for a rank that neither sends nor receives (it still takes part in the
+    collectives of the all-gather form)."""
+    if isinstance(group, LoopbackGroup):
+        per_peer = {}
+        for peer, t in recvs:
+            per_peer[peer] = per_peer.get(peer, 0) + t.numel() * t.element_size()
+        src = max((t for _, t in sends), key=lambda t: t.numel(), default=None)
+
+        def copies():                                                     # a range "arrives" as a copy of rows this rank sends
+            for _, t in recvs:
+                flat = t.view(-1)
+                if src is None or src.numel() == 0:
+                    flat.zero_()
+                    continue
+                s = src.view(-1)
+                for off in range(0, flat.numel(), s.numel()):
+                    n = min(s.numel(), flat.numel() - off)
+                    flat[off:off + n].copy_(s[:n])
+        ref = recvs[0][1] if recvs else sends[0][1] if sends else like
+        if ref is None:
+            return _LoopbackWork(None) if async_op else None
+        return group.run(copies, ref, async_op, link_bytes=max(per_peer.values(), default=0))
+    ref = recvs[0][1] if recvs else sends[0][1] if sends else like
+    if dist.get_backend(group) == "nccl" or ref is None or ref.device.type == "cpu":
+        peer_of = (lambda p: dist.get_global_rank(group, p)) if group is not None else (lambda p: p)
+        ops = [dist.P2POp(dist.irecv, t, peer_of(p), group) for p, t in recvs] + [dist.P2POp(dist.isend, t, peer_of(p), group) for p, t in sends]
+        works = _Works(dist.batch_isend_irecv(ops) if ops else [])
+        if async_op:
+            return works
+        works.wait()
+        return None
+    return _exchange_rows_gathered(recvs, sends, group, ref)
+
+
+def _exchange_rows_gathered(recvs, sends, group, ref):
+    """exchange_rows from an all-gather of every rank's packed sends (their sizes first): for backends without device send / receive.
+    Every rank takes part in the two collectives, whatever it sends or receives itself.  ref: a tensor of the exchange's device and dtype."""
+    world, rank = dist.get_world_size(group), dist.get_rank(group)
+    meta = [None] * world
+    dist.all_gather_object(meta, [(int(p), t.numel()) for p, t in sends], group=group)
+    dtype, device = (ref.dtype, ref.device)
+    longest = max(1, max(sum(n for _, n in m) for m in meta))
+    mine = torch.zeros(longest, dtype=dtype, device=device)
+    off = 0
+    for _, t in sends:
+        mine[off:off + t.numel()].copy_(t.reshape(-1))
+        off += t.numel()
+    everything = torch.empty(world * longest, dtype=dtype, device=device)
+    dist.all_gather_into_tensor(everything, mine, group=group)
+    everything = everything.view(world, longest)
+    mine_from = {}
+    for p, t in recvs:
+        mine_from.setdefault(int(p), []).append(t)
+    for sender, m in enumerate(meta):
+        off, views = 0, iter(mine_from.get(sender, []))
+        for dst, n in m:
+            if dst == rank:
+                t = next(views)
+                if t.numel() != n:
+                    raise RuntimeError(f"exchange_rows: rank {sender} sends {n} elements where rank {rank} expects {t.numel()}")
+                t.view(-1).copy_(everything[sender, off:off + n])
+            off += n
+        if next(views, None) is not None:
+            raise RuntimeError(f"exchange_rows: rank {rank} expects more ranges from rank {sender} than it sends")
+    return None
+
+
 def shard_rows(full: torch.Tensor, batch: int, seq_len: int, rank: int, world: int, chunk: int = None) -> torch.Tensor:
     """Per-token vector [B*L] (e.g. the AdaLN row index) -> this rank's [B*Lc] slice of the padded sequence; pad tokens repeat the
     last real token's entry (the reference pads `t` with its last element, wan_transformer3d_FlexAM.py:930-934).  `chunk`: rows per

@@ -26,8 +26,9 @@ from typing import List, Optional
 import torch
 
 from . import hip
-from .dit_layout import SINGLE_RANK, resolve_mode, resolve_parallel, sage_asked, sage_window_asked, smooth_k_asked, smooth_v_asked, sp_window_asked
-from .dit_sp import HeadAllToAll, KVGather, RecordGather
+from .dit_layout import (SINGLE_RANK, halo_plan, resolve_mode, resolve_parallel, sage_asked, sage_window_asked, smooth_k_asked, smooth_v_asked,
+                         sp_halo_asked, sp_window_asked)
+from .dit_sp import HeadAllToAll, KVGather, KVHalo, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
 
@@ -73,6 +74,7 @@ class DiTEngine:
     _smooth_v_warned = False
     _sage_window_warned = False
     _sp_window_overlap_warned = False
+    _sp_halo_warned = False
 
     def __init__(self, model):
         self.model = model
@@ -458,6 +460,28 @@ class DiTEngine:
                 import warnings
                 warnings.warn("flexam_amd: VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION is ignored with window_size / window_frames: self-attention "
                               "runs the windowed bf16 kernel", RuntimeWarning, stacklevel=3)
+        # FLEXAM_SP_HALO=1 (default 0): under FLEXAM_SP_WINDOW=1, the K|V gather and the bf16 kernel a rank fetches only the key rows its
+        # windowed call visits (dit_layout.halo_plan; dit_sp.KVHalo).  Kept beside the mode and part of a launch plan's key.  halo_rows /
+        # halo_gather_rows: the rows of this rank's compact buffer and of the gathered buffer it replaces (None when the switch does not act)
+        self._sp_halo, self.halo_rows, self.halo_gather_rows = False, None, None
+        if sp_halo_asked(env) and self.sp_size > 1 and self.fused:
+            why = None
+            if not sp_window:
+                why = "the model has no window_size / window_frames"
+            elif m.sp_mode != "allgather" or m.sage:
+                why = "the all-to-all over heads hands a rank every token of its heads"
+            else:
+                mask = self._window_mask()
+                plans = [halo_plan(cd["L"], m.sp, r, mask[0], mask[1], mask[2]) for r in range(m.sp)]
+                if all(pl.gap == 0 and pl.rows == cd["L"] for pl in plans):
+                    why = "every rank's window reaches the whole sequence"
+                else:
+                    self._sp_halo, self.halo_rows, self.halo_gather_rows = True, plans[m.rank].rows, m.sp * m.lc
+            if why is not None and not DiTEngine._sp_halo_warned:      # said once per process
+                DiTEngine._sp_halo_warned = True
+                import warnings
+                warnings.warn(f"flexam_amd: FLEXAM_SP_HALO=1 is ignored ({why}): the exchange runs as it does without the switch",
+                              RuntimeWarning, stacklevel=3)
         return m
 
     def run(self, x: torch.Tensor, t_rows: torch.Tensor, row_index: Optional[torch.Tensor], rows_per_batch: int,
@@ -589,7 +613,7 @@ class DiTEngine:
         cd, ri, tabs = self.cond, ws["row_index"], ws["tabs", m.R, m.per_layer]
         key = (m, self._ws_gen, ri.data_ptr() if ri is not None else 0, tabs["blk"].data_ptr(), tabs["head"].data_ptr(), cd["cos"].data_ptr(),
                torch.cuda.current_stream().cuda_stream, hip.num_cus(), id(self.sp_group), getattr(self, "window", (-1, -1)), getattr(self, "window_sink", 0),
-               DiTEngine._window_frames(self), self._smooth_v, self._smooth_k)      # (unbound: the mode tests hand a bare namespace)
+               DiTEngine._window_frames(self), self._sp_halo, self._smooth_v, self._smooth_k)      # (unbound: the mode tests hand a bare namespace)
         plans = cd.setdefault("_plans", {})
         plan = plans.get(key)
         if plan is None:
@@ -835,6 +859,8 @@ class DiTEngine:
         """The exchange object of sequence-parallel self-attention in this forward's layout (flexam_amd/dit_sp.py): one per workspace and
         layout, made by the first forward that needs it."""
         cls = HeadAllToAll if m.sp_mode == "ulysses" else (RecordGather if m.sage else KVGather)      # (the all-to-all serves bf16 and SAGE)
+        if self._sp_halo:                                  # (DiTEngine._mode: the bf16 K|V gather of a windowed model, FLEXAM_SP_HALO=1)
+            cls = KVHalo
         ex = ws.get(("exchange", cls.__name__))
         if ex is None:
             ex = ws["exchange", cls.__name__] = cls(self, m, ws)

@@ -118,6 +118,65 @@ def sp_window_asked(env) -> bool:
     return env.get("FLEXAM_SP_WINDOW", "0") == "1"
 
 
+def sp_halo_asked(env) -> bool:
+    """FLEXAM_SP_HALO=1 (default 0): under FLEXAM_SP_WINDOW=1, the K|V gather and the bf16 kernel, a rank receives only the key rows its
+    windowed call visits (halo_plan) into a compact buffer and runs flexam_attn_fwd_window_halo on it (dit_sp.KVHalo).  Not a field of
+    _Mode: DiTEngine._mode keeps it beside the mode and keys its launch plans on it."""
+    return env.get("FLEXAM_SP_HALO", "0") == "1"
+
+
+# What a rank's windowed call reads of the sequence's keys, and who holds it (halo_plan).  gap: whole key tiles left out between the sink
+# tiles and the window tiles; rows: rows of the compact buffer; local: the rank's own rows in it, [(src_row0, dst_row0, n), ...];
+# recvs / sends: [(peer, src_row0, dst_row0, n), ...] -- src in rows of the SENDER's chunk, dst in rows of the RECEIVER's buffer --
+# sorted by peer and row, so that the k-th range a rank sends a peer is the k-th that peer receives from it
+HaloPlan = namedtuple("HaloPlan", "gap rows local recvs sends")
+
+
+def _halo_segments(L, sp, rank, window, sink, frame_tokens):
+    """(gap, rows, [(key0, key1, buffer_row0), ...]): the key ranges [key0, key1) the compact buffer of `rank` holds, at most two.  From
+    the runs hip.attn_window_at_tiles plans for the rank's query blocks, pad rows included (they are queries, and the kernel walks their
+    tiles): the sink tiles [0, s_n) are every block's first run; the window runs are non-decreasing in the block, so their union is one
+    run from the first block's first window tile to the last window tile of any block, and the first block's gap is the smallest."""
+    tile = hip.ATTN_KV_TILE
+    _, lc, tok0 = token_layout(L, sp, rank)
+    runs = hip.attn_window_at_tiles(lc, L, tok0, window, sink, frame_tokens)
+    s_n = -(-min(int(sink), L) // tile) if hip.attn_window(window)[0] >= 0 else 0
+    first = runs[0] if runs else []
+    gap = first[1][0] - s_n if len(first) == 2 else first[0][0] if first and not s_n else 0
+    end = max([r[-1][1] for r in runs if r], default=-1) + 1              # tiles: one behind the last any block visits
+    segs = [(0, min(s_n * tile, L), 0)] if s_n else []
+    if end > s_n + gap:
+        segs.append(((s_n + gap) * tile, min(end * tile, L), s_n * tile))
+    if len(segs) == 2 and gap == 0:                                       # the two runs touch: one range
+        segs = [(0, segs[1][1], 0)]
+    return gap, (segs[-1][1] - segs[-1][0] + segs[-1][2] if segs else 0), segs
+
+
+def halo_plan(L: int, sp: int, rank: int, window, sink: int = 0, frame_tokens: int = 0) -> HaloPlan:
+    """Which key rows travel to `rank` of `sp` for its windowed self-attention call (flexam_attn_fwd_window_halo), and which it sends.
+    The compact buffer is tile-aligned: the sink tiles, then the window tiles from global tile s_n + gap on, a last tile cut at L; every
+    row of it is a planned row (the rank's own, or one peer's), so no tile a unit can visit holds a row nobody wrote.  Pad rows (global
+    tokens from L on) are never keys.  Remote rows are at most the rows some query of the rank sees plus 3 x (ATTN_KV_TILE - 1): tile
+    alignment at the end of the sink run and at both ends of the window run.  gap = 0 and rows = L is the whole sequence: the call of
+    flexam_attn_fwd_window_at.  GPU-free; every rank can state every other rank's plan, which is how the sends are derived."""
+    lc = token_layout(L, sp, rank)[1]
+    chunk = lambda r: (r * lc, max(r * lc, min((r + 1) * lc, L)))         # the real rows of rank r
+    gap, rows, segs = _halo_segments(L, sp, rank, window, sink, frame_tokens)
+
+    def pieces(segments, holder):                                         # (src_row0, dst_row0, n) of `segments` held by `holder`
+        h0, h1 = chunk(holder)
+        out = []
+        for k0, k1, d0 in segments:
+            a, b = max(k0, h0), min(k1, h1)
+            if a < b:
+                out.append((a - h0, d0 + a - k0, b - a))
+        return out
+
+    recvs = [(p, *x) for p in range(sp) if p != rank for x in pieces(segs, p)]
+    sends = [(p, *x) for p in range(sp) if p != rank for x in pieces(_halo_segments(L, sp, p, window, sink, frame_tokens)[2], rank)]
+    return HaloPlan(gap, rows, pieces(segs, rank), recvs, sends)
+
+
 def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, parallel: Parallel, B, L, dens_same,
                  bx, R, rows_per_batch, only_row, rows_shared, teacache: bool, record_gather: bool = True) -> _Mode:
     """The mode of one forward.  env: the environment mapping; fused .. parallel: the engine (all blocks native, layers, heads, head

@@ -1,16 +1,16 @@
-"""The three exchanges of sequence-parallel self-attention in the DiT engine: the all-to-all over heads, the K|V all-gather in bf16
-and the all-gather of MXFP8 key / value records.  One object per (workspace, layout) (DiTEngine._exchange): it owns the exchange's
-buffers, planned splits, per-peer view lists and the Work handles between the host step that issues a collective and the one that
+"""The exchanges of sequence-parallel self-attention in the DiT engine: the all-to-all over heads, the K|V all-gather in bf16, its
+halo form for a windowed model (only the key rows a rank's window reaches travel) and the all-gather of MXFP8 key / value records.
+One object per (workspace, layout) (DiTEngine._exchange): it owns the exchange's buffers, planned splits, per-peer view lists and the Work handles between the host step that issues a collective and the one that
 waits for it.  It keeps no reference to the engine or the workspace that holds it (both are arguments of `run`), so dropping a
 workspace frees its buffers at once.  Buffers that code outside the engine reads are placed in the workspace under their names
-(a2a_recv, a2a_out, kv_cat).
+(a2a_recv, a2a_out, kv_cat, kv_halo).
 Collectives, waits and torch copies are host steps (hip.host_op): run in place, and again in that place by every replay of a
 recorded launch plan.  The arithmetic of the layouts is flexam_amd/dit_layout.py."""
 import torch
 
 from . import hip
-from .dist import all_gather_into_tensor, all_to_all_blocks, group_backend
-from .dit_layout import a2a_koff, gather_key_ranges, key_range_sizes
+from .dist import all_gather_into_tensor, all_to_all_blocks, exchange_rows, group_backend
+from .dit_layout import a2a_koff, gather_key_ranges, halo_plan, key_range_sizes
 
 BF16, I64 = torch.bfloat16, torch.int64
 
@@ -200,6 +200,66 @@ class KVGather:
             if n_after:
                 n += hip.attn_fwd_partial(qg, heads(kc[:, tok0 + lc:Lr]), heads(vc[:, tok0 + lc:Lr]), part, n, s_after, prescaled=True)
             hip.attn_merge(og, part, n, prescaled=True)
+
+
+class KVHalo:
+    """The K|V gather of a windowed model that moves only the halo (FLEXAM_SP_HALO=1 under FLEXAM_SP_WINDOW=1, bf16; DiTEngine._mode):
+    a rank's windowed call visits the sink tiles and one run of window tiles, so it receives those rows alone, from the peers that hold
+    them, into a compact buffer [G, B, rows, 2*C/G] (dit_layout.halo_plan states rows, ranges and peers; `rows` instead of sp * lc).  The
+    same RMSNorm+RoPE launch fills the same send buffer [G, B, lc, 2*C/G]; a row range of one head group and CFG row is contiguous in
+    both buffers, so the ranges travel as they lie (dist.exchange_rows: one grouped send / receive for all of them) and the rank's own
+    rows are one device copy.  The exchange is waited for, then one flexam_attn_fwd_window_halo call per head group runs at the rank's
+    query offset on the buffer.  Every row of the buffer below `rows` is written by each exchange: a visited tile never holds stale bytes."""
+
+    def __init__(self, eng, m, ws):
+        self.group = eng.sp_group
+        G = m.sp_pieces
+        self.cb, self.hg = cb, hg = eng.dim // G, eng.nh // G
+        self.send = torch.empty(G, m.B, m.lc, 2 * cb, device=eng.device, dtype=BF16)
+        self.overlapped = group_backend(self.group) in ("nccl", "loopback")
+        self.plan = self.plan_of = self.halo = self.work = None
+
+    def _layout(self, eng, m, ws):
+        """The plan and the buffer for this clip's length and mask (another clip under the same chunk size: its own)."""
+        mask = eng._window_mask()
+        key = (eng.cond["L"], mask)
+        if key != self.plan_of:
+            plan = halo_plan(eng.cond["L"], m.sp, m.rank, mask[0], mask[1], mask[2])
+            send = self.send
+            halo = ws["kv_halo"] = torch.empty(send.shape[0], send.shape[1], max(plan.rows, 1), send.shape[3], device=send.device, dtype=BF16)
+            pairs = [(g, b) for g in range(send.shape[0]) for b in range(send.shape[1])]
+            # the per-range views, made once: head group and CFG row outermost on both sides, so a peer's k-th send is my k-th receive
+            self.recvs = [(peer, halo[g, b, d:d + n]) for g, b in pairs for peer, _, d, n in plan.recvs]
+            self.sends = [(peer, send[g, b, s:s + n]) for g, b in pairs for peer, s, _, n in plan.sends]
+            self.plan, self.plan_of, self.halo = plan, key, halo
+        return self.plan, self.halo, self.recvs, self.sends
+
+    def run(self, eng, ws, a8sa, layer, p, m):
+        cd, send, cb, hg = eng.cond, self.send, self.cb, self.hg
+        d, hd, lc, tok0, qkv, Lr = eng.dim, eng.hd, m.lc, m.tok0, ws["qkv"], cd["L"]
+        plan, halo, recvs, sends = self._layout(eng, m, ws)
+        q4, _, _, ao4 = eng._heads(m, ws)
+        flat = send.view(-1)
+        hip.rmsnorm_rope_scatter(None, None, qkv[:, d:2 * d], p["nk"], qkv[:, 2 * d:], None, flat, flat[cb:], ld_out=2 * cb, out_bs=lc * 2 * cb,
+                                 col_block=cb, block_stride=m.B * lc * 2 * cb, eps=eng.eps, rope_cos=cd["cos"], rope_sin=cd["sin"],
+                                 tokens_per_batch=lc, token_offset=tok0, head_dim=hd)
+
+        def issue():
+            self.work = exchange_rows(recvs, sends, self.group, async_op=self.overlapped, like=send)
+            for s, dst, n in plan.local:
+                halo[:, :, dst:dst + n].copy_(send[:, :, s:s + n])
+        hip.host_op(issue)
+        if not m.sp_fused_qkv:
+            eng._proj(ws["h"], a8sa, layer, p, "wqkv", "bqkv", slice(0, d), qkv[:, 0:d])
+        hip.rmsnorm_rope(qkv[:, 0:d], p["nq"], eps=eng.eps, rope_cos=cd["cos"], rope_sin=cd["sin"], tokens_per_batch=lc, token_offset=tok0,
+                         head_dim=hd)
+        hip.host_op(lambda: self.work is not None and self.work.wait())
+        window, sink, T = eng._window_mask()
+        heads = lambda t: t.unflatten(2, (hg, hd))
+        for g in range(m.sp_pieces):
+            hip.attn_fwd_window(q4[:, :, g * hg:(g + 1) * hg], heads(halo[g, :, :, 0:cb]), heads(halo[g, :, :, cb:]), window,
+                                out=ao4[:, :, g * hg:(g + 1) * hg], prescaled=True, sink=sink, frame_tokens=T, q_offset=tok0,
+                                key_gap_tiles=plan.gap, Lk=Lr, k_rows=plan.rows)
 
 
 class RecordGather:

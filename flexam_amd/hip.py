@@ -632,7 +632,8 @@ def attn_window_at_tiles(Lq: int, Lk: int, q_offset: int, window, sink: int = 0,
     return out
 
 
-def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0, frame_tokens=0, q_offset=None):
+def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=False, sink=0, frame_tokens=0, q_offset=None,
+                    key_gap_tiles=None, Lk=None, k_rows=None):
     """attn_fwd under flash-attn's sliding-window mask (see flexam_hip.h): q, k, v [B, L, H, 128] bf16 with the layouts of attn_fwd and
     ONE length L; window = (left, right), a negative side unbounded, (-1, -1) the ordinary call.  Whole work units only (no split-KV).
     sink > 0: the first `sink` keys stay visible to every row whatever the window says (flexam_attn_fwd_window_sink); sink = 0 is the
@@ -640,8 +641,25 @@ def attn_fwd_window(q, k, v, window, out=None, softmax_scale=None, prescaled=Fal
     frames i // T - a .. i // T + b whole (flexam_attn_fwd_window_frames); frame_tokens = 0 changes no call.
     q_offset (None: the calls above, one length): the Lq rows of q are the global tokens q_offset .. q_offset + Lq - 1 of a sequence whose
     first Lk tokens are the keys (flexam_attn_fwd_window_at: a rank's chunk under sequence parallelism; Lq != Lk is welcome, rows from Lk on
-    are pad rows, and a row that sees no key comes back as zeros)."""
+    are pad rows, and a row that sees no key comes back as zeros).
+    key_gap_tiles (None: the calls above; with q_offset and Lk): k and v are a COMPACT buffer of k_rows rows (default: all of k's) of a
+    sequence of Lk keys -- the sink tiles, then the key tiles from global tile s_n + key_gap_tiles on, as dit_layout.halo_plan lays them
+    out (flexam_attn_fwd_window_halo, which refuses a buffer that a query block's tiles do not fit)."""
     B, L, H, D = q.shape
+    if key_gap_tiles is not None:
+        if q_offset is None or Lk is None:
+            raise RuntimeError("attn_fwd_window: a compact key buffer (key_gap_tiles) goes with q_offset and the global key count Lk")
+        k_rows = k.shape[1] if k_rows is None else int(k_rows)
+        if v.shape[1] != k.shape[1] or k_rows > k.shape[1]:
+            raise RuntimeError(f"attn_fwd_window: k_rows = {k_rows} of a compact buffer of {k.shape[1]} key and {v.shape[1]} value rows")
+        _packed_heads("attn_fwd_window", q, k, v)
+        if out is None:
+            out = torch.empty(B, L, H, D, device=q.device, dtype=BF16)
+        left, right = attn_window(window)
+        _call("flexam_attn_fwd_window_halo", _ptr(q, BF16), q.stride(0), q.stride(1), _ptr(k, BF16), k.stride(0), k.stride(1), _ptr(v, BF16),
+              v.stride(0), v.stride(1), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, L, int(Lk), D,
+              _softmax_scale(softmax_scale, prescaled, D), left, right, int(frame_tokens), int(sink), int(q_offset), int(key_gap_tiles), k_rows)
+        return out
     if q_offset is not None and (int(q_offset) != 0 or k.shape[1] != L):
         Lk = k.shape[1]
         if v.shape[1] != Lk:

@@ -189,6 +189,21 @@ int flexam_attn_fwd_window_at(const void* q, int64_t q_bs, int64_t q_rs, const v
                               int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int Lk, int head_dim,
                               float softmax_scale, int window_left, int window_right, int frame_tokens, int sink, int q_offset,
                               void* stream);
+/* flexam_attn_fwd_window_at on a COMPACT key buffer: what a rank runs when it has fetched only the halo of keys its window reaches.  Lk
+ * stays the global key count and every mask and bound is the one above; k and v point at k_rows rows that hold, with s_n =
+ * ceil(min(sink, Lk) / 64) (0 under window_left < 0, which drops the sink): the key rows of the sink tiles [0, s_n) at buffer rows
+ * 0 .. 64 s_n - 1, and behind them the key rows from global tile s_n + key_gap_tiles on -- global key j >= 64 s_n lies at buffer row
+ * j - 64 key_gap_tiles.  A last tile is cut at Lk as ever: no row past key Lk - 1 is read.  Before the launch the call walks its
+ * ceil(Lq / 256) query blocks on the host, by the kernel's own arithmetic; a block that visits a tile of the gap left out, or a tile whose
+ * key rows end behind buffer row k_rows - 1, makes the call FLEXAM_E_ARG and nothing is launched: a wrong plan is never an out-of-range
+ * read.  (The rows of a visited tile that no query sees are multiplied by a probability of exactly 0: they must be written, by anyone.)
+ * key_gap_tiles = 0 with k_rows = Lk is flexam_attn_fwd_window_at, launch for launch.  Otherwise the kernels are instances of their own
+ * (attn_window_halo_kernel), q_offset = 0 with Lq = Lk included; a call that no side clips, or sink >= Lk, reads every key and is
+ * FLEXAM_E_ARG on a compact buffer, as are key_gap_tiles < 0 and k_rows outside 0 .. Lk. */
+int flexam_attn_fwd_window_halo(const void* q, int64_t q_bs, int64_t q_rs, const void* k, int64_t k_bs, int64_t k_rs, const void* v,
+                                int64_t v_bs, int64_t v_rs, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int Lk, int head_dim,
+                                float softmax_scale, int window_left, int window_right, int frame_tokens, int sink, int q_offset,
+                                int key_gap_tiles, int k_rows, void* stream);
 /* flexam_attn_fwd with the work units u =(batch*H + head)*ceil(Lq/256) + q_block at and after `split_from_unit` cut into kv_splits key
  * ranges each (flash-decoding style partial softmaxes + a merge launch), the units before it in one pass: with
  * split_from_unit = floor(units/256)*256 only the last, partial round of the 256 CUs is split; 0 splits everything (ranks of a

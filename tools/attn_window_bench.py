@@ -39,8 +39,16 @@ walks (token and frame windows of +-2 / +-5 / +-12 frames, frame-block-causal, p
 round.  Per arm: the time, its share of the rank's unmasked launch, the share of (query block, key tile) pairs visited
 (hip.attn_window_at_tiles), and the number of work units.  No condition.
 
+--rank-of=N --halo: the same masks and ranks on a COMPACT key buffer (FLEXAM_SP_HALO=1's launch, hip.attn_fwd_window(..., q_offset=,
+key_gap_tiles=, Lk=)) -> profiles/attn_window_halo_bench.json.  K and V are packed by dit_layout.halo_plan; per mask and rank the halo
+launch is timed beside the q_offset launch on the full keys, three arms per round -- full keys, halo, full keys again, the order rotating
+--, and both must give the same bytes: `margin` is the spread of the full-key launch against itself (its two arms' medians),
+`halo_over_at` the halo median over the pooled full-key median, `slower_beyond_margin` says whether it exceeds 1 + margin.  Beside
+them the planned rows: the buffer's, the remote rows a rank receives, and the Lk - Lq the gather moves.  No condition.
+
 usage: attn_window_bench.py [--iters=10] [--rounds=7] [--out=profiles/attn_window_bench.json]
        attn_window_bench.py --rank-of=8 [--out=profiles/attn_window_sp_bench.json]
+       attn_window_bench.py --rank-of=8 --halo [--out=profiles/attn_window_halo_bench.json]
        attn_window_bench.py --sage [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sage_bench.json]
        attn_window_bench.py --sink=0,448,896 [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sink_bench.json]
        attn_window_bench.py --frames[=2,5,12] [--sink=0,448] [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_frames_bench.json]"""
@@ -235,8 +243,71 @@ def rank_bench(N):
     print("wrote", path)
 
 
+def halo_bench(N):
+    """--rank-of=N --halo: see the module docstring."""
+    from flexam_amd.dit_layout import halo_plan
+    Lq = -(-L // N)
+    q_pad = torch.zeros(B, N * Lq, heads, D, dtype=torch.bfloat16, device="cuda")
+    q_pad[:, :L] = q
+    outs = [torch.empty(B, Lq, heads, D, dtype=torch.bfloat16, device="cuda") for _ in range(2)]
+    masks = [(f"tokens_{n}_{n}_sink_{s}", (FRAME * n, FRAME * n), s, 0) for n in (2, 5, 12) for s in (0, FRAME)]
+    masks += [(f"{name}_sink_{s}", w, s, FRAME) for name, w in [(f"frames_{n}_{n}", (n, n)) for n in (2, 5, 12)] +
+              [("frames_block_causal", (-1, 0)), ("frames_per_frame", (0, 0))] for s in (0, FRAME)]
+    rec = dict(shape=dict(B=B, H=heads, Lk=L, Lq=Lq, ranks=N, head_dim=D, frame_tokens=FRAME, prescaled=True), iters=iters, rounds=rounds,
+               device=torch.cuda.get_device_name(0), gather_remote_rows=L - Lq,
+               method="one process; per rank and mask the launch on the full keys (hip.attn_fwd_window(..., q_offset=)) and the launch on the "
+                      "compact buffer dit_layout.halo_plan lays out (..., key_gap_tiles=, Lk=), three arms per round -- full keys, halo, full keys, "
+                      "the order rotating --, device events around `iters` back-to-back launches, median over the rounds; the two launches "
+                      "must give the same bytes; margin: the full-key launch against itself; remote_rows: what the rank receives, of "
+                      "gather_remote_rows under the K|V gather", ranks={})
+    for rank in sorted({0, N // 2, N - 1}):
+        off = rank * Lq
+        qr = q_pad[:, off:off + Lq]
+        arms = {}
+        print(f"rank {rank} of {N} (rows {off} .. {off + Lq - 1})")
+        for name, w, s, ft in masks:
+            plan = halo_plan(L, N, rank, w, s, ft)
+            s_n = -(-min(s, L) // H.ATTN_KV_TILE) if w[0] >= 0 else 0
+            rows = torch.arange(plan.rows, device="cuda")
+            rows = torch.where(rows < s_n * H.ATTN_KV_TILE, rows, rows + plan.gap * H.ATTN_KV_TILE)
+            kc, vc = k[:, rows].contiguous(), v[:, rows].contiguous()
+            at = lambda out: H.attn_fwd_window(qr, k, v, w, out=out, prescaled=True, sink=s, frame_tokens=ft, q_offset=off)
+            halo = lambda out: H.attn_fwd_window(qr, kc, vc, w, out=out, prescaled=True, sink=s, frame_tokens=ft, q_offset=off,
+                                                 key_gap_tiles=plan.gap, Lk=L)
+            at(outs[0])
+            halo(outs[1])
+            torch.cuda.synchronize()
+            same = bool(torch.equal(outs[0], outs[1]))
+            calls = [("at_a", lambda: at(outs[0])), ("halo", lambda: halo(outs[1])), ("at_b", lambda: at(outs[0]))]
+            ms = {n: [] for n, _ in calls}
+            for r in range(rounds):
+                for n, fn in calls[r % 3:] + calls[:r % 3]:
+                    ms[n].append(timed_call(fn))
+            med = {n: statistics.median(x) for n, x in ms.items()}
+            pooled = statistics.median(ms["at_a"] + ms["at_b"])
+            margin = abs(med["at_a"] - med["at_b"]) / pooled
+            ratio = med["halo"] / pooled
+            remote = sum(n for *_, n in plan.recvs)
+            arms[name] = dict(window=list(w), sink=s, frame_tokens=ft, key_gap_tiles=plan.gap, buffer_rows=plan.rows, remote_rows=remote,
+                              remote_share=round(remote / (L - Lq), 4), whole_sequence=plan.gap == 0 and plan.rows == L, same_bytes=same,
+                              at_ms=round(pooled, 4), at_a_ms=round(med["at_a"], 4), at_b_ms=round(med["at_b"], 4), halo_ms=round(med["halo"], 4),
+                              halo_ms_min=round(min(ms["halo"]), 4), halo_ms_max=round(max(ms["halo"]), 4), margin=round(margin, 4),
+                              halo_over_at=round(ratio, 4), slower_beyond_margin=bool(ratio > 1 + margin))
+            print(f"  {name:30s} at {pooled:7.3f} ms  halo {med['halo']:7.3f} ms  ratio {ratio:6.4f} (margin {margin:6.4f})  rows {plan.rows:6d} "
+                  f"remote {remote:6d} of {L - Lq}  same bytes {same}")
+        rec["ranks"][str(rank)] = dict(q_offset=off, arms=arms)
+    path = os.path.join(root, opt.get("out", "profiles/attn_window_halo_bench.json"))
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
+
+
 if "sage" in opt:
     sage_bench()
+    sys.exit(0)
+if "rank-of" in opt and "halo" in opt:
+    halo_bench(int(opt["rank-of"] or 8))
     sys.exit(0)
 if "rank-of" in opt:
     rank_bench(int(opt["rank-of"] or 8))
