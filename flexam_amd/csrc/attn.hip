@@ -240,7 +240,8 @@ __device__ __forceinline__ void store_partial(const AttnParams& p, const f32x16 
 // per dword between the groups of a pair (lower lanes give their part of the odd group, upper lanes their part of the even
 // one) leaves 16 contiguous bytes in every lane: 8 stores of 16 B instead of 16 of 8 B (the tail is store-issue bound).
 // OSHIFT: p.o_shift[b][head * 128 + column] is added to O / l in fp32, loaded here (behind the key loop) in the accumulator's column order.
-template <bool OSHIFT = false>
+// EMPTY (the attn8_window_at instances with OSHIFT): inv_l = 0 marks a row that saw no key, which is written as zeros, not as the shift.
+template <bool OSHIFT = false, bool EMPTY = false>
 __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (&o_acc)[4], float inv_l, int b, int head, int qi, int h) {
   bf16* orow = p.o + (int64_t)b * p.o_bs + (int64_t)min(qi, p.Lq - 1) * p.o_rs + head * HD + 8 * h;
   const float* srow = OSHIFT ? p.o_shift + ((int64_t)b * p.H + head) * HD + 4 * h : nullptr;
@@ -253,6 +254,7 @@ __device__ __forceinline__ void store_output(const AttnParams& p, const f32x16 (
       if constexpr (OSHIFT) {
         se = *(const f32x4*)(srow + 32 * dt + 8 * i);
         so = *(const f32x4*)(srow + 32 * dt + 8 * i + 8);
+        if constexpr (EMPTY) if (inv_l == 0.f) { se = (f32x4){0.f, 0.f, 0.f, 0.f}; so = se; }
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -892,6 +894,9 @@ constexpr int ATTN_INSTANCES = 16;
 // the two windowed MXFP8 kernels take their mask as a second argument; defined at the end of this file, as the two below
 struct Attn8WindowInstance { void (*kern)(AttnParams, Attn8Window); int slot; };      // slot in win_attr_set (attn_run)
 Attn8WindowInstance attn8_window_instance(bool oshift);
+// ... and the two at a query offset (slots 2 and 3), defined last of all in this file
+struct Attn8WindowAtInstance { void (*kern)(AttnParams, Attn8WindowAt); int slot; };
+Attn8WindowAtInstance attn8_window_at_instance(bool oshift);
 // the two attn_window_frames_kernel instances (slots 10 and 11).  Defined at the end of this file, so that they are emitted behind every
 // other kernel of it: a listing of this file then differs from one without them by the two kernels alone (tools/isa_diff.py)
 AttnInstance attn_frames_instance(bool prescaled);
@@ -959,9 +964,9 @@ int attn_run(const AttnCall& c) {
   // a sink that holds every key leaves no mask; one under a window without a left bound (nothing lies to the left of it) adds no key
   const bool window = (win_left >= 0 || win_right >= 0) && c.win_sink < c.Lk;
   const int win_sink = win_left < 0 ? 0 : c.win_sink;
-  FX_REQUIRE(!c.win_at || (window && !c.q8 && c.win_by_frames && c.win_q0 >= 0), FLEXAM_E_ARG, "attn_fwd: a window at an offset is a bf16 call under a mask");
-  FX_REQUIRE(!window || ((c.Lq == c.Lk || c.win_at) && c.kv8_chunk_tiles == 0 && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f), FLEXAM_E_ARG,
-             "attn_fwd: a window goes with operands of one length (MXFP8: one chunk) and whole work units");
+  FX_REQUIRE(!c.win_at || (window && c.win_by_frames && c.win_q0 >= 0), FLEXAM_E_ARG, "attn_fwd: a window at an offset is a call under a mask");
+  FX_REQUIRE(!window || ((c.Lq == c.Lk || c.win_at) && (c.kv8_chunk_tiles == 0 || (c.win_at && c.q8)) && c.kv_splits == 1 && c.partial_slot0 < 0 && c.last_key_bias == 0.f),
+             FLEXAM_E_ARG, "attn_fwd: a window goes with operands of one length (MXFP8: one chunk) or a query offset, and whole work units");
   FX_REQUIRE(tiles_all < 65536, FLEXAM_E_SHAPE, "attn_fwd: %d key tiles (at most 65535)", tiles_all);
   p.kv8_chunk_magic = p.kv8_chunk_tiles > 1 ? (unsigned)(((1ull << 32) + (unsigned)p.kv8_chunk_tiles - 1) / (unsigned)p.kv8_chunk_tiles) : 0u;
   // (in the words of four MXFP8 fields above: see AttnParams.  A token window leaves win_frame 0, the low word of the null qs, and runs
@@ -1001,16 +1006,23 @@ int attn_run(const AttnCall& c) {
     // One workgroup per unit, every unit whole
     const Attn8Window w = {win_left, win_right, win_sink, c.win_by_frames ? c.win_frame : 0};
     const Attn8WindowInstance wi = attn8_window_instance(c.o_shift != nullptr);
+    const Attn8WindowAtInstance ai = attn8_window_at_instance(c.o_shift != nullptr);      // (win_at: flexam_attn_fwd_fp8_window_at, the records in chunks)
+    const void* kern = c.win_at ? (const void*)ai.kern : (const void*)wi.kern;
     constexpr int F8 = NSLOT * REC_BYTES;
-    static bool win_attr_set[FLEXAM_MAX_DEVICES][2] = {};
-    bool& raised = win_attr_set[flexam_current_device()][wi.slot];
+    static bool win_attr_set[FLEXAM_MAX_DEVICES][4] = {};
+    bool& raised = win_attr_set[flexam_current_device()][c.win_at ? ai.slot : wi.slot];
     if (!raised) {
-      if (hipFuncSetAttribute((const void*)wi.kern, hipFuncAttributeMaxDynamicSharedMemorySize, F8) != hipSuccess)
+      if (hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, F8) != hipSuccess)
         return flexam_fail(FLEXAM_E_LAUNCH, "attn_fwd: cannot raise dynamic LDS to %d bytes", F8);
       raised = true;
     }
     const int n = c.B * c.H * p.q_blocks;
     p.unit0 = 0; p.n_units = n; p.kv_splits = 1; p.tiles_per_split = tiles_all;
+    if (c.win_at) {
+      const Attn8WindowAt a = {w, c.win_q0};
+      hipLaunchKernelGGL(ai.kern, dim3(n), dim3(NT), F8, (hipStream_t)c.stream, p, a);
+      return flexam_check_launch("flexam_attn_fwd_fp8_window_at");
+    }
     hipLaunchKernelGGL(wi.kern, dim3(n), dim3(NT), F8, (hipStream_t)c.stream, p, w);
     return flexam_check_launch("flexam_attn_fwd_fp8_window");
   }
@@ -1106,7 +1118,8 @@ static int attn_window_at(AttnCall c, int window_left, int window_right, int fra
   FX_REQUIRE(q_offset >= 0, FLEXAM_E_ARG, "attn_fwd_window_at: negative q_offset %d", q_offset);
   FX_REQUIRE(sink >= 0, FLEXAM_E_ARG, "attn_fwd: negative sink %d", sink);
   FX_REQUIRE(frame_tokens >= 0, FLEXAM_E_ARG, "attn_fwd_window_at: frame_tokens %d (0 = a token window)", frame_tokens);
-  if (q_offset == 0 && Lq == Lk && !c.win_halo) {         // one length from token 0: the entry point of the form asked for, launch for launch
+  // (MXFP8, flexam_attn_fwd_fp8_window_at: its entry point leaves kv8_chunk_tiles 0 where one chunk holds exactly the call's tiles)
+  if (q_offset == 0 && Lq == Lk && !c.win_halo && c.kv8_chunk_tiles == 0) {         // one length from token 0: the entry point of the form asked for, launch for launch
     c.win_left = window_left; c.win_right = window_right; c.win_sink = sink; c.win_by_frames = frame_tokens > 0; c.win_frame = frame_tokens;
     return attn_run(c);
   }
@@ -1125,7 +1138,12 @@ static int attn_window_at(AttnCall c, int window_left, int window_right, int fra
   const bool clip_left = left >= 0 && ((rows - 1) / T - left) * T > 0;
   const bool clip_right = right >= 0 && (q_offset / T + right + 1) * T - 1 < Lk - 1;
   // every row sees every key: flexam_attn_fwd on (Lq, Lk).  (win_halo: a compact buffer cannot serve that call; attn_run refuses it)
-  if ((!clip_left && !clip_right) || sink >= Lk) return attn_run(c);
+  if ((!clip_left && !clip_right) || sink >= Lk) {
+    // (MXFP8: flexam_attn_fwd_fp8_chunked at kv_splits = 1, which takes no output shift)
+    FX_REQUIRE(!(c.q8 && c.o_shift), FLEXAM_E_ARG, "attn_fwd_fp8_window_at: no side of the window clips a row of this call, which is "
+               "flexam_attn_fwd_fp8_chunked, and that call takes no o_shift");
+    return attn_run(c);
+  }
   c.win_at = true; c.win_q0 = q_offset; c.win_by_frames = true; c.win_frame = (int)T;
   c.win_left = left; c.win_right = right; c.win_sink = sink;      // (attn_run drops the sink under left < 0, as for the sibling entry points)
   return attn_run(c);
@@ -1344,6 +1362,20 @@ extern "C" int flexam_attn_fwd_fp8_window(const void* q8, const void* qs, const 
   return attn_run(c);
 }
 
+extern "C" int flexam_attn_fwd_fp8_window_at(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq,
+                                             int Lk, int chunk_tiles, int head_dim, int window_left, int window_right, int sink, int frame_tokens,
+                                             int q_offset, const float* o_shift, void* stream) {
+  FX_REQUIRE(q8 && qs && kv8, FLEXAM_E_ARG, "attn_fwd_fp8_window_at: null pointer");
+  FX_REQUIRE(((uintptr_t)q8 | (uintptr_t)qs | (uintptr_t)kv8) % 16 == 0, FLEXAM_E_ARG, "attn_fwd_fp8_window_at: misaligned pointer");
+  FX_REQUIRE(chunk_tiles > 0, FLEXAM_E_ARG, "attn_fwd_fp8_window_at: chunk_tiles = %d", chunk_tiles);
+  AttnCall c;
+  c.q8 = q8; c.qs = qs; c.kv8 = kv8; c.o = o; c.o_bs = o_bs; c.o_rs = o_rs;
+  c.B = B; c.H = H; c.Lq = Lq; c.Lk = Lk; c.head_dim = head_dim; c.softmax_scale = FLEXAM_ATTN_PRESCALED; c.stream = stream; c.o_shift = o_shift;
+  // one chunk that holds exactly the call's tiles is the record layout of the plain call: with q_offset = 0 and Lq == Lk, flexam_attn_fwd_fp8_window
+  c.kv8_chunk_tiles = q_offset == 0 && Lq == Lk && Lk > 0 && chunk_tiles == (Lk + KVBLK - 1) / KVBLK ? 0 : chunk_tiles;
+  return attn_window_at(c, window_left, window_right, frame_tokens, sink, q_offset);
+}
+
 extern "C" int flexam_attn_merge(void* o, int64_t o_bs, int64_t o_rs, int B, int H, int Lq, int head_dim, float softmax_scale,
                                  int n_slots, const float* ws_o, const float* ws_ml, void* stream) {
   FX_REQUIRE(o && ws_o && ws_ml, FLEXAM_E_ARG, "attn_merge: null pointer");
@@ -1384,5 +1416,10 @@ AttnInstance attn_halo_instance(bool prescaled) {
   constexpr int BF = NSLOT * 2 * KV_TILE_BYTES;
   if (prescaled) return {attn_window_halo_kernel<true>, BF, 15};
   return {attn_window_halo_kernel<false>, BF, 14};
+}
+// ... and, last, the windowed MXFP8 kernels at a query offset (flexam_attn_fwd_fp8_window_at; AT in attn8_fwd_body)
+Attn8WindowAtInstance attn8_window_at_instance(bool oshift) {
+  if (oshift) return {attn8_window_at_oshift_kernel<0>, 3};
+  return {attn8_window_at_kernel<0>, 2};
 }
 }  // namespace

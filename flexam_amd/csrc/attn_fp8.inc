@@ -45,6 +45,10 @@ __device__ __forceinline__ i32x8 join8(u32x4 lo, u32x4 hi) {
 // lo(i) <= j <= hi(i), with lo = i - left, hi = i + right in tokens (frame = 0), or lo = (i / T - left) T, hi = (i / T + right + 1) T - 1
 // with frame = T > 0; a negative side is unbounded.  The rule of the bf16 kernel's WIN / FRAMES instances (attn.hip).
 struct Attn8Window { int left, right, sink, frame; };
+// ... and that of the instances at a query offset (attn8_window_at_kernel, attn8_window_at_oshift_kernel; flexam_attn_fwd_fp8_window_at): a
+// sibling, so that the two kernels above keep their argument.  Row i of the call is global token g = q_offset + i and sees key j
+// (0 <= j < Lk) iff j < sink or lo(g) <= j <= hi(g): a rank's lc queries against the records of every rank's chunk, Lq and Lk two lengths
+struct Attn8WindowAt { Attn8Window w; int q_offset; };
 
 // The kernel's body, inlined into its __global__ wrappers below (KIND: the profiler symbol, as attn_fwd_kernel's).  OSHIFT: the
 // epilogue adds p.o_shift (smooth-V) to O / l in fp32 in front of the rounding to bf16 -- loaded behind the key loop, nothing of it inside.
@@ -58,8 +62,13 @@ struct Attn8Window { int left, right, sink, frame; };
 // reference the way the prologue does for every row of the other instances -- O = l = 0 until then, so nothing is rescaled, and rd
 // counts from there.  A half tile in which a row sees nothing is all -inf: its maximum moves no reference (-inf passes no test; the
 // factors are selected, never computed from it) and its exponentials are exactly 0.  Every row sees its own key: l > 0 at the end.
-template <int KIND, bool OSHIFT, bool WIN = false>
-__device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Window w = {}) {
+// AT (on top of WIN; g0 = the global token of the call's row 0): the unit's bounds and the lane's row are taken at g0 + ..., the keys are
+// the first Lk tokens and their records come in chunks ([chunk][B][H][chunk_tiles], as the unwindowed kernel reads them).  Rows from
+// global token Lk on are pad rows: queries, never keys.  A unit none of whose rows sees a key issues no tile and writes zeros
+// (attn_fwd_body's arithmetic for it, attn.hip); a row that sees no key in a unit that walks some stays unstarted to the end -- O = l = 0,
+// reference 0 -- and is written as zeros (with OSHIFT too), not as 0 / 0.
+template <int KIND, bool OSHIFT, bool WIN = false, bool AT = false>
+__device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Window w = {}, const int g0 = 0) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // ring of 4 records
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -103,7 +112,7 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Wi
   // shared: the bf16 windowed instances keep the parent's machine code, and FRAMES is a template argument there, w.frame > 0 a test here)
   int w_n = 0, ti_lo = 0, ti_hi = 0, s_n = 0, s_full = 0, gap = 0;
   if constexpr (WIN) {
-    const int qa = qb * QBLK, qz = min(qa + QBLK, p.Lq) - 1;      // first and last row of the unit
+    const int qa = g0 + qb * QBLK, qz = g0 + min(qb * QBLK + QBLK, p.Lq) - 1;      // first and last row of the unit (AT: as global tokens)
     int fa = 0, fz = 0;
     if (w.frame > 0) { fa = (int)((unsigned)qa / (unsigned)w.frame); fz = (int)((unsigned)qz / (unsigned)w.frame); }
     const int lo_a = w.frame > 0 ? (fa - w.left) * w.frame : qa - w.left;
@@ -114,6 +123,7 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Wi
     s_full = w.sink / KVBLK;
     gap = max(0, k_first / KVBLK - s_n);
     w_n = max(k_last / KVBLK, s_n - 1) + 1 - gap;
+    if constexpr (AT) if (k_first > k_last) { gap = 0; w_n = s_n; }      // every row's window lies behind the last key: the sink tiles alone, or none
     const int lo_z = w.frame > 0 ? (fz - w.left) * w.frame : qz - w.left;
     ti_lo = w.left < 0 ? 0 : (max(0, lo_z) + KVBLK - 1) / KVBLK;
     const int hi_a = w.frame > 0 ? (fa + w.right + 1) * w.frame - 1 : qa + w.right;
@@ -124,6 +134,17 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Wi
   }
   const int t0 = WIN ? 0 : split * tps;
   const int ntiles = WIN ? w_n : min(tps, tiles_all - t0);
+  if constexpr (AT) {
+    if (ntiles == 0) {                       // no row of the unit sees a key: zeros, and no record read (uniform over the workgroup)
+      f32x16 z[4];
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) z[dt][e] = 0.f;
+      store_output(p, z, 0.f, b, head, q0 + r_, h_);
+      return;
+    }
+  }
   // records: [chunk][B][H][chunk_tiles]; one chunk holds all tiles unless the records came out of a sequence-parallel all-gather
   // (flexam_attn_fwd_fp8_chunked).  Tile g = t0 + t -> chunk g / chunk_tiles by one scalar multiply-high (uniform: scalar registers)
   const unsigned ct = (unsigned)p.kv8_chunk_tiles, cmagic = p.kv8_chunk_magic;
@@ -134,7 +155,7 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Wi
   auto issue_tile = [&](int t, int parts, int tslot = -1) {      // parts: 1 = K (+ the scales of both), 2 = V; tslot: the ring position (default t)
     const unsigned slot = lds0 + (unsigned)(((tslot < 0 ? t : tslot) & (NSLOT - 1)) * REC_BYTES);
     const unsigned gt = WIN ? (unsigned)(t < s_n ? t : t + gap) : (unsigned)(t0 + t);      // (WIN: one chunk holds all tiles)
-    const unsigned chunk = WIN ? 0u : ct > 1 ? __umulhi(gt, cmagic) : gt;
+    const unsigned chunk = WIN && !AT ? 0u : ct > 1 ? __umulhi(gt, cmagic) : gt;      // (AT: the global tile through the chunk table)
     const char* src = rec0 + (chunk * chunk_recs + (gt - chunk * ct)) * REC_BYTES;
     if (parts & 1) {
       lds_dma16_sbase(src, voff16, slot + wave * 1024);
@@ -170,7 +191,7 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Wi
   // half's base is uniform.  The visible in-half positions as ONE bit mask, as attn_fwd_body's mask_window has them and for its reason.
   int w_lo = 0, w_hi = 0, w_sk = 0;
   if constexpr (WIN) {
-    const int row = q0 + r_, h4 = 4 * h_;
+    const int row = g0 + q0 + r_, h4 = 4 * h_;      // (AT: the lane's row as a global token)
     const int f = w.frame > 0 ? (int)((unsigned)row / (unsigned)w.frame) : 0;
     w_lo = w.left < 0 ? -(1 << 30) : (w.frame > 0 ? (f - w.left) * w.frame : row - w.left) - h4;
     w_hi = (w.right < 0 ? p.Lk - 1 : min(p.Lk - 1, w.frame > 0 ? (f + w.right + 1) * w.frame - 1 : row + w.right)) - h4;
@@ -388,7 +409,8 @@ __device__ __forceinline__ void attn8_fwd_body(const AttnParams p, const Attn8Wi
     store_partial<true>(p, o_acc, osc, ref, l_tot, split, ul, wave, r, h, q0 + r);      // reference in exp2 units (the merge runs in its prescaled form)
     return;
   }
-  store_output<OSHIFT>(p, o_acc, osc / l_tot, b, head, q0 + r, h);
+  if constexpr (AT) store_output<OSHIFT, true>(p, o_acc, l_tot > 0.f ? osc / l_tot : 0.f, b, head, q0 + r, h);      // (a row that saw no key is zeros)
+  else store_output<OSHIFT>(p, o_acc, osc / l_tot, b, head, q0 + r, h);
 }
 
 template <int KIND>
@@ -402,6 +424,12 @@ template <int KIND>
 __global__ __launch_bounds__(NT, 2) void attn8_window_kernel(AttnParams p, Attn8Window w) { attn8_fwd_body<KIND, false, true>(p, w); }
 template <int KIND>
 __global__ __launch_bounds__(NT, 2) void attn8_window_oshift_kernel(AttnParams p, Attn8Window w) { attn8_fwd_body<KIND, true, true>(p, w); }
+// ... and the windowed instances at a query offset on chunked records (flexam_attn_fwd_fp8_window_at), emitted behind those by
+// attn8_window_at_instance at the end of attn.hip
+template <int KIND>
+__global__ __launch_bounds__(NT, 2) void attn8_window_at_kernel(AttnParams p, Attn8WindowAt a) { attn8_fwd_body<KIND, false, true, true>(p, a.w, a.q_offset); }
+template <int KIND>
+__global__ __launch_bounds__(NT, 2) void attn8_window_at_oshift_kernel(AttnParams p, Attn8WindowAt a) { attn8_fwd_body<KIND, true, true, true>(p, a.w, a.q_offset); }
 
 // ---- the pack kernel: q, k (after RMSNorm + RoPE; q carrying softmax_scale * log2 e) and v, bf16 [B, L, H, 128] -> MXFP8 operands.
 // One workgroup per (64-token tile, head, batch).  K and Q: thread = (token row, 32-channel block); V: thread = (channel, 32-key half

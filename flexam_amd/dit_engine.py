@@ -27,7 +27,7 @@ import torch
 
 from . import hip
 from .dit_layout import (SINGLE_RANK, halo_plan, resolve_mode, resolve_parallel, sage_asked, sage_window_asked, smooth_k_asked, smooth_v_asked,
-                         sp_halo_asked, sp_window_asked)
+                         sp_halo_asked, sp_sage_window_asked, sp_window_asked)
 from .dit_sp import HeadAllToAll, KVGather, KVHalo, RecordGather
 from .implicit_conv import GuardedImage, PackedConv, Tap, pad_k, reach, round_up
 from .rope import rope_angle_table, rope_tables
@@ -416,13 +416,16 @@ class DiTEngine:
                 import warnings
                 warnings.warn("flexam_amd: FLEXAM_SP_OVERLAP is ignored with window_size / window_frames under the K|V all-gather: each "
                               "piece of the gather is waited for and one windowed attention call follows", RuntimeWarning, stacklevel=3)
-        # (record_gather: the gathered MXFP8 records are read by flexam_attn_fwd_fp8_chunked, which has no mask -- under a window the
-        #  ranks gather bf16 K|V and pad to the ranks alone, whatever FLEXAM_SAGE_WINDOW says)
+        # (record_gather: under a window the ranks gather bf16 K|V and pad to the ranks alone, whatever FLEXAM_SAGE_WINDOW says -- unless
+        #  FLEXAM_SP_SAGE_WINDOW=1 (default 0; with FLEXAM_SP_WINDOW=1, SAGE_ATTENTION and FLEXAM_SAGE_WINDOW=1 only) asks for the MXFP8
+        #  records, which flexam_attn_fwd_fp8_window_at reads under the mask at the rank's query offset: resolve_mode then decides
+        #  sage_gather as it does for an unmasked model, and where it does not resolve the replacement below runs as ever)
+        sp_sage_window = sp_window and sp_sage_window_asked(env)
         m = resolve_mode(env, fused=self.fused, nl=self.nl, nh=self.nh, hd=self.hd, dim=self.dim, table_limit=self.table_limit, fp8=self.fp8,
                          sp=self.sp_size, rank=self.sp_rank,
                          parallel=(self.sp_mode, overlap, self.sp_pieces, self.sp_fused_qkv),
                          B=cd["B"], L=cd["L"], dens_same=cd.get("dens_same", False), bx=bx, R=R, rows_per_batch=rows_per_batch,
-                         only_row=only_row, rows_shared=rows_shared, teacache=teacache is not None, record_gather=not sp_window)
+                         only_row=only_row, rows_shared=rows_shared, teacache=teacache is not None, record_gather=not sp_window or sp_sage_window)
         if sage_asked(env) and not m.sage and not sp_window and not DiTEngine._sage_warned:          # said once per process
             DiTEngine._sage_warned = True
             import warnings
@@ -451,7 +454,8 @@ class DiTEngine:
         # FLEXAM_SAGE_WINDOW=1 (default 0): a windowed model under SAGE runs the windowed MXFP8 kernel (flexam_attn_fwd_fp8_window); the mode
         # keeps `sage` then, which tells a launch plan of it from one of the replacement below.  Without the switch:
         # (under sequence parallelism, FLEXAM_SP_WINDOW=1: the same, and with the switch the all-to-all over heads alone keeps `sage` --
-        #  resolve_mode never asked for the record gather above, which is said here as well)
+        #  resolve_mode never asked for the record gather above, which is said here as well; with FLEXAM_SP_SAGE_WINDOW=1 on top it was
+        #  asked for, and where it resolved `sage` stands)
         if windowed and ((m.sage and not sage_window_asked(env)) or (sp_window and self.fused and sage_asked(env) and not m.sage)):      # the windowed bf16 kernel runs
             m = m._replace(sage=False, sage_gather=False, sage_fused=False)
             self._smooth_k = self._smooth_v = False
@@ -468,6 +472,8 @@ class DiTEngine:
             why = None
             if not sp_window:
                 why = "the model has no window_size / window_frames"
+            elif m.sage_gather:                            # (FLEXAM_SP_SAGE_WINDOW=1)
+                why = "the MXFP8 record gather moves whole chunks"
             elif m.sp_mode != "allgather" or m.sage:
                 why = "the all-to-all over heads hands a rank every token of its heads"
             else:

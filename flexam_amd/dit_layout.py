@@ -118,6 +118,15 @@ def sp_window_asked(env) -> bool:
     return env.get("FLEXAM_SP_WINDOW", "0") == "1"
 
 
+def sp_sage_window_asked(env) -> bool:
+    """FLEXAM_SP_SAGE_WINDOW=1 (default 0): on top of FLEXAM_SP_WINDOW=1, SAGE_ATTENTION and FLEXAM_SAGE_WINDOW=1 -- it acts with all
+    three only -- a windowed self-attention under the K|V gather exchanges the MXFP8 records as an unmasked model does and runs the
+    windowed MXFP8 kernel at each rank's query offset on them (flexam_attn_fwd_fp8_window_at; dit_sp.RecordGather) instead of gathering
+    bf16 K|V for the windowed bf16 kernel.  Not a field of _Mode: with it the mode keeps `sage` / `sage_gather`, without it
+    DiTEngine._mode never asks resolve_mode for the record gather, so the two forwards differ in their mode and their launch plans."""
+    return (env.get("FLEXAM_SP_SAGE_WINDOW", "0") == "1" and sp_window_asked(env) and sage_asked(env) and sage_window_asked(env))
+
+
 def sp_halo_asked(env) -> bool:
     """FLEXAM_SP_HALO=1 (default 0): under FLEXAM_SP_WINDOW=1, the K|V gather and the bf16 kernel, a rank receives only the key rows its
     windowed call visits (halo_plan) into a compact buffer and runs flexam_attn_fwd_window_halo on it (dit_sp.KVHalo).  Not a field of
@@ -188,8 +197,8 @@ def resolve_mode(env, *, fused, nl, nh, hd, dim, table_limit, fp8, sp, rank, par
     # VIDEOX_ATTENTION_TYPE=SAGE_ATTENTION under the K|V gather (one gather, waited for): the ranks exchange their MXFP8 key / value
     # RECORDS (one per 64 keys) instead of bf16 rows, so every chunk is a whole number of 64-key tiles: the padding unit is 64 x ranks
     asked = sage_asked(env)
-    # (record_gather = False: the caller cannot use the gathered records -- a windowed model, whose mask flexam_attn_fwd_fp8_chunked does
-    #  not take -- and the bf16 K|V gather runs, padded to the ranks alone)
+    # (record_gather = False: the caller does not use the gathered records -- a windowed model without FLEXAM_SP_SAGE_WINDOW=1, whose mask
+    #  flexam_attn_fwd_fp8_chunked does not take -- and the bf16 K|V gather runs, padded to the ranks alone)
     sage_gather = asked and fused and sp > 1 and sp_mode == "allgather" and overlap == 0 and pieces == 1 and record_gather
     Lp, lc, tok0 = token_layout(L, sp, rank, sp * hip.ATTN_KV_TILE if sage_gather else sp)
     # quantised self-attention on one rank: MXFP8 operands of the rank's tokens.  Sequence parallel with the all-to-all over heads:

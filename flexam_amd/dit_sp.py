@@ -279,4 +279,7 @@ class RecordGather:
         bufs = eng._attn8_buffers(m.B, m.lc)
         eng._norm_rope_qk(p, m, ws, m.B, bufs)
         hip.host_op(lambda: all_gather_into_tensor(kv8_all.view(m.sp * m.B, *bufs[2].shape[1:]), bufs[2], group=group))
-        hip.attn_fwd_fp8_chunked(bufs[0], bufs[1], kv8_all, m.lc, eng.cond["L"], out=eng._heads(m, ws)[3])
+        # a windowed model (FLEXAM_SP_SAGE_WINDOW=1): the mask at this rank's query offset, on the same records
+        window, sink, T = eng._window_mask() or ((-1, -1), 0, 0)
+        hip.attn_fwd_fp8_chunked(bufs[0], bufs[1], kv8_all, m.lc, eng.cond["L"], out=eng._heads(m, ws)[3], window=window, sink=sink,
+                                 frame_tokens=T, q_offset=m.tok0)

@@ -878,10 +878,13 @@ def attn_fwd_fp8(bufs, L, out=None, kv_splits=None, split_from_unit=None, o_shif
     return out
 
 
-def attn_fwd_fp8_chunked(q8, qs, kv8_chunks, lq, lk, out=None):
+def attn_fwd_fp8_chunked(q8, qs, kv8_chunks, lq, lk, out=None, window=(-1, -1), sink=0, frame_tokens=0, q_offset=0, o_shift=None):
     """Attention of `lq` local queries (q8 / qs of attn_fp8_buffers(B, H, lq)) over `lk` keys whose MXFP8 records come in CHUNKS:
     kv8_chunks uint8 [n_chunks, B, H, chunk_tiles, ATTN8_REC_BYTES], chunk c holding the keys [c, c + 1) * chunk_tiles * 64 -- the
-    rank-major result of all-gathering every sequence-parallel rank's own records.  -> out [B, lq, H, 128] bf16."""
+    rank-major result of all-gathering every sequence-parallel rank's own records.  -> out [B, lq, H, 128] bf16.
+    window / sink / frame_tokens / q_offset: attn_fwd_window's mask with row i of the call as global token q_offset + i
+    (flexam_attn_fwd_fp8_window_at: whole work units; a row that sees no key is zeros); o_shift goes with a window only.  The defaults
+    make the call this function has always made."""
     B, H, D = q8.shape[0], q8.shape[1], ATTN_HEAD_DIM
     for t, (shape, dt) in zip((q8, qs), _fp8_operands(B, H, lq)):
         if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
@@ -897,6 +900,14 @@ def attn_fwd_fp8_chunked(q8, qs, kv8_chunks, lq, lk, out=None):
     _packed_heads("attn_fwd_fp8_chunked", out)
     if tuple(out.shape) != (B, lq, H, D):
         raise RuntimeError(f"attn_fwd_fp8_chunked: out must be [B={B}, L={lq}, H={H}, {D}] with heads packed along the row, got {tuple(out.shape)}")
+    left, right = attn_window(window)
+    if (left, right) != (-1, -1):
+        shift = _k_shift("attn_fwd_fp8_chunked", o_shift, B, H * D, q8.device, "o_shift") if o_shift is not None else None
+        _call("flexam_attn_fwd_fp8_window_at", _raw(q8), _raw(qs), _raw(kv8_chunks), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, lq, lk,
+              chunk_tiles, D, left, right, int(sink), int(frame_tokens), int(q_offset), shift)
+        return out
+    if o_shift is not None:
+        raise RuntimeError("attn_fwd_fp8_chunked: o_shift goes with a window (the unmasked chunked call takes none)")
     _call("flexam_attn_fwd_fp8_chunked", _raw(q8), _raw(qs), _raw(kv8_chunks), _ptr(out, BF16), out.stride(0), out.stride(1), B, H, lq, lk,
           chunk_tiles, D, *_fp8_split_words(q8.device, None, None, B * H, lq, lk))
     return out

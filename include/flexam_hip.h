@@ -318,6 +318,24 @@ int flexam_attn_fwd_fp8_chunked(const void* q8, const void* qs, const void* kv8,
 int flexam_attn_fwd_fp8_window(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs, int B, int H, int L,
                                int head_dim, int window_left, int window_right, int sink, int frame_tokens, const float* o_shift,
                                void* stream);
+/* flexam_attn_fwd_fp8_window at a query offset, on the chunked records of flexam_attn_fwd_fp8_chunked: a rank's call under sequence
+ * parallelism and the MXFP8 record gather.  The semantics are flexam_attn_fwd_window_at's: row i of the call is global token
+ * g = q_offset + i and sees key j (0 <= j < Lk) iff j < sink or lo(g) <= j <= hi(g), lo / hi of flexam_attn_fwd_fp8_window taken at g; a
+ * negative side is unbounded and window_left < 0 drops the sink.  q_offset + Lq may exceed Lk: the rows from global token Lk on are pad
+ * rows, queries and never keys.  A row that sees no key is written as zeros (with o_shift as well: not as the shift), and a work unit
+ * none of whose rows sees a key reads no record.  q8 / qs as for flexam_attn_fwd_fp8_chunked (L = Lq); kv8 = [n_chunks][B][H][chunk_tiles]
+ * records.  The kernels are two further instances of the MXFP8 kernel under their own symbols (attn8_window_at_kernel,
+ * attn8_window_at_oshift_kernel), whose argument is the four window words and q_offset; the first-reference rule, the cap and the whole
+ * units are those of flexam_attn_fwd_fp8_window.  Normalisations, each the very launch named: q_offset = 0, Lq == Lk and chunk_tiles =
+ * ceil(Lk / 64) (one chunk that holds exactly the call's tiles) is flexam_attn_fwd_fp8_window; a window that clips no row of THIS call
+ * on either side, or sink >= Lk, is flexam_attn_fwd_fp8_chunked at kv_splits = 1 -- which takes no output shift, so that case with
+ * o_shift != NULL is FLEXAM_E_ARG.  q_offset < 0, sink < 0, frame_tokens < 0 and chunk_tiles <= 0 are FLEXAM_E_ARG.  The number of
+ * chunks is not an argument: that Lk fits the chunks the buffer holds is the caller's to check (hip.attn_fwd_fp8_chunked does, against
+ * the tensor's shape). */
+int flexam_attn_fwd_fp8_window_at(const void* q8, const void* qs, const void* kv8, void* o, int64_t o_bs, int64_t o_rs,
+                                  int B, int H, int Lq, int Lk, int chunk_tiles, int head_dim,
+                                  int window_left, int window_right, int sink, int frame_tokens, int q_offset,
+                                  const float* o_shift, void* stream);
 
 /* out_bf16[m,:] = LN(x_f32[m,:]; eps) [* ln_w + ln_b] [* scale[row(m),:] + shift[row(m),:]]
  * row(m) = row_index[m] if row_index else m / rows_per_batch; scale rows already hold (1+scale),

@@ -46,8 +46,16 @@ launch is timed beside the q_offset launch on the full keys, three arms per roun
 `halo_over_at` the halo median over the pooled full-key median, `slower_beyond_margin` says whether it exceeds 1 + margin.  Beside
 them the planned rows: the buffer's, the remote rows a rank receives, and the Lk - Lq the gather moves.  No condition.
 
+--rank-of=N --sage: the frame windows +-2 / +-5 / +-12 (sink 0 and 448) under the MXFP8 kernel at a rank's shape under the record gather
+(FLEXAM_SP_SAGE_WINDOW=1's launch, hip.attn_fwd_fp8_chunked(..., window=, q_offset=)) -> profiles/attn_window_sp_sage_bench.json.
+Lq = 64 ceil(11648 / (64 N)) rows a rank (1472 at N = 8: the record padding, not the bf16 gather's 1456), the records of every rank's
+chunk stacked rank-major, ranks 0, N / 2 and N - 1.  Per rank the unmasked MXFP8 launch a rank runs today (hip.attn_fwd_fp8_chunked)
+and, per mask, the windowed MXFP8 launch beside the windowed bf16 launch of the same mask on the same rows (hip.attn_fwd_window(...,
+q_offset=)), alternating inside every round; per arm its spread against itself.  No condition.
+
 usage: attn_window_bench.py [--iters=10] [--rounds=7] [--out=profiles/attn_window_bench.json]
        attn_window_bench.py --rank-of=8 [--out=profiles/attn_window_sp_bench.json]
+       attn_window_bench.py --rank-of=8 --sage [--out=profiles/attn_window_sp_sage_bench.json]
        attn_window_bench.py --rank-of=8 --halo [--out=profiles/attn_window_halo_bench.json]
        attn_window_bench.py --sage [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sage_bench.json]
        attn_window_bench.py --sink=0,448,896 [--base=path/to/parent/libflexam_hip.so] [--out=profiles/attn_window_sink_bench.json]
@@ -303,6 +311,69 @@ def halo_bench(N):
     print("wrote", path)
 
 
+def rank_sage_bench(N):
+    """--rank-of=N --sage: see the module docstring."""
+    tile = H.ATTN_KV_TILE
+    lc = tile * -(-L // (tile * N))                    # resolve_mode pads the record gather to 64 x ranks
+    pad = lambda t: torch.cat([t, torch.zeros(B, N * lc - L, heads, D, dtype=t.dtype, device=t.device)], dim=1)
+    q_pad, k_pad, v_pad = pad(q), pad(k), pad(v)
+    packed = [H.attn_fp8_pack(*(t[:, r * lc:(r + 1) * lc] for t in (q_pad, k_pad, v_pad))) for r in range(N)]
+    recs = torch.stack([p[2] for p in packed]).contiguous()      # [N][B][H][lc / 64] records, rank-major: what the all-gather leaves
+    out = torch.empty(B, lc, heads, D, dtype=torch.bfloat16, device="cuda")
+    masks = [(f"frames_{n}_{n}_sink_{s}", (n, n), s, FRAME) for n in (2, 5, 12) for s in (0, FRAME)]
+    units, n_tiles = H.attn_units(B * heads, lc), H.attn_kv_tiles(L)
+    rec = dict(shape=dict(B=B, H=heads, Lk=L, Lq=lc, ranks=N, chunk_tiles=lc // tile, head_dim=D, frame_tokens=FRAME), work_units=units, iters=iters,
+               rounds=rounds, device=torch.cuda.get_device_name(0),
+               note=f"Lq = {lc} rows a rank: the record gather pads the sequence to 64 x ranks; the bf16 K|V gather's chunk is {-(-L // N)} rows "
+                    f"(profiles/attn_window_sp_bench.json).  The bf16 arm here runs on the same {lc} rows at the same offset, so the two windowed "
+                    "launches of a mask do the same work",
+               bytes_per_key_and_head=dict(mxfp8_records=288, bf16_rows=512, note="whole chunks travel either way"),
+               method="one process, per rank the unmasked MXFP8 launch on the gathered records (hip.attn_fwd_fp8_chunked: the launch a rank runs "
+                      "today, tail split and merge included) and, per mask, the windowed MXFP8 launch at the rank's offset "
+                      "(hip.attn_fwd_fp8_chunked(..., window=, q_offset=)) and the windowed bf16 launch of the same mask and rows "
+                      "(hip.attn_fwd_window(..., q_offset=)) alternating per round, device events around `iters` back-to-back launches, median "
+                      "over the rounds; ms_min / ms_max: the arm's spread against itself; tile_share: hip.attn_window_at_tiles over (query "
+                      "blocks x key tiles)",
+               not_measured=["no multi-GPU run", "no link time", "no in-step figure", "no quality figure on a real checkpoint"], ranks={})
+    for rank in sorted({0, N // 2, N - 1}):
+        off = rank * lc
+        q8, qs = packed[rank][0], packed[rank][1]
+        qr = q_pad[:, off:off + lc]
+        calls = {"full": lambda: H.attn_fwd_fp8_chunked(q8, qs, recs, lc, L, out=out)}
+        for name, w, s, ft in masks:
+            calls[name] = lambda w=w, s=s, ft=ft: H.attn_fwd_fp8_chunked(q8, qs, recs, lc, L, out=out, window=w, sink=s, frame_tokens=ft, q_offset=off)
+            calls[name + "/bf16"] = lambda w=w, s=s, ft=ft: H.attn_fwd_window(qr, k, v, w, out=out, prescaled=True, sink=s, frame_tokens=ft, q_offset=off)
+        for fn in calls.values():                      # warm-up: every instance once
+            fn()
+        torch.cuda.synchronize()
+        ms = {name: [] for name in calls}
+        for _ in range(rounds):
+            for name, fn in calls.items():
+                ms[name].append(timed_call(fn))
+        med = {name: statistics.median(x) for name, x in ms.items()}
+        arms = dict(full=dict(ms=round(med["full"], 4), ms_min=round(min(ms["full"]), 4), ms_max=round(max(ms["full"]), 4)))
+        print(f"rank {rank} of {N} (rows {off} .. {off + lc - 1}), {units} work units: unmasked MXFP8 {med['full']:.3f} ms")
+        for name, w, s, ft in masks:
+            runs = H.attn_window_at_tiles(lc, L, off, w, s, ft)
+            sh = sum(b - a + 1 for r in runs for a, b in r) / (len(runs) * n_tiles)
+            t, tb = med[name], med[name + "/bf16"]
+            arms[name] = dict(window=list(w), sink=s, frame_tokens=ft, ms=round(t, 4), ms_min=round(min(ms[name]), 4), ms_max=round(max(ms[name]), 4),
+                              tile_share=round(sh, 4), time_ratio=round(t / med["full"], 4), bf16_ms=round(tb, 4), bf16_ms_min=round(min(ms[name + "/bf16"]), 4),
+                              bf16_ms_max=round(max(ms[name + "/bf16"]), 4), mxfp8_over_bf16=round(t / tb, 4),
+                              slower_than_unmasked=bool(t > med["full"]))
+            print(f"  {name:24s} {t:8.3f} ms (min {min(ms[name]):.3f}, max {max(ms[name]):.3f})  tiles {sh:6.4f}  of unmasked {t / med['full']:6.3f}  "
+                  f"bf16 same mask {tb:8.3f} ms  mxfp8 / bf16 {t / tb:6.3f}")
+        rec["ranks"][str(rank)] = dict(q_offset=off, arms=arms)
+    path = os.path.join(root, opt.get("out", "profiles/attn_window_sp_sage_bench.json"))
+    with open(path, "w") as f:
+        json.dump(rec, f, indent=1)
+        f.write("\n")
+    print("wrote", path)
+
+
+if "rank-of" in opt and "sage" in opt:
+    rank_sage_bench(int(opt["rank-of"] or 8))
+    sys.exit(0)
 if "sage" in opt:
     sage_bench()
     sys.exit(0)
